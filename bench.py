@@ -1,17 +1,22 @@
 #!/usr/bin/env python3
 """Benchmark of the VQ-VAE-WaveNet hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one full training step (forward + backward + gradient all-reduce over RCCL for
 N > 1 + TF-Adam + EMA) on synthetic 16 kHz segments, len=6656, batch=8 PER GPU (weak scaling),
 default config (encoder '64', K=512, 30-layer WaveNet), fp32 -- BASELINE.json configs[1].
-Rank 0 prints ONE JSON line: training audio-samples/s for the whole job, the roofline of the
-dominant kernel (the gated dilated conv, MFMA-bound: SURVEY.md 8(d)) measured live with HIP
-events on the launch stream, the CPU baseline (the oracle restatement timed on this box's host
-cores; rank 0 at N=1 only) and the fast-generation rate.
+Rank 0 prints ONE JSON line: training audio-samples/s for the whole job and ms_per_step.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.  That step starts
+from the seeded initial state of the model and the batch is seeded, so with the same arguments its
+inputs are the same every run and two builds can be compared output for output.
+--full adds everything beside the headline: the roofline of the dominant kernel (the gated
+dilated conv, MFMA-bound: SURVEY.md 8(d)) measured live with HIP events on the launch stream,
+the same step on the fp32-MFMA engine, the fast-generation rate, BASELINE.json configs[4] and
+the CPU baseline (the oracle restatement timed on the host cores; rank 0 at N=1 only).
 """
 import argparse
+import contextlib
 import importlib
 import json
 import os
@@ -70,7 +75,6 @@ class KernelTimers:
     def __init__(self, kernels_mod):
         self.K = kernels_mod
         self.orig = {n: getattr(kernels_mod, n) for n in ('conv_gemm', 'f16x3_gate_conv', 'f16x3_wgrad', 'f16x3_wgrad_batch', 'wgrad_gemm')}
-        self.x3 = False          # the plane engine's gate kernel was the one launched
         self.events = {'gate': [], 'wgrad': []}
         self.on = False
 
@@ -94,7 +98,6 @@ class KernelTimers:
         def gate_conv(**kw):
             if self.on:
                 self._timed('gate', o['f16x3_gate_conv'], kw, 0.0)
-                self.x3 = True
             else:
                 o['f16x3_gate_conv'](**kw)
 
@@ -156,6 +159,28 @@ def hbm_traffic(name='round1_gate_conv_traffic.json'):
 
 def log(*a):
     print('[bench]', *a, file=sys.stderr, flush=True)
+
+
+DUMP_SAMPLE = 1 << 21      # elements of each flat-buffer sample: 8 MB per file
+
+
+def dump_outputs(d, model, ws):
+    """What the last timed step hands its caller (train.py reads the same through model.losses / model.summaries /
+    model.named_gradients / model.named_parameters): the four losses and the VQ codes (float64), the encoder output z_e and
+    a fixed, seeded sample of the flat gradient and of the parameters after the update (float32); about 17 MB in all."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    model.finish_steps()
+    pick = torch.randint(0, model.n_flat, (min(DUMP_SAMPLE, model.n_flat),), generator=torch.Generator().manual_seed(0))
+    pick = pick.sort().values.to(model.grad.device)
+    out = {'losses': np.array(model.losses(ws), dtype=np.float64),              # loss, reconstruction, vq, commitment
+           'vq_indices': ws['idx'].cpu().double().numpy(),
+           'z_e': ws['z_e'].float().cpu().numpy(),
+           'grad_sample': model.grad.index_select(0, pick).float().cpu().numpy(),
+           'params_sample': model.flat.index_select(0, pick).float().cpu().numpy()}
+    for name, v in out.items():
+        np.save(os.path.join(d, name + '.npy'), v)
+    log('outputs of the last step written to %s (%s)' % (d, ', '.join(sorted(out))))
 
 
 def host_cores():
@@ -243,6 +268,9 @@ def main():
     ap.add_argument('--no-config4', action='store_true', help="skip the 5-step '2019' encoder / bf16 leg (BASELINE.json configs[4])")
     ap.add_argument('--probe-ranks', action='store_true', help='only start the ranks and report how many joined (no GPU work)')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend (nccl = RCCL; gloo only to rehearse the N>1 code path)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed as DIR/<name>.npy (rank 0)')
+    ap.add_argument('--full', action='store_true', help='beside the headline: kernel rooflines (HIP events around every launch of the '
+                    'timed steps), the fp32-engine, AR-generation, configs[4] and CPU-baseline legs (each --no-* flag drops one)')
     a = ap.parse_args()
 
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -306,39 +334,62 @@ def main():
     # the guarded engine's range flag of step k is read after step k + 1 has been enqueued (model._train_step_deferred, as
     # train.py runs it); finish_steps() inside the timed region resolves the last step's flag before the clock stops
     model.defer_guard = os.environ.get('VQW_DEFER_GUARD', '1') != '0'
-    with KernelTimers(K) as gt:
+    # the last timed step starts from the seeded initial state (parameters, Adam slots, EMA shadows, guard scales, step counter,
+    # restored on the device): a step is not bitwise reproducible (the order of its floating-point reductions varies between
+    # runs) and the steps before it train on one batch, which amplifies that, so the state they leave differs from run to run;
+    # from the restored state what the last step computes (what --dump-outputs writes) depends on the arguments alone.  The clock
+    # stops for the restore (and the drain of the pipeline before it): the last step then starts on an idle GPU, as the first does
+    init = {k: v.clone() for k, v in model.state_dict().items()}
+    # --full: HIP events around every launch of the roofline's kernel families during the timed steps (as the figures have
+    # always been taken); a plain run times the bare steps
+    with contextlib.ExitStack() as stack:
+        gt = stack.enter_context(KernelTimers(K)) if a.full else None
         for _ in range(a.warmup):
             model.train_step(x, spk)
         model.finish_steps()
         barrier()
         log('timing %d steps' % a.steps)
-        gt.on = True
+        if gt:
+            gt.on = True
         t0 = time.perf_counter()
-        for _ in range(a.steps):
-            ws = model.train_step(x, spk)
+        for _ in range(a.steps - 1):
+            model.train_step(x, spk)
         model.finish_steps()
         barrier()
         dt = time.perf_counter() - t0
-        gt.on = False
-        gate_ms = gt.mean_ms('gate')
-        gate_x3 = gt.x3
-        wg_n, wg_ms, wg_flop = gt.family('wgrad')
-        # the same kernel families once more with the step on ONE stream (outside the timed region): in the timed region the
-        # weight gradients share the chip with the backward chain's kernels, so their event brackets include the other
-        # stream's work; these are the stand-alone durations profiles/*_single_stream.csv shows
+        t1 = time.perf_counter()
+        model.load_state_dict(init)
+        barrier()
+        log('seeded state restored for the last step: %.2f ms, outside the clock' % ((time.perf_counter() - t1) * 1e3))
+        t0 = time.perf_counter()
+        ws = model.train_step(x, spk)
+        # the plane engine's gate kernel runs in this step (its plan, read before the range flag is resolved), in both modes
+        gate_x3 = bool(ws.get('x3_used'))
+        model.finish_steps()
+        barrier()
+        dt += time.perf_counter() - t0
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, model, ws)
         ss = None
-        if world == 1 and model.overlap_wgrad:
-            gt.reset()
-            model.overlap_wgrad = False
-            model.train_step(x, spk)
-            torch.cuda.synchronize()
-            gt.on = True
-            for _ in range(3):
-                model.train_step(x, spk)
-            torch.cuda.synchronize()
+        if gt:
             gt.on = False
-            model.overlap_wgrad = True
-            ss = {'gate_ms': gt.mean_ms('gate'), 'wgrad': gt.family('wgrad')}
+            gate_ms = gt.mean_ms('gate')
+            wg_n, wg_ms, wg_flop = gt.family('wgrad')
+            # the same kernel families once more with the step on ONE stream (outside the timed region): in the timed region the
+            # weight gradients share the chip with the backward chain's kernels, so their event brackets include the other
+            # stream's work; these are the stand-alone durations profiles/*_single_stream.csv shows
+            if world == 1 and model.overlap_wgrad:
+                gt.reset()
+                model.overlap_wgrad = False
+                model.train_step(x, spk)
+                torch.cuda.synchronize()
+                gt.on = True
+                for _ in range(3):
+                    model.train_step(x, spk)
+                torch.cuda.synchronize()
+                gt.on = False
+                model.overlap_wgrad = True
+                ss = {'gate_ms': gt.mean_ms('gate'), 'wgrad': gt.family('wgrad')}
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -348,7 +399,7 @@ def main():
 
     # Beside the headline: the same step on the other engine (VQW_ENGINE=fp32: the fp32-MFMA engine everywhere)
     exp = None
-    if world == 1 and not a.no_other_engine and model.x3_guard and a.dtype == 'f32':
+    if a.full and world == 1 and not a.no_other_engine and model.x3_guard and a.dtype == 'f32':
         try:
             os.environ['VQW_ENGINE'] = 'fp32'
             try:
@@ -374,7 +425,7 @@ def main():
             log('fp32-engine leg failed: %s' % exp['error'])
 
     gen = None
-    if not a.no_gen:
+    if a.full and not a.no_gen:
         gen_mod = pkg.generator
         enc = model.encode(x[:1].contiguous(), spk[:1].contiguous())          # one utterance per GPU
         g = gen_mod.FastGenerator(model, batch=1)
@@ -410,7 +461,7 @@ def main():
 
     # BASELINE.json configs[4] on this GPU: '2019' encoder, T=6400, bf16 storage + fp32 accumulate, 5 timed steps
     cfg4 = None
-    if world == 1 and not a.no_config4 and a.dtype == 'f32' and (a.encoder or m['encoder']) == '64':
+    if a.full and world == 1 and not a.no_config4 and a.dtype == 'f32' and (a.encoder or m['encoder']) == '64':
         model.free_workspaces()
         ws = None
         torch.cuda.empty_cache()
@@ -443,17 +494,6 @@ def main():
             log('configs[4] leg failed: %s' % cfg4['error'])
 
     if rank == 0:
-        R, ks = model.R, model.ks
-        flops_gate = 2.0 * B * T * (ks * R) * (2 * R)       # K1: causal dilated conv 256 -> 512, k=3 (ALGORITHMIC: SURVEY 8(d))
-        ach = flops_gate / (gate_ms * 1e-3) / 1e12
-        step_tflops = 118.14e6 * B * T * a.steps / dt / 1e12   # 118.14 MFLOP per audio sample, fwd + bwd
-
-        def wgrad_line(n, ms, flop, peak, note):
-            if not n or ms <= 0:
-                return None
-            ach_w = flop / (ms * 1e-3) / 1e12
-            return {"bound": "mfma", "kernel": note, "achieved": ach_w, "peak": peak, "unit": "TFLOP/s", "frac": ach_w / peak,
-                    "launches_per_step": n / a.steps, "ms_per_step": ms / a.steps, "flop_per_step": flop / a.steps, "traffic": None}
         rec = {
             "metric": "training audio-samples/sec", "value": B * T * a.steps * world / dt,
             "unit": "audio-samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -463,21 +503,34 @@ def main():
                                    "(fwd+bwd+allreduce+Adam+EMA)" % (m['encoder'], T, B),
                        "global_batch": B * world, "seq_len": T, "parallelism": "dp%d" % world},
             "loss": loss,
-            "roofline": {"bound": "mfma", "kernel": "conv_gemm_kernel<2,2,GATE> (dilated k=3 conv 256->512 + cond-add + tanh*sigmoid gate; LDS-DMA pipeline, half-width tail tiles)",
-                         "achieved": ach, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                         "frac": ach / PEAK_FP32_MFMA_TFLOPS, "traffic": hbm_traffic(),
-                         "ms_per_launch": gate_ms, "flop_per_launch": flops_gate,
-                         "whole_step_tflops": step_tflops, "whole_step_frac": step_tflops / PEAK_FP32_MFMA_TFLOPS},
         }
-        rec["roofline_wgrad"] = wgrad_line(wg_n, wg_ms, wg_flop, PEAK_FP32_MFMA_TFLOPS, "wgrad_kernel<2,2> (fp32 MFMA, atomics)")
+        if gt:
+            R, ks = model.R, model.ks
+            flops_gate = 2.0 * B * T * (ks * R) * (2 * R)       # K1: causal dilated conv 256 -> 512, k=3 (ALGORITHMIC: SURVEY 8(d))
+            ach = flops_gate / (gate_ms * 1e-3) / 1e12
+            step_tflops = 118.14e6 * B * T * a.steps / dt / 1e12   # 118.14 MFLOP per audio sample, fwd + bwd
+
+            def wgrad_line(n, ms, flop, peak, note):
+                if not n or ms <= 0:
+                    return None
+                ach_w = flop / (ms * 1e-3) / 1e12
+                return {"bound": "mfma", "kernel": note, "achieved": ach_w, "peak": peak, "unit": "TFLOP/s", "frac": ach_w / peak,
+                        "launches_per_step": n / a.steps, "ms_per_step": ms / a.steps, "flop_per_step": flop / a.steps, "traffic": None}
+            rec["roofline"] = {"bound": "mfma", "kernel": "conv_gemm_kernel<2,2,GATE> (dilated k=3 conv 256->512 + cond-add + tanh*sigmoid gate; LDS-DMA pipeline, half-width tail tiles)",
+                               "achieved": ach, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                               "frac": ach / PEAK_FP32_MFMA_TFLOPS, "traffic": hbm_traffic(),
+                               "ms_per_launch": gate_ms, "flop_per_launch": flops_gate,
+                               "whole_step_tflops": step_tflops, "whole_step_frac": step_tflops / PEAK_FP32_MFMA_TFLOPS}
+            rec["roofline_wgrad"] = wgrad_line(wg_n, wg_ms, wg_flop, PEAK_FP32_MFMA_TFLOPS, "wgrad_kernel<2,2> (fp32 MFMA, atomics)")
         if gate_x3 and model.bf16:   # BASELINE.json configs[4]: one bf16 MFMA per product
             rec["dtype"] = ("bf16 (decoder contraction operands stored as bf16 planes, v_mfma_f32_32x32x16_bf16, fp32 accumulate; master "
                             "weights, optimiser, residual stream, encoder, VQ and losses fp32)")
             rec["config"]["workload"] = rec["config"]["workload"].replace("fp32,", "bf16 storage + fp32 accumulate,")
-            rec["roofline"].update({"kernel": "gate_f16x3_kernel<bf16> (dilated k=3 conv 256->512 + cond-add + tanh*sigmoid gate; one bf16 plane per operand)",
-                                    "achieved": ach, "peak": PEAK_F16_MFMA_TFLOPS, "frac": ach / PEAK_F16_MFMA_TFLOPS, "traffic": None,
-                                    "whole_step_frac": step_tflops / PEAK_F16_MFMA_TFLOPS})
-            rec["roofline_wgrad"] = wgrad_line(wg_n, wg_ms, wg_flop, PEAK_F16_MFMA_TFLOPS, "wgrad_f16x3_kernel<bf16> + fp32-engine launches")
+            if gt:
+                rec["roofline"].update({"kernel": "gate_f16x3_kernel<bf16> (dilated k=3 conv 256->512 + cond-add + tanh*sigmoid gate; one bf16 plane per operand)",
+                                        "achieved": ach, "peak": PEAK_F16_MFMA_TFLOPS, "frac": ach / PEAK_F16_MFMA_TFLOPS, "traffic": None,
+                                        "whole_step_frac": step_tflops / PEAK_F16_MFMA_TFLOPS})
+                rec["roofline_wgrad"] = wgrad_line(wg_n, wg_ms, wg_flop, PEAK_F16_MFMA_TFLOPS, "wgrad_f16x3_kernel<bf16> + fp32-engine launches")
             rec["engine"] = {"name": "bf16", "steps_on_engine": model.x3_steps}
         elif gate_x3:
             # the fp16x3 engine ran.  frac = ALGORITHMIC flop / time / the peak of the pipe the kernel runs on (the
@@ -489,17 +542,18 @@ def main():
                             "of encoder layers 1-5; the Cin=1 convs, encoder layer 6 (1x1) and the condition projection on the fp32 "
                             "MFMA / VALU; the exact-fp32 engine's number for the same step is engine_fp32)")
             rec["config"]["workload"] = rec["config"]["workload"].replace("fp32,", "fp32 (fp16x3 engine),")
-            rec["roofline"].update({"kernel": "gate_f16x3_kernel<%d-row blocks> (dilated k=3 conv 256->512 + cond-add + tanh*sigmoid gate; operands as two fp16 planes, 3 MFMA terms)" % (128 if model.x3_mode_fwd & 2 else 256),
-                                    "achieved": ach, "peak": PEAK_F16_MFMA_TFLOPS, "frac": ach / PEAK_F16_MFMA_TFLOPS,
-                                    "pipe_utilisation": 3 * ach / PEAK_F16_MFMA_TFLOPS, "mfma_terms_per_product": 3,
-                                    "traffic": hbm_traffic('round3_gate_f16x3_traffic.json' if model.x3_mode_fwd & 2 else 'round2_gate_f16x3_traffic_256row_blocks.json'),
-                                    "whole_step_frac": step_tflops / PEAK_F16_MFMA_TFLOPS})
-            rec["roofline_wgrad"] = wgrad_line(wg_n, wg_ms, wg_flop, PEAK_F16_MFMA_TFLOPS,
-                                               "wgrad_f16x3_kernel + wgrad_reduce_kernel (every engine weight-gradient launch of the step: the decoder's "
-                                               "layers in batches -- all skip halves, gate kernels by six, residual halves -- with both operands read as "
-                                               "planes, the convs around the stack, encoder layers 1-5) + the 2 fp32-engine launches")
-            if rec["roofline_wgrad"]:
-                rec["roofline_wgrad"]["pipe_utilisation"] = 3 * rec["roofline_wgrad"]["frac"]
+            if gt:
+                rec["roofline"].update({"kernel": "gate_f16x3_kernel<%d-row blocks> (dilated k=3 conv 256->512 + cond-add + tanh*sigmoid gate; operands as two fp16 planes, 3 MFMA terms)" % (128 if model.x3_mode_fwd & 2 else 256),
+                                        "achieved": ach, "peak": PEAK_F16_MFMA_TFLOPS, "frac": ach / PEAK_F16_MFMA_TFLOPS,
+                                        "pipe_utilisation": 3 * ach / PEAK_F16_MFMA_TFLOPS, "mfma_terms_per_product": 3,
+                                        "traffic": hbm_traffic('round3_gate_f16x3_traffic.json' if model.x3_mode_fwd & 2 else 'round2_gate_f16x3_traffic_256row_blocks.json'),
+                                        "whole_step_frac": step_tflops / PEAK_F16_MFMA_TFLOPS})
+                rec["roofline_wgrad"] = wgrad_line(wg_n, wg_ms, wg_flop, PEAK_F16_MFMA_TFLOPS,
+                                                   "wgrad_f16x3_kernel + wgrad_reduce_kernel (every engine weight-gradient launch of the step: the decoder's "
+                                                   "layers in batches -- all skip halves, gate kernels by six, residual halves -- with both operands read as "
+                                                   "planes, the convs around the stack, encoder layers 1-5) + the 2 fp32-engine launches")
+                if rec["roofline_wgrad"]:
+                    rec["roofline_wgrad"]["pipe_utilisation"] = 3 * rec["roofline_wgrad"]["frac"]
             rec["engine"] = {"name": "f16x3", "steps_on_engine": model.x3_steps, "steps_repeated_on_fp32": model.x3_fallbacks,
                              "range_flag": "read one step late (model.defer_guard)" if model.defer_guard else "read before the optimiser (host sync per step)",
                              "host_enqueue_ms_per_step": model.host_enqueue_ms}
@@ -516,7 +570,7 @@ def main():
             rec["engine_fp32"] = exp
         if gen:
             rec["ar_gen"] = gen
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(1, T, 12)          # ~10 s of host work
             if gen:
                 rec["ar_gen"]["cpu_baseline"] = cpu_ar_baseline(128)

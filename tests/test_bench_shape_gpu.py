@@ -11,7 +11,10 @@ Bars (unchanged from tests/test_model_gpu.py): VQ indices + labels bit-exact, lo
 tensor max, gradients 5e-3 in relative L2; every GPU decision = the oracle's argmax within 2e-6 in probability.
 """
 import importlib.util
+import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -176,6 +179,48 @@ def test_batch_16_runs_on_the_fp16x3_engine(pkg, monkeypatch, capfd):
     assert not wss['x3_used']
     err = capfd.readouterr().err
     assert err.count('runs on the fp32-MFMA engine') == 1 and 'not a multiple of 256' in err
+
+
+def test_bench_plain_run_dumps_the_last_step(pkg, tmp_path):
+    """A plain `bench.py --steps K --warmup W --dump-outputs DIR` (no --full): one result line with the headline fields and none
+    of the --full legs, K timed steps, and the last step's outputs as float32 / float64 .npy files, 64 MB at most in all; the
+    loss it dumps is the loss it prints.  The last timed step starts from the seeded initial state, so what it dumps is what
+    the first step of a fresh model computes here, up to rounding (not every reduction of the step is order-stable; this is the
+    benchmarked batch, whose forward pass repeats exactly, while at small batches summation-order noise can flip a relu mask)."""
+    d = tmp_path / 'out'
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--dump-outputs', str(d)],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
+    assert rec['steps'] == 3 and rec['warmup'] == 1 and rec['metric'] == 'training audio-samples/sec' and rec['higher_is_better']
+    assert rec['ms_per_step'] > 0 and abs(rec['value'] - 8 * 6656 / (rec['ms_per_step'] * 1e-3)) < 1e-6 * rec['value']
+    assert rec['dtype'].startswith('f32 via fp16x3') and rec['engine']['name'] == 'f16x3'
+    # every step it ran (1 warm-up + 3 timed, the last from the restored state) on the guarded engine, none repeated on fp32
+    assert rec['engine']['steps_on_engine'] == 4 and rec['engine']['steps_repeated_on_fp32'] == 0
+    assert not {'roofline', 'roofline_wgrad', 'engine_fp32', 'ar_gen', 'config4_bf16', 'cpu_baseline'} & set(rec)
+    files = sorted(d.iterdir())
+    assert {f.name for f in files} == {'losses.npy', 'vq_indices.npy', 'z_e.npy', 'grad_sample.npy', 'params_sample.npy'}
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    for f in files:
+        v = np.load(str(f))
+        assert v.dtype in (np.float32, np.float64) and v.size and np.isfinite(v).all(), f.name
+    assert np.load(str(d / 'losses.npy'))[0] == rec['loss']
+    assert np.load(str(d / 'vq_indices.npy')).shape == (8, 6656 // 64)
+    bench = _bench()
+    m, w = bench.default_configs()
+    model = pkg.model.VQVAE(m, w, 109, device='cuda', seed=0)
+    x, spk = bench.synthetic_batch(8, 6656, 109, 1234, 'cuda')
+    ws = model.train_step(x, spk)
+    bench.dump_outputs(str(tmp_path / 'here'), model, ws)
+    got = {f.name: np.load(str(f)) for f in files}
+    want = {f.name: np.load(str(f)) for f in (tmp_path / 'here').iterdir()}
+    np.testing.assert_allclose(got['losses.npy'], want['losses.npy'], rtol=1e-5)
+    assert np.array_equal(got['vq_indices.npy'], want['vq_indices.npy'])
+    for name, tol in (('z_e.npy', 1e-5), ('grad_sample.npy', 1e-4), ('params_sample.npy', 1e-6)):
+        err = np.abs(got[name].astype(np.float64) - want[name]).max() / np.abs(want[name]).max()
+        assert err < tol, '%s: %.3e of the tensor max' % (name, err)
+    del model, ws
+    torch.cuda.empty_cache()
 
 
 @pytest.mark.parametrize('persistent', ['1', '0'])
