@@ -9,6 +9,10 @@ fast WaveNet generator conditioned on each requested speaker, using the EMA weig
 `<dir>/<step>_<speaker>.wav` (float32, 16 kHz) plus `embedding_<step>.npy` /
 `speaker_embedding_<step>.npy` like the reference (generate.py:94-117).  Under torchrun the
 speakers are sharded over the GPUs (rows of the batch never interact).
+
+With `-prior <prior.pt> -frames N` no input utterance is needed: N VQ codes per speaker are sampled from a latent prior
+(prior.py, trained by train_prior.py), decoded through the VQ-VAE's codebook (condition_from_codes) and its fast WaveNet
+generator, and written as `<dir>/<step>_<speaker>_prior.wav` (N x 64 samples) plus `prior_codes_<step>_<speaker>.npy`.
 """
 import importlib
 import json
@@ -31,7 +35,13 @@ def main():
     parser.add_argument('-mode', default='sample', dest='mode', help='decode mode, sample or greedy')
     parser.add_argument('-params', default='model_parameters.json', dest='parameter_path', metavar='str', help='path to parameters file')
     parser.add_argument('-seed', default=None, type=int, help='seed of the sampling uniforms (reference: unseeded)')
+    parser.add_argument('-prior', dest='prior_path', help='latent prior weights (train_prior.py): sample codes instead of encoding -audio')
+    parser.add_argument('-frames', default=256, type=int, dest='frames', help='codes to sample per speaker with -prior (x 64 samples)')
+    parser.add_argument('-prior_params', default='prior_parameters.json', dest='prior_params', metavar='str',
+                        help='the prior\'s parameters file (with -prior)')
     args = parser.parse_args()
+    if args.prior_path is None and args.audio_path is None:
+        parser.error('-audio is required (or -prior to sample codes from a latent prior)')
     if args.mode not in ('sample', 'greedy'):
         raise NotImplementedError('decode mode %s not implemented' % args.mode)
 
@@ -44,6 +54,8 @@ def main():
 
     gs = int(args.restore_path.split('-')[-1].split('.')[0])
     from scipy.io import wavfile
+    if args.prior_path is not None:
+        return generate_from_prior(args, pkg, gs, rank, world, dev)
     sr, wav = wavfile.read(args.audio_path)
     if wav.ndim > 1:
         wav = wav[:, 0]
@@ -56,31 +68,10 @@ def main():
     wav = wav[:len(wav) // 512 * 512]          # generate.py:39 (512 = largest dilation)
     length = len(wav)
 
-    first = args.speakers[0]
-    if first[0] == 'p':
-        spk_file, num_speakers = 'data/vctk_speakers.txt', 109
-    elif first[0].lower() == 's':
-        spk_file, num_speakers = 'data/aishell_speakers.txt', 340
-    else:
-        spk_file, num_speakers = 'data/librispeech_speakers.txt', 251
-    speaker_to_int = pkg.data.get_speaker_to_int(spk_file) if os.path.exists(spk_file) else {}
-    # 'None' -> all-zero one-hot -> argmax 0 (generate.py:59-60, model.py:22)
-    ids = []
-    for sp in args.speakers:
-        if sp.lower() != 'none' and sp not in speaker_to_int:
-            raise ValueError('unknown speaker %r (not in %s)' % (sp, spk_file))
-        i = 0 if sp.lower() == 'none' else speaker_to_int[sp]
-        if not 0 <= i < num_speakers:
-            raise ValueError('speaker %r maps to %d, outside the %d-row speaker table' % (sp, i, num_speakers))
-        ids.append(i)
+    num_speakers, ids = speaker_ids(args, pkg)
 
     parameters, wavenet_parameters = pkg.model.load_configs(args.parameter_path)
-    model = pkg.model.VQVAE(parameters, wavenet_parameters, num_speakers, device=dev, seed=0)
-    if args.restore_path.endswith(('.safetensors', '.npz')):      # TF variable names (checkpoint.py); EMA shadows -> live
-        pkg.checkpoint.load(model, args.restore_path, ema_to_live=True)
-    else:
-        model.load_state_dict(torch.load(args.restore_path, map_location='cpu', weights_only=True))
-        model.use_ema_weights()                # generate.py:88-90
+    model = load_vqvae(args, pkg, parameters, wavenet_parameters, num_speakers, dev)
     save_path = args.restore_path.split('/weights')[0]
     if rank == 0:
         if model.use_vq:                      # generate.py:96-101
@@ -110,6 +101,73 @@ def main():
             s = 'no_speaker' if args.speakers[i] == 'None' else args.speakers[i]
             wavfile.write(save_path + '/%d_%s.wav' % (gs, s), 16000, out[j])
             print('wrote', save_path + '/%d_%s.wav' % (gs, s))
+
+
+def speaker_ids(args, pkg):
+    first = args.speakers[0]
+    if first[0] == 'p':
+        spk_file, num_speakers = 'data/vctk_speakers.txt', 109
+    elif first[0].lower() == 's':
+        spk_file, num_speakers = 'data/aishell_speakers.txt', 340
+    else:
+        spk_file, num_speakers = 'data/librispeech_speakers.txt', 251
+    speaker_to_int = pkg.data.get_speaker_to_int(spk_file) if os.path.exists(spk_file) else {}
+    # 'None' -> all-zero one-hot -> argmax 0 (generate.py:59-60, model.py:22)
+    ids = []
+    for sp in args.speakers:
+        if sp.lower() != 'none' and sp not in speaker_to_int:
+            raise ValueError('unknown speaker %r (not in %s)' % (sp, spk_file))
+        i = 0 if sp.lower() == 'none' else speaker_to_int[sp]
+        if not 0 <= i < num_speakers:
+            raise ValueError('speaker %r maps to %d, outside the %d-row speaker table' % (sp, i, num_speakers))
+        ids.append(i)
+    return num_speakers, ids
+
+
+def load_vqvae(args, pkg, parameters, wavenet_parameters, num_speakers, dev):
+    model = pkg.model.VQVAE(parameters, wavenet_parameters, num_speakers, device=dev, seed=0)
+    if args.restore_path.endswith(('.safetensors', '.npz')):      # TF variable names (checkpoint.py); EMA shadows -> live
+        pkg.checkpoint.load(model, args.restore_path, ema_to_live=True)
+    else:
+        model.load_state_dict(torch.load(args.restore_path, map_location='cpu', weights_only=True))
+        model.use_ema_weights()                # generate.py:88-90
+    return model
+
+
+def generate_from_prior(args, pkg, gs, rank, world, dev):
+    """Sample codes from the latent prior, decode them with the VQ-VAE's WaveNet (no input utterance)."""
+    from scipy.io import wavfile
+    num_speakers, ids = speaker_ids(args, pkg)
+    parameters, wavenet_parameters = pkg.model.load_configs(args.parameter_path)
+    prior_cfg = pkg.prior.load_prior_config(args.prior_params, parameters)
+    model = load_vqvae(args, pkg, parameters, wavenet_parameters, num_speakers, dev)
+    prior = pkg.prior.LatentPrior(prior_cfg, num_speakers, device=dev, seed=0, n_codes=model.Kc)
+    prior.load_state_dict(torch.load(args.prior_path, map_location='cpu', weights_only=True))
+    prior.use_ema_weights()
+    save_path = args.restore_path.split('/weights')[0]
+    mine = list(range(rank, len(ids), world))
+    n, length = args.frames, args.frames * 64
+    g = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
+    u_codes = torch.rand(len(ids), n, generator=g)[mine].contiguous().to(dev) if args.mode == 'sample' else None
+    u_audio = torch.rand(len(ids), length, generator=g)[mine].contiguous().to(dev) if args.mode == 'sample' else None
+    for b0 in range(0, len(mine), 8):
+        rows = mine[b0:b0 + 8]
+        sl = slice(b0, b0 + len(rows))
+        spk = torch.tensor([ids[i] for i in rows], dtype=torch.int64, device=dev)
+        pgen = pkg.generator.PriorGenerator(prior, batch=len(rows))
+        codes = pgen.sample(n, spk, mode=args.mode, uniforms=None if u_codes is None else u_codes[sl].contiguous())
+        pgen.close()
+        cond = model.condition_from_codes(codes, spk)
+        gen = pkg.generator.FastGenerator(model, batch=len(rows))
+        audio, _ = gen.generate(cond, length, mode=args.mode, ratio=64,
+                                uniforms=None if u_audio is None else u_audio[sl].contiguous())
+        gen.close()
+        audio, codes = audio.cpu().numpy(), codes.cpu().numpy()
+        for j, i in enumerate(rows):
+            s = 'no_speaker' if args.speakers[i] == 'None' else args.speakers[i]
+            wavfile.write(save_path + '/%d_%s_prior.wav' % (gs, s), 16000, audio[j])
+            np.save(save_path + '/prior_codes_%d_%s.npy' % (gs, s), codes[j])
+            print('wrote', save_path + '/%d_%s_prior.wav' % (gs, s))
 
 
 if __name__ == '__main__':

@@ -344,6 +344,25 @@ int vqw_ar_decode_run_group_async(vqw_ar_decoder* const* hs, int n, const float*
 /* workgroups (= CUs held for the whole run) of the handle's persistent kernel; 0: launch-per-phase path */
 int vqw_ar_decode_workgroups(const vqw_ar_decoder* h);
 int vqw_ar_decode_destroy(vqw_ar_decoder* h);
+/* Code-input mode (the latent prior over VQ codes, prior.py): the same persistent kernel with a discrete input.  w->Q is the
+ * number of codes n_codes and w->pre_w is read as [pre_k][n_codes][R] (prior/preprocess/kernel); the handle keeps its own copy.
+ * The history holds past codes and the preprocess gathers W_pre rows; the sampled index is the next input (no mu-law).
+ * reset = no code yet (a zero one-hot, not code 0).  With supplied uniforms u > cdf[n_codes-1] gives n_codes, which is no
+ * code: it is clamped to n_codes - 1.  run / run_async / run_group_async / wait / reset / destroy as above; `audio` may be
+ * NULL (as a whole or per handle), `indices` receives the codes.  Only the persistent kernel has the mode: the call fails
+ * where it does not run (VQW_AR_PERSISTENT=0, an unsupported shape). */
+int vqw_ar_prior_create(vqw_ar_decoder** out, const vqw_ar_weights* w, int batch, int channels_per_workgroup, int n_codes);
+
+/* ---- The latent prior's input stage (csrc/prior.hip).  net0[b][:][t] = b_pre + sum_{j<pre_k} w_pre[j][codes[b][t-pre_k+j]][:]
+ * (the causal conv of one_hot(shift_right(codes)); codes outside [0, k) contribute nothing); labels (may be NULL) := codes.
+ * codes int32 [B][T], w_pre [pre_k][k][R], b_pre [R], net0 [B][R][T]. */
+int vqw_prior_input_fwd(const int32_t* codes, const float* w_pre, const float* b_pre, float* net0, int32_t* labels,
+                        int B, int T, int k, int R, int pre_k, vqw_stream_t s);
+/* dw_pre[j][q][:] = sum over the positions p = b*T + s of code q (order[starts[q] .. starts[q+1]), a stable sort of the codes
+ * by value) of dnet_t[b][s + pre_k - j][:] where s + pre_k - j < T.  dnet_t [B][T][R] (dnet transposed).  Deterministic:
+ * one fixed summation order, no atomics.  Writes (does not accumulate into) dw_pre [pre_k][k][R]. */
+int vqw_prior_input_wgrad(const int32_t* order, const int32_t* starts, const float* dnet_t, float* dw_pre, int B, int T,
+                          int k, int R, int pre_k, vqw_stream_t s);
 
 /* ---- The fp16x3 engine (the default path of model.py for the decoder's residual stack): contractions
  * that are fp32-accurate on the fp16 matrix pipe.  Every operand is split into two fp16 planes (x = h1 + h2), products

@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""train_prior.py -- fit a WaveNet prior over the VQ codes of a trained VQ-VAE (prior.py), same flag style as train.py.
+
+    python3 train_prior.py -restore saved_model/weights-110640.pt -dataset VCTK -length 1024 -batch 16 \\
+        -step 100000 -save saved_prior/prior
+
+Every step encodes fresh audio crops of `length` x 64 samples with the VQ-VAE's EMA weights (encoder + VQ: one code per 64
+samples) and runs one prior training step on those codes and their speakers.  Checkpoints are `<save>-<step>.pt` (+ a
+`<name>.json` with the prior's config and speaker count).  One GPU: data-parallel prior training is not supported.
+"""
+import importlib
+import json
+import os
+import sys
+import time
+from argparse import ArgumentParser
+
+import torch
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    parser = ArgumentParser()
+    parser.add_argument('-restore', dest='vqvae_path', required=True, metavar='string', help='trained VQ-VAE weights (<save>-<step>.pt)')
+    parser.add_argument('-prior_restore', dest='prior_path', metavar='string', help='prior weights to resume from')
+    parser.add_argument('-dataset', default='VCTK', type=str, help='VCTK or LibriSpeech or Aishell (or synthetic)', metavar='DATASET')
+    parser.add_argument('-length', default=1024, type=int, dest='frames', metavar='int', help='code frames per crop (x 64 audio samples)')
+    parser.add_argument('-step', default=100000, type=int, dest='num_steps', metavar='int', help='number of steps to train')
+    parser.add_argument('-batch', default=16, type=int, dest='batch_size', metavar='int', help='batch size')
+    parser.add_argument('-interval', default=200, type=int, dest='interval', metavar='int', help='log every interval step')
+    parser.add_argument('-save', default='saved_prior/prior', dest='save_path', metavar='string', help='path to save weights')
+    parser.add_argument('-params', default='prior_parameters.json', dest='prior_params', metavar='str', help='prior parameters file')
+    parser.add_argument('-vqvae_params', default='model_parameters.json', dest='vqvae_params', metavar='str',
+                        help='the VQ-VAE\'s parameters file')
+    args = parser.parse_args()
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise NotImplementedError('train_prior.py runs on one GPU (multi-GPU prior training is not supported)')
+
+    pkg = importlib.import_module('vq-vae-wavenet_amd')
+    vq_cfg, vq_wavenet = pkg.model.load_configs(args.vqvae_params)
+    prior_cfg = pkg.prior.load_prior_config(args.prior_params, vq_cfg)     # k and the encoder ratio are checked here
+    if args.frames % pkg.prior.CODES_PER_FRAME:
+        raise ValueError('-length must be a multiple of %d code frames' % pkg.prior.CODES_PER_FRAME)
+    dev = torch.device('cuda', 0)
+    torch.cuda.set_device(dev)
+
+    D = pkg.data
+    T_audio = args.frames * 64
+    dargs = dict(batch_size=args.batch_size, max_len=T_audio, device=dev)
+    if args.dataset == 'VCTK':
+        dataset = D.VCTK(relative_path='data/', **dargs)
+    elif args.dataset == 'LibriSpeech':
+        dataset = D.LibriSpeech(relative_path='data/', **dargs)
+    elif args.dataset == 'Aishell':
+        dataset = D.Aishell(relative_path='data/', **dargs)
+    elif args.dataset == 'synthetic':
+        dataset = D.Synthetic(seed=1234, **dargs)
+    else:
+        raise NotImplementedError('dataset %s not implemented' % args.dataset)
+    dataset = D.Prefetcher(dataset, depth=3, device=dev)
+
+    vqvae = pkg.model.VQVAE(vq_cfg, vq_wavenet, dataset.num_speakers, device=dev, seed=0)
+    vqvae.load_state_dict(torch.load(args.vqvae_path, map_location='cpu', weights_only=True))
+    vqvae.use_ema_weights()                    # codes of the EMA weights, as generate.py decodes with
+    prior = pkg.prior.LatentPrior(prior_cfg, dataset.num_speakers, device=dev, seed=0, n_codes=vqvae.Kc)
+    if args.prior_path is not None:
+        prior.load_state_dict(torch.load(args.prior_path, map_location='cpu', weights_only=True))
+    prior.defer_guard = os.environ.get('VQW_DEFER_GUARD', '1') != '0'
+    gs = prior.global_step
+    print('[restore] last global step: %d, learning rate: %.5f' % (gs, prior.lr_at(gs)))
+    save_dir, save_name = os.path.split(args.save_path)
+    if save_dir and not os.path.isdir(save_dir):
+        os.makedirs(save_dir)
+
+    for step in range(1, 1 + args.num_steps):
+        t = time.time()
+        x, spk = dataset.next()
+        codes = vqvae.encode_codes(x, spk)       # [B][frames] int32
+        prior.train_step(codes, spk)
+        gs = prior.global_step
+        if gs % args.interval == 0 or step == args.num_steps:
+            ws = prior._workspace(args.batch_size, args.frames)
+            loss = prior.losses(ws)[0]             # synchronises: only every `interval` steps
+            t = time.time() - t
+            print('\r[step %d] %.2f%% [prior %.5f] [lr %.5f] [BATCH %.3fs]     '
+                  % (gs, step / args.num_steps * 100, loss, prior.lr_at(gs - 1), t), end='', flush=True)
+    torch.cuda.synchronize()
+    path = '%s-%d.pt' % (args.save_path, prior.global_step)
+    torch.save(prior.state_dict(), path)
+    with open(os.path.join(save_dir or '.', save_name + '.json'), 'w') as f:
+        json.dump({'prior': prior_cfg, 'num_speakers': dataset.num_speakers}, f)
+    print('\nsaved', path)
+    dataset.close()
+
+
+if __name__ == '__main__':
+    main()

@@ -153,6 +153,9 @@ SIGNATURES = {
                                            C.POINTER(_fp), C.POINTER(_fp), _fp]),
     'vqw_ar_decode_workgroups': (_i, [_fp]),
     'vqw_ar_decode_destroy': (_i, [_fp]),
+    'vqw_ar_prior_create': (_i, [C.POINTER(_fp), C.POINTER(ArWeights), _i, _i, _i]),
+    'vqw_prior_input_fwd': (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp]),
+    'vqw_prior_input_wgrad': (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp]),
     'vqw_f16x3_amax': (_i, [_fp, _i64, _i, _i64, _i64, _i, _fp, _fp, _fp]),
     'vqw_f16x3_update_scales': (_i, [_fp, _fp, _i, _i, _i, _fp, _fp]),
     'vqw_f16x3_update_scales_guarded': (_i, [_fp, _fp, _i, _i, _i, _fp, _fp, _fp]),

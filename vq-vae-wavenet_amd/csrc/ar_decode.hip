@@ -328,6 +328,7 @@ struct vqw_ar_decoder {
     ArPersist* persist = nullptr;  // persistent single-launch generator (default model shapes)
     bool pending = false;          // a run has been enqueued and not yet waited for
     hipStream_t run_stream = nullptr;   // the stream that run was enqueued on (a group run: the first handle's)
+    int n_codes = 0;               // > 0: code-input mode of the latent prior (persistent kernel only, vqw_ar_prior_create)
 };
 
 namespace {
@@ -402,11 +403,13 @@ void free_all(vqw_ar_decoder* h) {
 
 }  // namespace
 
+static int ar_create(vqw_ar_decoder** out, const vqw_ar_weights* w, int batch, int channels_per_workgroup, int n_codes);
+
 extern "C" int vqw_ar_decode_create(vqw_ar_decoder** out, const vqw_ar_weights* w, int batch) {
     return vqw_ar_decode_create_ex(out, w, batch, 0);
 }
 
-extern "C" int vqw_ar_decode_create_ex(vqw_ar_decoder** out, const vqw_ar_weights* w, int batch, int channels_per_workgroup) {
+static int ar_create(vqw_ar_decoder** out, const vqw_ar_weights* w, int batch, int channels_per_workgroup, int n_codes) {
     VQW_CHECK(out && w, "vqw_ar_decode_create: null pointer");
     VQW_CHECK(channels_per_workgroup == 0 || channels_per_workgroup == 4 || channels_per_workgroup == 8,
               "vqw_ar_decode_create_ex: channels_per_workgroup is 0 (auto), 4 or 8 (got %d)", channels_per_workgroup);
@@ -453,13 +456,27 @@ extern "C" int vqw_ar_decode_create_ex(vqw_ar_decoder** out, const vqw_ar_weight
         free_all(h);
         return vqw_set_error("vqw_ar_decode_create: stream/event creation failed");
     }
+    h->n_codes = n_codes;
     if (arp_supported(w, batch)) {
         const int rc = arp_create(&h->persist, w, h->dil.data(), h->gated_w.data(), h->gated_b.data(), h->out_w.data(),
-                                  h->out_b.data(), batch, channels_per_workgroup);
+                                  h->out_b.data(), batch, channels_per_workgroup, n_codes);
         if (rc) { free_all(h); return rc; }
+    } else if (n_codes > 0) {
+        free_all(h);
+        return vqw_set_error("vqw_ar_prior_create: code-input mode needs the persistent generator, which does not run here "
+                             "(VQW_AR_PERSISTENT=0, or a shape / batch it does not support); the launch-per-phase path has no code input");
     }
     *out = h;
     return vqw_ar_decode_reset(h, nullptr);
+}
+
+extern "C" int vqw_ar_decode_create_ex(vqw_ar_decoder** out, const vqw_ar_weights* w, int batch, int channels_per_workgroup) {
+    return ar_create(out, w, batch, channels_per_workgroup, 0);
+}
+
+extern "C" int vqw_ar_prior_create(vqw_ar_decoder** out, const vqw_ar_weights* w, int batch, int channels_per_workgroup, int n_codes) {
+    VQW_CHECK(w && n_codes > 0 && n_codes == w->Q, "vqw_ar_prior_create: n_codes=%d must be > 0 and equal w->Q", n_codes);
+    return ar_create(out, w, batch, channels_per_workgroup, n_codes);
 }
 
 extern "C" int vqw_ar_decode_reset(vqw_ar_decoder* h, vqw_stream_t s) {
@@ -601,11 +618,14 @@ extern "C" int vqw_ar_decode_run_group_async(vqw_ar_decoder* const* hs, int n, c
                                              int ratio, int n_steps, int mode, const float* const* uniforms,
                                              float* const* audio, int32_t* const* indices,
                                              float* const* probs_last, vqw_stream_t s) {
-    VQW_CHECK(hs && encoding && audio && n >= 1 && n <= 8, "vqw_ar_decode_run_group: null pointer or n=%d outside 1..8", n);
+    VQW_CHECK(hs && encoding && (audio || (hs[0] && hs[0]->n_codes > 0)) && n >= 1 && n <= 8,
+              "vqw_ar_decode_run_group: null pointer or n=%d outside 1..8", n);
     VQW_CHECK(Tz > 0 && ratio > 0 && n_steps > 0, "vqw_ar_decode_run: bad Tz/ratio/n_steps");
     VQW_CHECK(mode == 0 || (mode == 1 && uniforms), "vqw_ar_decode_run: mode must be 0 (greedy) or 1 (sample, needs uniforms)");
     for (int i = 0; i < n; ++i) {
-        VQW_CHECK(hs[i] && encoding[i] && audio[i] && (mode == 0 || uniforms[i]), "vqw_ar_decode_run_group: null pointer (handle %d)", i);
+        VQW_CHECK(hs[i] && encoding[i] && (hs[i]->n_codes > 0 || audio[i]) && (mode == 0 || uniforms[i]),
+                  "vqw_ar_decode_run_group: null pointer (handle %d)", i);
+        VQW_CHECK(hs[i]->n_codes == hs[0]->n_codes, "vqw_ar_decode_run_group: handles of one launch must share the input mode");
         VQW_CHECK(hs[i]->persist && arp_same_launch(hs[0]->persist, hs[i]->persist),
                   "vqw_ar_decode_run_group: every handle must run the same persistent kernel (start the others one by one)");
         for (int j = 0; j < i; ++j) VQW_CHECK(hs[j] != hs[i], "vqw_ar_decode_run_group: handle %d given twice", i);

@@ -66,7 +66,9 @@ struct PArgs {
     u64* rings;                   // sum_l depth_l * B * R granules: layer inputs == dilation queues
     const float* const* cond;     // [L+1] this run's condition projections ([B][2R][Tz] ..., [B][S][Tz])
     u64 *ex_g, *ex_s, *ex_h, *ex_l;  // [2][B][R] (phase parity), [B][S], [B][S], [B][Q]
-    float* xhist;                 // [B][pre_k] encoded input history (state across runs)
+    float* xhist;                 // [B][pre_k] encoded input history (state across runs); code mode: code + 1, 0 = no code
+    int n_codes;                  // > 0: code-input mode (latent prior): the input is the sampled index, no mu-law
+    const float* prew;            // code mode: [pre_k][n_codes][R] preprocess kernel (the handle's copy)
     float* prev;                  // [B] last decoded sample
     int* state;                   // [0] = step, [1] = error
     int Tz, ratio, mode, n_steps;
@@ -307,6 +309,17 @@ __device__ __forceinline__ void decode_rows(const PArgs& a, int bi, int tid, int
                     if (cdf < u) idx = q + 1;
                 }
             }
+            if (a.n_codes) {
+                // code mode: u > cdf[Q-1] (the float sum of the probabilities may end below 1) gives Q, which is no code:
+                // clamp it to the last code.  The code itself is the next input (stored as code + 1; 0 = no code yet).
+                if (idx > Q - 1) idx = Q - 1;
+                xh[b * a.pre_k + ((t + 1) % a.pre_k)] = (float)(idx + 1);
+                if (bi == 0) {
+                    if (a.audio) a.audio[(size_t)b * a.n_steps + it] = (float)idx;
+                    if (a.indices) a.indices[(size_t)b * a.n_steps + it] = idx;
+                }
+                continue;
+            }
             const float dec = dtab[idx];                   // p_mu_dec(idx), p_mu_enc(that): tabulated once per launch
             xh[b * a.pre_k + ((t + 1) % a.pre_k)] = dtab[Q + 1 + idx];
             if (bi == 0) {
@@ -380,7 +393,8 @@ __global__ __launch_bounds__(NTHR, 1) void ar_persist_kernel(const PGroup grp) {
         lds[cv.dtab + Q + 1 + i] = p_mu_enc(dec);
     }
     __syncthreads();
-    if (tid < B) xh[tid * a.pre_k + (t0 % a.pre_k)] = p_mu_enc(a.prev[tid]);   // x_in(t0) = mu_law_encode(previous sample)
+    if (tid < B && !a.n_codes) xh[tid * a.pre_k + (t0 % a.pre_k)] = p_mu_enc(a.prev[tid]);   // x_in(t0) = mu_law_encode(previous sample)
+    // (code mode: the history saved by the last run already holds the previous code, or 0 = none after a reset)
     __syncthreads();
 
     const int PH = L + 4;                                 // tags of a step: gated_p (p < L), skip, h, logits
@@ -426,12 +440,24 @@ __global__ __launch_bounds__(NTHR, 1) void ar_persist_kernel(const PGroup grp) {
                 for (int b = 0; b < TB; ++b) {
                     if (b < B) {
                         float acc = 0.0f;
-                        for (int i = 0; i < cv.n_pre; ++i) {
-                            const int j = kl + LPC * i;
-                            if (j < a.pre_k) {
-                                int slot = tm1 + j;
-                                if (slot >= a.pre_k) slot -= a.pre_k;
-                                acc = fmaf(hw_pre[i * NCT + ct], xh[b * a.pre_k + slot], acc);
+                        if (a.n_codes) {           // code mode: tap j adds row W_pre[j][code] (a one-hot input), none for "no code"
+                            for (int i = 0; i < cv.n_pre; ++i) {
+                                const int j = kl + LPC * i;
+                                if (j < a.pre_k) {
+                                    int slot = tm1 + j;
+                                    if (slot >= a.pre_k) slot -= a.pre_k;
+                                    const int code = (int)xh[b * a.pre_k + slot] - 1;
+                                    if (code >= 0 && code < a.n_codes) acc += a.prew[((size_t)j * a.n_codes + code) * R + c];
+                                }
+                            }
+                        } else {
+                            for (int i = 0; i < cv.n_pre; ++i) {
+                                const int j = kl + LPC * i;
+                                if (j < a.pre_k) {
+                                    int slot = tm1 + j;
+                                    if (slot >= a.pre_k) slot -= a.pre_k;
+                                    acc = fmaf(hw_pre[i * NCT + ct], xh[b * a.pre_k + slot], acc);
+                                }
                             }
                         }
                         cur[b] = chan_sum<LPC>(acc) + bs[cv.bias_head + (NS + nQ) * CPB + cg];
@@ -912,7 +938,8 @@ bool arp_supported(const vqw_ar_weights* w, int batch) {
 }
 
 int arp_create(ArPersist** out, const vqw_ar_weights* w, const int* dil, const float* const* gated_w,
-               const float* const* gated_b, const float* const* out_w, const float* const* out_b, int batch, int cpb_want) {
+               const float* const* gated_b, const float* const* out_w, const float* const* out_b, int batch, int cpb_want,
+               int n_codes) {
     ArPersist* h = new ArPersist();
     h->w = *w;
     h->B = batch;
@@ -952,7 +979,16 @@ int arp_create(ArPersist** out, const vqw_ar_weights* w, const int* dil, const f
     e0 += cv.n_p1;
     hipLaunchKernelGGL(pack_head_kernel, dim3(256), dim3(256), 0, 0, w->post2_w, Q, S, R, nQ, hwd, e0, cv.nhead, CPB);
     e0 += cv.n_p2;
-    hipLaunchKernelGGL(pack_head_kernel, dim3(64), dim3(256), 0, 0, w->pre_w, R, w->pre_k, R, 1, hwd, e0, cv.nhead, CPB);
+    if (n_codes > 0) {     // code mode: the preprocess gathers rows of its own copy of W_pre (the head section stays unused)
+        const size_t np = (size_t)w->pre_k * n_codes * R;
+        float* prew = (float*)pmalloc(h, np * sizeof(float));
+        if (!prew) return fail("hipMalloc failed");
+        if (hipMemcpy(prew, w->pre_w, np * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess) return fail("hipMemcpy failed");
+        a.prew = prew;
+        a.n_codes = n_codes;
+    } else {
+        hipLaunchKernelGGL(pack_head_kernel, dim3(64), dim3(256), 0, 0, w->pre_w, R, w->pre_k, R, 1, hwd, e0, cv.nhead, CPB);
+    }
     hipLaunchKernelGGL(pack_head_bias_kernel, dim3(8), dim3(256), 0, 0, w->post1_b, R, nS, cv.nbias, cv.bias_head, CPB, db);
     hipLaunchKernelGGL(pack_head_bias_kernel, dim3(8), dim3(256), 0, 0, w->post2_b, R, nQ, cv.nbias, cv.bias_head + nS * CPB, CPB, db);
     hipLaunchKernelGGL(pack_head_bias_kernel, dim3(8), dim3(256), 0, 0, w->pre_b, R, 1, cv.nbias, cv.bias_head + (nS + nQ) * CPB, CPB, db);
@@ -1037,7 +1073,7 @@ int arp_run(ArPersist* const* hs, int n, const float* const* const* condenc, int
         PHIPC(hipMemcpyAsync(h->dcond, condenc[i], (L + 1) * sizeof(float*), hipMemcpyHostToDevice, st));
         PArgs a = h->args;
         a.Tz = Tz; a.ratio = ratio; a.mode = mode; a.n_steps = n_steps;
-        a.uniforms = uniforms ? uniforms[i] : nullptr; a.audio = audio[i];
+        a.uniforms = uniforms ? uniforms[i] : nullptr; a.audio = audio ? audio[i] : nullptr;
         a.indices = indices ? indices[i] : nullptr; a.probs_last = probs_last ? probs_last[i] : nullptr;
 #ifdef VQW_AR_TRACE
         if (!h->trace) h->trace = (u64*)pmalloc(h, (size_t)h->nwg * 16 * 16 * sizeof(u64));

@@ -82,7 +82,7 @@ class FastGenerator:
         self._hs = []
         for nb in self._parts:
             h = C.c_void_p()
-            L.check(L.lib().vqw_ar_decode_create_ex(C.byref(h), C.byref(w), nb, cpb))
+            self._create(h, w, nb, cpb)
             self._hs.append(h)
         # waves of handles that are co-resident by construction: floor((CUs - margin) / workgroups), at most MAX_GROUP
         # (no margin where the whole batch fits the chip exactly: the one-utterance-per-XCD layout)
@@ -99,6 +99,9 @@ class FastGenerator:
                 j += 1
             self._waves.append(list(range(i, j))); i = j
 
+    def _create(self, h, w, rows, cpb):
+        L.check(L.lib().vqw_ar_decode_create_ex(C.byref(h), C.byref(w), rows, cpb))
+
     def reset(self):
         """sess.run(wavenet.init_ops) (generate.py:105)."""
         for h in self._hs:
@@ -109,13 +112,18 @@ class FastGenerator:
         Returns (audio [B][n] float32, indices [B][n] int32[, probs of the last step [B][Q]])."""
         if mode not in ('greedy', 'sample'):
             raise NotImplementedError('decode mode %s not implemented' % mode)   # utils.py:46
+        B = encoding.shape[0]
+        audio = torch.empty(B, n_steps, device=encoding.device)
+        idx, probs = self._run(encoding, n_steps, mode, uniforms, ratio or 64, audio, return_probs)
+        return (audio, idx, probs) if return_probs else (audio, idx)
+
+    def _run(self, encoding, n_steps, mode, uniforms, ratio, audio, return_probs):
+        """One run of every handle over its rows; audio may be None (code mode).  Returns (indices, probs of the last step)."""
         B, Cc, Tz = encoding.shape
         if B != self.B or Cc != self.model.Cc:
             raise ValueError('encoding must be [%d][%d][Tz]' % (self.B, self.model.Cc))
         L.require_cuda(encoding, uniforms)
-        ratio = ratio or 64
         dev = encoding.device
-        audio = torch.empty(B, n_steps, device=dev)
         idx = torch.empty(B, n_steps, dtype=torch.int32, device=dev)
         probs = torch.empty(B, self.model.Q, device=dev) if return_probs else None
         if mode == 'sample':
@@ -132,7 +140,7 @@ class FastGenerator:
             L.check(L.lib().vqw_ar_decode_run_group_async(
                 hs, len(wave), vp([encoding[rows[i]] for i in wave]), Tz, ratio, n_steps, 0 if mode == 'greedy' else 1,
                 vp([uniforms[rows[i]] for i in wave]) if uniforms is not None else None,
-                vp([audio[rows[i]] for i in wave]), vp([idx[rows[i]] for i in wave]),
+                vp([audio[rows[i]] for i in wave]) if audio is not None else None, vp([idx[rows[i]] for i in wave]),
                 vp([probs[rows[i]] for i in wave]) if probs is not None else None, L.stream())
                 if L.lib().vqw_ar_decode_workgroups(self._hs[wave[0]]) > 0 else
                 L.lib().vqw_ar_decode_run_async(
@@ -141,7 +149,7 @@ class FastGenerator:
                     L.ptr(idx[rows[wave[0]]]), L.ptr(probs[rows[wave[0]]]) if probs is not None else None, L.stream()))
             for i in wave:
                 L.check(L.lib().vqw_ar_decode_wait(self._hs[i]))
-        return (audio, idx, probs) if return_probs else (audio, idx)
+        return idx, probs
 
     def close(self):
         for h in getattr(self, '_hs', []):
@@ -153,3 +161,41 @@ class FastGenerator:
             self.close()
         except Exception:
             pass
+
+
+class PriorGenerator(FastGenerator):
+    """Samples VQ codes from a prior.LatentPrior on the persistent generator's code-input mode (vqw_ar_prior_create): the
+    history holds past codes, the preprocess gathers rows of W_pre[j][code], the sampled index is the next input.  Same
+    layout policy as FastGenerator; uses the prior's LIVE variables at construction (prior.use_ema_weights() first for
+    the EMA shadows).  The launch-per-phase generator (VQW_AR_PERSISTENT=0) has no code input."""
+
+    def __init__(self, prior, batch):
+        import os
+        if os.environ.get('VQW_AR_PERSISTENT', '1').startswith('0'):
+            raise NotImplementedError('prior sampling runs on the persistent generator only: the launch-per-phase path '
+                                      '(VQW_AR_PERSISTENT=0) has no code-input mode')
+        self._t = 0
+        super().__init__(prior, batch)
+
+    def _create(self, h, w, rows, cpb):
+        L.check(L.lib().vqw_ar_prior_create(C.byref(h), C.byref(w), rows, cpb, self.model.Q))
+
+    def reset(self):
+        """Empty history ("no code yet": a zero one-hot, not code 0); the next sample is step 0."""
+        super().reset()
+        self._t = 0
+
+    def sample(self, n_frames, spk, mode='greedy', uniforms=None, return_probs=False):
+        """n_frames codes per row, continuing from the current state.  spk int64 [B] on the GPU.  mode 'greedy' (argmax) or
+        'sample' (searchsorted(cumsum(p), u) with uniforms [B][n_frames], drawn here when None; u above the cdf's last
+        value gives the last code).  Returns codes int32 [B][n_frames][, probabilities of the last step [B][k]]."""
+        if mode not in ('greedy', 'sample'):
+            raise NotImplementedError('decode mode %s not implemented' % mode)
+        if spk.numel() != self.B:
+            raise ValueError('%d speaker ids for a batch of %d' % (spk.numel(), self.B))
+        ratio = 64                                     # code steps per condition frame (prior.CODES_PER_FRAME)
+        Tz = -(-(self._t + n_frames) // ratio)
+        cond = self.model.speaker_condition(spk.contiguous(), Tz)
+        idx, probs = self._run(cond, n_frames, mode, uniforms, ratio, None, return_probs)
+        self._t += n_frames
+        return (idx, probs) if return_probs else idx

@@ -506,6 +506,44 @@ def mfcc(x, mel, out, *, n_keep=13):
     L.check(L.lib().vqw_mfcc(L.ptr(x), L.ptr(mel), L.ptr(out), B, T, frames, mel.shape[1], n_keep, C_out, L.stream()))
 
 
+def prior_input_fwd(codes, w_pre, b_pre, net0, labels=None):
+    """The latent prior's input stage (csrc/prior.hip): net0[b][:][t] = b_pre + sum_j w_pre[j][codes[b][t-pre_k+j]] (the causal
+    conv of one_hot(shift_right(codes)), never materialised); labels := codes.  codes int32 [B][T], w_pre [pre_k][k][R]."""
+    B, T = codes.shape
+    pre_k, k, R = w_pre.shape
+    L.require_cuda(codes, w_pre, b_pre, net0, labels)
+    if codes.dtype != torch.int32:
+        raise ValueError('codes must be int32 [B][T]')
+    _need(b_pre, R, 'b_pre')
+    _need(net0, B * R * T, 'net0')
+    if labels is not None:
+        if labels.dtype != torch.int32 or labels.numel() < B * T:
+            raise ValueError('labels must be int32 with at least B*T elements')
+    L.check(L.lib().vqw_prior_input_fwd(L.ptr(codes), L.ptr(w_pre), L.ptr(b_pre), L.ptr(net0), L.ptr(labels), B, T, k, R, pre_k,
+                                        L.stream()))
+
+
+def prior_code_buckets(codes, k):
+    """Host-side plumbing of prior_input_wgrad: the flat positions b*T + s sorted by code (stable, so the order inside a
+    code is fixed) and the start of every code's run, starts[k] = B*T.  No host sync."""
+    flat = codes.reshape(-1)
+    sorted_codes, order = torch.sort(flat, stable=True)
+    starts = torch.searchsorted(sorted_codes, torch.arange(k + 1, device=codes.device, dtype=sorted_codes.dtype))
+    return order.to(torch.int32), starts.to(torch.int32)
+
+
+def prior_input_wgrad(order, starts, dnet_t, dw_pre, *, B, T):
+    """dw_pre[j][q][:] = sum of dnet_t[b][s + pre_k - j][:] over the positions (b, s) of code q, in the order of `order`
+    (deterministic, no atomics).  dnet_t [B][T][R]; dw_pre [pre_k][k][R] is written, not accumulated."""
+    pre_k, k, R = dw_pre.shape
+    L.require_cuda(order, starts, dnet_t, dw_pre)
+    if order.dtype != torch.int32 or starts.dtype != torch.int32 or order.numel() != B * T or starts.numel() != k + 1:
+        raise ValueError('order must be int32 [B*T] and starts int32 [k+1]')
+    _need(dnet_t, B * T * R, 'dnet_t')
+    L.check(L.lib().vqw_prior_input_wgrad(L.ptr(order), L.ptr(starts), L.ptr(dnet_t), L.ptr(dw_pre), B, T, k, R, pre_k,
+                                          L.stream()))
+
+
 def transpose(src, dst, batch, rows, cols):
     _need(src, batch * rows * cols, 'src')
     _need(dst, batch * rows * cols, 'dst')

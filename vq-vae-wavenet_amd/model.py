@@ -44,8 +44,8 @@ def same_pads(n, k, s):
     return total // 2, total - total // 2
 
 
-def layer_scope(i, num_cycle_layers):
-    return 'decoder/cycle_%d/layer_%d' % (1 + i // num_cycle_layers, 1 + i % num_cycle_layers)
+def layer_scope(i, num_cycle_layers, scope='decoder'):
+    return '%s/cycle_%d/layer_%d' % (scope, 1 + i // num_cycle_layers, 1 + i % num_cycle_layers)
 
 
 def _suffix(i):
@@ -55,27 +55,13 @@ def _suffix(i):
 class VQVAE:
     """model.py:7-159.  encoder '64' + VQ + speaker embedding + WaveNet decoder."""
 
+    scope = 'decoder'      # name scope of the WaveNet's variables (named_parameters)
+
     def __init__(self, model_cfg, wavenet_cfg, num_speakers, device='cuda', seed=0):
-        self.enc = model_cfg.get('encoder', '64')
-        if self.enc not in ('64', 'Magenta', '2019'):
-            raise NotImplementedError('encoder %s not implemented' % self.enc)
         self.m, self.w = model_cfg, wavenet_cfg
         self.dev = torch.device(device)
         self.S_spk = num_speakers
-        self.F = model_cfg.get('encoder_filters', 768)
-        self.D = model_cfg['latent_dim']
-        self.Kc = model_cfg['k']
-        self.Cs = model_cfg['speaker_embedding']
-        self.beta = float(model_cfg['beta'])
-        self.use_vq = bool(model_cfg.get('use_vq', True))     # false: z_q = e_k = z_e, reconstruction loss only (model.py:139-141)
-        # speaker_embedding = 0: the one-hot speaker vector itself is the global condition (model.py:19-27 leaves self.h
-        # as [B, 1, num_speakers]); its width is padded to a multiple of 16 channels for the conv engine (the extra
-        # condition rows are always zero, their kernel rows never receive a gradient)
-        self.spk_table = self.Cs > 0
-        self.Cs_eff = self.Cs if self.spk_table else (num_speakers + 15) // 16 * 16
-        self.Cc_ref = self.D + (self.Cs if self.spk_table else num_speakers)      # the reference's condition width
-        self.Cc = self.D + self.Cs_eff
-        self.magenta = {'Magenta': EncoderMagenta, '2019': Encoder2019}[self.enc](self.D) if self.enc != '64' else None
+        self._setup_front(model_cfg, num_speakers)
         w = wavenet_cfg
         self.dil = list(w['dilation_rates'])
         self.L = len(self.dil)
@@ -159,24 +145,30 @@ class VQVAE:
         self.cond_proj = self.Cc <= 128 and self.Mall % 4 == 0 and os.environ.get('VQW_COND_PROJ', '1') != '0'
         self.host_enqueue_ms = None
 
-    # ------------------------------------------------------------------ parameter layout
+    def _setup_front(self, model_cfg, num_speakers):
+        """What feeds the WaveNet's condition: encoder, VQ codebook, speaker embedding (hook: prior.LatentPrior has only the last)."""
+        self.enc = model_cfg.get('encoder', '64')
+        if self.enc not in ('64', 'Magenta', '2019'):
+            raise NotImplementedError('encoder %s not implemented' % self.enc)
+        self.F = model_cfg.get('encoder_filters', 768)
+        self.D = model_cfg['latent_dim']
+        self.Kc = model_cfg['k']
+        self.Cs = model_cfg['speaker_embedding']
+        self.beta = float(model_cfg['beta'])
+        self.use_vq = bool(model_cfg.get('use_vq', True))     # false: z_q = e_k = z_e, reconstruction loss only (model.py:139-141)
+        # speaker_embedding = 0: the one-hot speaker vector itself is the global condition (model.py:19-27 leaves self.h
+        # as [B, 1, num_speakers]); its width is padded to a multiple of 16 channels for the conv engine (the extra
+        # condition rows are always zero, their kernel rows never receive a gradient)
+        self.spk_table = self.Cs > 0
+        self.Cs_eff = self.Cs if self.spk_table else (num_speakers + 15) // 16 * 16
+        self.Cc_ref = self.D + (self.Cs if self.spk_table else num_speakers)      # the reference's condition width
+        self.Cc = self.D + self.Cs_eff
+        self.magenta = {'Magenta': EncoderMagenta, '2019': Encoder2019}[self.enc](self.D) if self.enc != '64' else None
     def _build_layout(self):
-        F, D, R, S, Q, L, ks, Cc = self.F, self.D, self.R, self.S, self.Q, self.L, self.ks, self.Cc
+        R, S, Q, L, ks, Cc = self.R, self.S, self.Q, self.L, self.ks, self.Cc
         seg = OrderedDict()  # internal (grouped) tensors of the flat buffer
-        if self.spk_table:
-            seg['speaker_embedding'] = (self.S_spk, self.Cs)
-        if self.enc == '64':
-            seg['enc_w0'] = (5, F)                 # conv1d/kernel [5,1,F]
-            seg['enc_w'] = (5, 5, F, F)            # conv1d_1..5/kernel
-            seg['enc_b'] = (6, F)
-            seg['enc_w6'] = (F, D)                 # conv1d_6/kernel [1,F,D]
-            seg['enc_b6'] = (D,)
-            seg['bn_gamma'] = (6 * F + D,)
-            seg['bn_beta'] = (6 * F + D,)
-        else:
-            seg.update(self.magenta.segments())
-        seg['embedding'] = (self.Kc, D)
-        seg['pre_w'] = (self.pre_k, R)
+        self._front_segments(seg)
+        seg['pre_w'] = self._pre_w_shape()
         seg['pre_b'] = (R,)
         seg['skip0_w'] = (R, S)
         seg['skip0_b'] = (S,)
@@ -196,6 +188,27 @@ class VQVAE:
             off += (math.prod(shp) + 3) // 4 * 4  # keep every segment 16-byte aligned
         self.n_flat = off
         self.seg_shapes = seg
+
+    def _front_segments(self, seg):
+        """Flat-buffer segments in front of the WaveNet's: speaker table, encoder, VQ codebook (hook)."""
+        F, D = self.F, self.D
+        if self.spk_table:
+            seg['speaker_embedding'] = (self.S_spk, self.Cs)
+        if self.enc == '64':
+            seg['enc_w0'] = (5, F)                 # conv1d/kernel [5,1,F]
+            seg['enc_w'] = (5, 5, F, F)            # conv1d_1..5/kernel
+            seg['enc_b'] = (6, F)
+            seg['enc_w6'] = (F, D)                 # conv1d_6/kernel [1,F,D]
+            seg['enc_b6'] = (D,)
+            seg['bn_gamma'] = (6 * F + D,)
+            seg['bn_beta'] = (6 * F + D,)
+        else:
+            seg.update(self.magenta.segments())
+        seg['embedding'] = (self.Kc, D)
+
+    def _pre_w_shape(self):
+        """The preprocess kernel: [pre_k][R] over the one input channel (prior: [pre_k][k][R] over one-hot codes)."""
+        return (self.pre_k, self.R)
 
     def _views(self, flat):
         return {n: flat[o:o + math.prod(shp)].view(shp) for n, (o, shp) in self.seg_off.items()}
@@ -220,21 +233,11 @@ class VQVAE:
             lim = math.sqrt(6.0 / (k * cin + k * cout))
             return (torch.rand(shape, generator=g) * 2 - 1) * lim
 
-        F, D, R, S, Q, L, ks, Cc = self.F, self.D, self.R, self.S, self.Q, self.L, self.ks, self.Cc
+        R, S, Q, L, ks, Cc = self.R, self.S, self.Q, self.L, self.ks, self.Cc
         P = self.P
-        if self.spk_table:
-            P['speaker_embedding'].copy_(uus((self.S_spk, self.Cs), self.S_spk, 2.0))   # model.py:23-26
-        else:
-            self.onehot = torch.eye(self.S_spk, self.Cs_eff, device=dev)              # row s = one_hot(s), zero padded
-        if self.enc == '64':
-            P['enc_w0'].copy_(glorot((5, F), 5, 1, F))
-            P['enc_w'].copy_(glorot((5, 5, F, F), 5, F, F))
-            P['enc_w6'].copy_(glorot((F, D), 1, F, D))
-            P['bn_gamma'].fill_(1.0)
-        else:
-            self.magenta.init(P, uus if self.enc == 'Magenta' else glorot)
-        P['embedding'].copy_(uus((self.Kc, D), self.Kc, 1.7))                       # model.py:47-49
-        P['pre_w'].copy_(uus((self.pre_k, R), self.pre_k, 1.0))                     # wavenet_ops.py:69
+        self._init_front(P, uus, glorot)
+        pre_shape = self._pre_w_shape()
+        P['pre_w'].copy_(uus(pre_shape, math.prod(pre_shape[:-1]), 1.0))          # wavenet_ops.py:69
         P['skip0_w'].copy_(uus((R, S), R, 1.0))
         P['gated_w'].copy_(uus((L, ks, R, 2 * R), ks * R, 1.0))
         P['cond_w'].copy_(uus((Cc, self.Mall), self.Cc_ref, 1.0))
@@ -248,9 +251,25 @@ class VQVAE:
         with A.record(self._poison_T):
             self._alloc_scratch()
 
+    def _init_front(self, P, uus, glorot):
+        """Initial values of the _front_segments (hook)."""
+        F, D = self.F, self.D
+        if self.spk_table:
+            P['speaker_embedding'].copy_(uus((self.S_spk, self.Cs), self.S_spk, 2.0))   # model.py:23-26
+        else:
+            self.onehot = torch.eye(self.S_spk, self.Cs_eff, device=self.dev)         # row s = one_hot(s), zero padded
+        if self.enc == '64':
+            P['enc_w0'].copy_(glorot((5, F), 5, 1, F))
+            P['enc_w'].copy_(glorot((5, 5, F, F), 5, F, F))
+            P['enc_w6'].copy_(glorot((F, D), 1, F, D))
+            P['bn_gamma'].fill_(1.0)
+        else:
+            self.magenta.init(P, uus if self.enc == 'Magenta' else glorot)
+        P['embedding'].copy_(uus((self.Kc, D), self.Kc, 1.7))                       # model.py:47-49
+
     def _alloc_scratch(self):
         dev = self.dev
-        F, D, R, S, Q, L, ks, Cc = self.F, self.D, self.R, self.S, self.Q, self.L, self.ks, self.Cc
+        R, S, Q, L, ks, Cc = self.R, self.S, self.Q, self.L, self.ks, self.Cc
         self.T = {
             'gated_w': A.empty(L, ks, 2 * R, R, device=dev),
             'out_w': A.empty(L, S + R, R, device=dev),
@@ -259,17 +278,46 @@ class VQVAE:
             'skip0_w': A.empty(S, R, device=dev),
             'cond_w': A.empty(self.Mall, Cc, device=dev),
         }
+        self.T.update(self._front_scratch())
+
+    def _front_scratch(self):
+        """Transposed-kernel scratch of the encoder's input-gradient GEMMs (hook)."""
+        F, D, dev = self.F, self.D, self.dev
         if self.enc == '64':
-            self.T['enc_w'] = A.empty(5, 5, F, F, device=dev)
-            self.T['enc_w6'] = A.empty(D, F, device=dev)
-        else:
-            self.T.update(self.magenta.scratch(dev))
+            return {'enc_w': A.empty(5, 5, F, F, device=dev), 'enc_w6': A.empty(D, F, device=dev)}
+        return self.magenta.scratch(dev)
 
     # ------------------------------------------------------------------ reference-name views
     def _named(self, V, bn_stats=True):
         """Reference TF variable name -> tensor (copy) with the reference shape."""
-        F, D, R, S, L = self.F, self.D, self.R, self.S, self.L
+        R, S, L = self.R, self.S, self.L
         out = OrderedDict()
+        self._named_front(V, out, bn_stats)
+        sc = self.scope
+        out[sc + '/preprocess/kernel'] = V['pre_w'].reshape(self.pre_k, -1, R)
+        out[sc + '/preprocess/bias'] = V['pre_b']
+        out[sc + '/skip/kernel'] = V['skip0_w'].reshape(1, R, S)
+        out[sc + '/skip/bias'] = V['skip0_b']
+        ncl = self.w['num_cycle_layers']
+        for l in range(L):
+            s = layer_scope(l, ncl, sc)
+            out[s + '/gated/kernel'] = V['gated_w'][l]
+            out[s + '/gated/bias'] = V['gated_b'][l]
+            out[s + '/gated/local_condition/kernel'] = V['cond_w'][:self.Cc_ref, l * 2 * R:(l + 1) * 2 * R].unsqueeze(0)
+            out[s + '/skip/kernel'] = V['out_w'][l][:, :S].unsqueeze(0)
+            out[s + '/skip/bias'] = V['out_b'][l][:S]
+            out[s + '/residual/kernel'] = V['out_w'][l][:, S:].unsqueeze(0)
+            out[s + '/residual/bias'] = V['out_b'][l][S:]
+        out[sc + '/postprocess1/kernel'] = V['post1_w'].reshape(1, S, S)
+        out[sc + '/postprocess1/bias'] = V['post1_b']
+        out[sc + '/postprocess1/local_condition/kernel'] = V['cond_w'][:self.Cc_ref, L * 2 * R:].unsqueeze(0)
+        out[sc + '/postprocess2/kernel'] = V['post2_w'].reshape(1, S, self.Q)
+        out[sc + '/postprocess2/bias'] = V['post2_b']
+        return out
+
+    def _named_front(self, V, out, bn_stats=True):
+        """The _front_segments under the reference's names (hook)."""
+        F, D = self.F, self.D
         if self.spk_table:
             out['speaker_embedding'] = V['speaker_embedding']
         if self.enc == '64':
@@ -292,26 +340,6 @@ class VQVAE:
             self.magenta.named(V, out)
         if self.use_vq:          # (the reference only creates the codebook under use_vq, model.py:137-138)
             out['embedding/embedding'] = V['embedding']
-        out['decoder/preprocess/kernel'] = V['pre_w'].reshape(self.pre_k, 1, R)
-        out['decoder/preprocess/bias'] = V['pre_b']
-        out['decoder/skip/kernel'] = V['skip0_w'].reshape(1, R, S)
-        out['decoder/skip/bias'] = V['skip0_b']
-        ncl = self.w['num_cycle_layers']
-        for l in range(L):
-            s = layer_scope(l, ncl)
-            out[s + '/gated/kernel'] = V['gated_w'][l]
-            out[s + '/gated/bias'] = V['gated_b'][l]
-            out[s + '/gated/local_condition/kernel'] = V['cond_w'][:self.Cc_ref, l * 2 * R:(l + 1) * 2 * R].unsqueeze(0)
-            out[s + '/skip/kernel'] = V['out_w'][l][:, :S].unsqueeze(0)
-            out[s + '/skip/bias'] = V['out_b'][l][:S]
-            out[s + '/residual/kernel'] = V['out_w'][l][:, S:].unsqueeze(0)
-            out[s + '/residual/bias'] = V['out_b'][l][S:]
-        out['decoder/postprocess1/kernel'] = V['post1_w'].reshape(1, S, S)
-        out['decoder/postprocess1/bias'] = V['post1_b']
-        out['decoder/postprocess1/local_condition/kernel'] = V['cond_w'][:self.Cc_ref, L * 2 * R:].unsqueeze(0)
-        out['decoder/postprocess2/kernel'] = V['post2_w'].reshape(1, S, self.Q)
-        out['decoder/postprocess2/bias'] = V['post2_b']
-        return out
 
     def named_parameters(self, ema=False):
         """Copies of all variables under the reference's names (ema=True: the EMA shadows
@@ -356,47 +384,12 @@ class VQVAE:
         return ws
 
     def _build_workspace(self, B, T, train):
-        if self.enc == '64':
-            if T % 64 != 0:
-                raise ValueError('length must be a multiple of 64 for Encoder_64 (got %d)' % T)
-            Tz = T // 64
-        else:
-            Tz = self.magenta.latent_len(T)
-        dev, F, D, R, S, Q, L = self.dev, self.F, self.D, self.R, self.S, self.Q, self.L
-        e = lambda *s: A.empty(*s, device=dev)  # noqa: E731
-        ws = {'B': B, 'T': T, 'Tz': Tz, 'ratio': T // Tz}
-        ws['Tl'] = [T // (2 ** (i + 1)) for i in range(6)]
-        ws['inputs'] = e(B, T)
-        ws['labels'] = A.empty(B, T, dtype=torch.int32, device=dev)
-        if self.enc == '64':
-            ws['X'] = [e(B, F, t) for t in ws['Tl']]      # BN outputs of encoder layers 0..5
-            if self.x3_guard and not self.bf16 and F % 256 == 0:      # fp16x3 engine for layers 1..3 (_enc_x3_layers)
-                ws['eplanes'] = A.empty(2 * B * F * ws['Tl'][0], dtype=torch.float16, device=dev)   # planes of one layer's operand
-                ws['ewp'] = A.empty(5, 2 * 5 * F * F, dtype=torch.float16, device=dev)
-                ws['enc_amax'] = torch.zeros(12, dtype=torch.int32, device=dev)
-                ws['enc_scale'] = torch.ones(12, device=dev)
-                if train:
-                    ws['ewtp'] = A.empty(5, 2 * 5 * F * F, dtype=torch.float16, device=dev)
-                    if self.wg_planes:     # the planes of each layer's input (space-to-depth) and output gradient are KEPT: the strided weight
-                        # gradients read them (p_planes / q_planes) instead of fetching fp32 one float per request (240 MB at B = 8)
-                        ws['esp'] = {i: A.empty(2 * B * F * ws['Tl'][i - 1], dtype=torch.float16, device=dev) for i in range(1, 6)}
-                        ws['edp'] = {i: A.empty(2 * B * F * ws['Tl'][i], dtype=torch.float16, device=dev) for i in range(1, 6)}
-            if train:
-                ws['r'] = [e(B, F, t) for t in ws['Tl']]      # relu outputs
-                ws['y6'] = e(B, D, Tz)
-                ws['dX'] = [e(B, F, t) for t in ws['Tl']]
-        else:
-            self.magenta.workspace(ws, B, T, dev, train)
-        ws['z_e'] = e(B, D, Tz)
-        ws['idx'] = A.empty(B, Tz, dtype=torch.int64, device=dev)
-        ws['e_k'] = e(B, D, Tz)
-        ws['mind'] = e(B, Tz)
-        ws['cond'] = e(B, self.Cc, Tz)
-        ws['scale'] = e(6 * F + D)
-        ws['shift'] = e(6 * F + D)
+        ws = self._front_workspace(B, T, train)
         if not train:
             return ws
-        ws['condenc'] = e(B, self.Mall, Tz)
+        dev, R, S, Q, L, T = self.dev, self.R, self.S, self.Q, self.L, ws['T']
+        e = lambda *s: A.empty(*s, device=dev)  # noqa: E731
+        ws['condenc'] = e(B, self.Mall, ws['Tz'])
         ws['net'] = [e(B, R, T) for _ in range(L + 1)]
         ws['skip'] = e(B, S, T)
         ws['gated'] = [e(B, R, T) for _ in range(L)]
@@ -437,12 +430,59 @@ class VQVAE:
         ws['dpre'] = e(B, 2 * R, T)
         ws['dnet_ring'] = [ws['dnet'], e(B, R, T), e(B, R, T)]      # ping-pong sets for the two-stream backward
         ws['dpre_ring'] = [ws['dpre'], e(B, 2 * R, T)]
-        ws['dcondenc'] = e(B, self.Mall, Tz)
-        ws['dcond'] = e(B, self.Cc, Tz)
-        ws['dz'] = e(B, D, Tz)
+        ws['dcondenc'] = e(B, self.Mall, ws['Tz'])
+        ws['dcond'] = e(B, self.Cc, ws['Tz'])
         ws['bskip'] = e(S)
-        ws['dscale'] = e(6 * F + D)
+        self._front_workspace_train(ws)
         return ws
+
+    def _front_workspace(self, B, T, train):
+        """The (B, T) workspace up to the condition: inputs / labels, encoder + VQ buffers, ws['cond'] (hook)."""
+        if self.enc == '64':
+            if T % 64 != 0:
+                raise ValueError('length must be a multiple of 64 for Encoder_64 (got %d)' % T)
+            Tz = T // 64
+        else:
+            Tz = self.magenta.latent_len(T)
+        dev, F, D, R, S, Q, L = self.dev, self.F, self.D, self.R, self.S, self.Q, self.L
+        e = lambda *s: A.empty(*s, device=dev)  # noqa: E731
+        ws = {'B': B, 'T': T, 'Tz': Tz, 'ratio': T // Tz}
+        ws['Tl'] = [T // (2 ** (i + 1)) for i in range(6)]
+        ws['inputs'] = e(B, T)
+        ws['labels'] = A.empty(B, T, dtype=torch.int32, device=dev)
+        if self.enc == '64':
+            ws['X'] = [e(B, F, t) for t in ws['Tl']]      # BN outputs of encoder layers 0..5
+            if self.x3_guard and not self.bf16 and F % 256 == 0:      # fp16x3 engine for layers 1..3 (_enc_x3_layers)
+                ws['eplanes'] = A.empty(2 * B * F * ws['Tl'][0], dtype=torch.float16, device=dev)   # planes of one layer's operand
+                ws['ewp'] = A.empty(5, 2 * 5 * F * F, dtype=torch.float16, device=dev)
+                ws['enc_amax'] = torch.zeros(12, dtype=torch.int32, device=dev)
+                ws['enc_scale'] = torch.ones(12, device=dev)
+                if train:
+                    ws['ewtp'] = A.empty(5, 2 * 5 * F * F, dtype=torch.float16, device=dev)
+                    if self.wg_planes:     # the planes of each layer's input (space-to-depth) and output gradient are KEPT: the strided weight
+                        # gradients read them (p_planes / q_planes) instead of fetching fp32 one float per request (240 MB at B = 8)
+                        ws['esp'] = {i: A.empty(2 * B * F * ws['Tl'][i - 1], dtype=torch.float16, device=dev) for i in range(1, 6)}
+                        ws['edp'] = {i: A.empty(2 * B * F * ws['Tl'][i], dtype=torch.float16, device=dev) for i in range(1, 6)}
+            if train:
+                ws['r'] = [e(B, F, t) for t in ws['Tl']]      # relu outputs
+                ws['y6'] = e(B, D, Tz)
+                ws['dX'] = [e(B, F, t) for t in ws['Tl']]
+        else:
+            self.magenta.workspace(ws, B, T, dev, train)
+        ws['z_e'] = e(B, D, Tz)
+        ws['idx'] = A.empty(B, Tz, dtype=torch.int64, device=dev)
+        ws['e_k'] = e(B, D, Tz)
+        ws['mind'] = e(B, Tz)
+        ws['cond'] = e(B, self.Cc, Tz)
+        ws['scale'] = e(6 * F + D)
+        ws['shift'] = e(6 * F + D)
+        return ws
+
+    def _front_workspace_train(self, ws):
+        """Backward buffers of the encoder + VQ (hook)."""
+        e = lambda *s: A.empty(*s, device=self.dev)  # noqa: E731
+        ws['dz'] = e(ws['B'], self.D, ws['Tz'])
+        ws['dscale'] = e(6 * self.F + self.D)
 
     # ------------------------------------------------------------------ forward pieces
     def _bn_affine(self, ws):
@@ -569,10 +609,8 @@ class VQVAE:
         (wavenet.py:33-44), this step's guard scales and weight planes, the skip start (wavenet.py:53-54).  Returns the
         plan of the step (which engine carries what, the guard slots) for _decode_layers."""
         P, R, S, Q, L, B, T, Tz = self.P, self.R, self.S, self.Q, self.L, ws['B'], ws['T'], ws['Tz']
-        K.wavenet_inputs(x, ws['inputs'], ws['labels'])                                   # wavenet.py:33-37
+        self._decode_input(x, ws)
         net = ws['net']
-        K.conv_cin1_fwd(ws['inputs'], P['pre_w'], P['pre_b'], net[0], k=self.pre_k, stride=1,
-                        offset=-(self.pre_k - 1))                                         # wavenet.py:42-44
         # fp16x3 needs whole 256-step tiles inside a batch row, 128-channel blocks and one condition frame per 32 steps;
         # |w| < 255 and |net| < 65504 (fp16 range of the leading planes) are assumed, not checked
         f16x3 = self.gate_f16x3 and T % 256 == 0 and R % 128 == 0 and (T // Tz) % 32 == 0
@@ -645,6 +683,12 @@ class VQVAE:
                 K.f16x3_pack_weights(P['out_w'], ws['wop_all'], R, S + R, S + R, WS, count=L, mode=md)
         return dict(f16x3=f16x3, f16x3_skip=f16x3_skip, f16x3_out=f16x3_out, ngrp=ngrp, Lg=Lg, md=md, gd=gd, sc=sc, am=am, flag=flag, WS=WS,
                     head_x3=head_x3, xpl=xpl, drop_th=drop_th, drop_g=drop_g, save=save)
+
+    def _decode_input(self, x, ws):
+        """The input stage: labels and net[0] = the preprocess conv of the shifted input (hook)."""
+        K.wavenet_inputs(x, ws['inputs'], ws['labels'])                                   # wavenet.py:33-37
+        K.conv_cin1_fwd(ws['inputs'], self.P['pre_w'], self.P['pre_b'], ws['net'][0], k=self.pre_k, stride=1,
+                        offset=-(self.pre_k - 1))                                         # wavenet.py:42-44
 
     def _decode_layers(self, ws, plan):
         """The condition projections, the residual stack and the convs behind it (wavenet.py:58-100; wavenet_ops.py:93-138)."""
@@ -739,8 +783,12 @@ class VQVAE:
         N = B * T
         K.softmax_xent(ws['logits'], ws['labels'], loss_sum=self.loss_buf[0:1],
                        dlogits=ws['logits'] if compute_grad_seed else None, grad_scale=1.0 / N)  # model.py:91-94
-        K.rowsum(ws['mind'].view(1, 1, -1), total=self.loss_buf[1:2])
+        self._front_loss(ws)
         return ws
+
+    def _front_loss(self, ws):
+        """loss_buf[1] = the sum of the VQ distances (hook)."""
+        K.rowsum(ws['mind'].view(1, 1, -1), total=self.loss_buf[1:2])
 
     def forward_checked(self, x, spk, compute_grad_seed=False):
         """forward() for callers that do not go on to train_step (evaluation, summaries of a held-out batch).  On the guarded
@@ -761,7 +809,7 @@ class VQVAE:
         return ws
 
     def losses(self, ws):
-        """(loss, reconstruction, vq, commitment) as python floats (synchronises)."""
+        """(loss, reconstruction, vq, commitment) as python floats (synchronises; hook)."""
         self.finish_steps()
         v = self.loss_buf.tolist()
         recon = v[0] / (ws['B'] * ws['T'])
@@ -819,6 +867,11 @@ class VQVAE:
             self._tt_done.add(name)
         return self.T[name]
 
+    def _backward_prepare(self):
+        """Transposed kernels of the encoder's backward pass (hook)."""
+        if self.enc != '64':
+            self.magenta.transpose(self.P, self.T)
+
     def backward(self, x, spk, ws):
         """Gradients of loss = CE + vq + commitment (model.py:90-106) w.r.t. every trainable
         variable, accumulated into self.grad (zeroed here)."""
@@ -827,8 +880,7 @@ class VQVAE:
         B, T, Tz, ratio = ws['B'], ws['T'], ws['Tz'], ws['ratio']
         self.grad.zero_()
         self._tt_done = set()
-        if self.enc != '64':
-            self.magenta.transpose(P, Tt)
+        self._backward_prepare()
         dlog, h1, skip = ws['logits'], ws['h1'], ws['skip']
         cbs = self.Mall * Tz
         dce = ws['dcondenc']
@@ -1093,8 +1145,7 @@ class VQVAE:
             K.rowsum(dskip, total=ws['bskip'])
         G['out_b'][:, :S] += ws['bskip']
         G['skip0_b'] += ws['bskip']
-        K.conv_cin1_wgrad(ws['inputs'], dnet, G['pre_w'], k=self.pre_k, stride=1, offset=-(self.pre_k - 1))
-        K.rowsum(dnet, total=G['pre_b'])
+        self._backward_input(x, ws, dnet)
         # ---- local condition (wavenet_ops.py:93-101) -> d cond
         if self.cond_proj and Tz % 4 == 0 and P['cond_w'].data_ptr() % 16 == 0:
             if 'cp_scratch' not in ws:
@@ -1105,6 +1156,19 @@ class VQVAE:
         else:
             K.wgrad_gemm(p=ws['cond'], q0=dce, dw=G['cond_w'], B=B, T_q=Tz, T_p=Tz, Cp=self.Cc, Q0=self.Mall, taps=[0])
             K.conv_gemm(x0=dce, w=self._tt('cond_w'), out0=ws['dcond'], B=B, T_in=Tz, T_out=Tz, M=self.Cc, C0=self.Mall, taps=[0])
+        self._backward_front(x, spk, ws)
+
+    def _backward_input(self, x, ws, dnet):
+        """Gradients of the preprocess conv from dnet = d loss / d net[0] (hook)."""
+        G = self.G
+        K.conv_cin1_wgrad(ws['inputs'], dnet, G['pre_w'], k=self.pre_k, stride=1, offset=-(self.pre_k - 1))
+        K.rowsum(dnet, total=G['pre_b'])
+
+    def _backward_front(self, x, spk, ws):
+        """From d cond on: speaker embedding, VQ and encoder backward (hook)."""
+        P, G, Tt = self.P, self.G, self.T
+        F, D = self.F, self.D
+        B, T, Tz = ws['B'], ws['T'], ws['Tz']
         if self.grad_sync is not None:      # decoder gradients are final: exchange them under the encoder backward
             self.grad_sync.bucket_ready(self.seg_off['pre_w'][0], self.n_flat)
         # ---- speaker embedding + VQ (model.py:22-27, 57-74, 99-106)
@@ -1375,6 +1439,32 @@ class VQVAE:
         cond = ws['cond'].repeat(B, 1, 1)
         K.speaker_tile_fwd(self.P['speaker_embedding'] if self.spk_table else self.onehot, spk, cond,
                            cond_bstride=self.Cc * ws['Tz'], row0=self.D, Cs=self.Cs_eff, Tz=ws['Tz'])
+        return cond
+
+    def encode_codes(self, x, spk):
+        """The VQ indices [B][Tz] (int32) that encode() computes for x [B][T]: the discrete codes a latent prior
+        (prior.LatentPrior) models."""
+        if not self.use_vq:
+            raise ValueError('encode_codes: the model has no codebook (use_vq is false)')
+        self.finish_steps()
+        B, T = x.shape
+        ws = self._workspace(B, T, train=False)
+        self._encode(x, spk.contiguous(), ws, save=False)
+        return ws['idx'].to(torch.int32)
+
+    def condition_from_codes(self, codes, spk):
+        """The [B][Cc][Tz] condition [embedding[codes]; speaker] that encode() produces for those VQ codes (model.py:57-74 +
+        decoder.py:30-31): decodes codes sampled from a latent prior."""
+        if not self.use_vq:
+            raise ValueError('condition_from_codes: the model has no codebook (use_vq is false)')
+        self.finish_steps()
+        B, Tz = codes.shape
+        if spk.numel() != B:
+            raise ValueError('condition_from_codes: %d code rows for %d speaker ids' % (B, spk.numel()))
+        cond = torch.empty(B, self.Cc, Tz, device=self.dev)
+        cond[:, :self.D] = self.P['embedding'][codes.long()].permute(0, 2, 1)      # e_k = the chosen rows, exactly
+        K.speaker_tile_fwd(self.P['speaker_embedding'] if self.spk_table else self.onehot, spk, cond,
+                           cond_bstride=self.Cc * Tz, row0=self.D, Cs=self.Cs_eff, Tz=Tz)
         return cond
 
     def free_workspaces(self):
