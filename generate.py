@@ -13,6 +13,9 @@ speakers are sharded over the GPUs (rows of the batch never interact).
 With `-prior <prior.pt> -frames N` no input utterance is needed: N VQ codes per speaker are sampled from a latent prior
 (prior.py, trained by train_prior.py), decoded through the VQ-VAE's codebook (condition_from_codes) and its fast WaveNet
 generator, and written as `<dir>/<step>_<speaker>_prior.wav` (N x 64 samples) plus `prior_codes_<step>_<speaker>.npy`.
+
+`-temperature / -top_k / -top_p` temper and truncate the audio sampling, `-prior_temperature / -prior_top_k / -prior_top_p`
+the code sampling of `-prior` (mode sample only; the same values for every speaker; the defaults are plain sampling).
 """
 import importlib
 import json
@@ -39,6 +42,13 @@ def main():
     parser.add_argument('-frames', default=256, type=int, dest='frames', help='codes to sample per speaker with -prior (x 64 samples)')
     parser.add_argument('-prior_params', default='prior_parameters.json', dest='prior_params', metavar='str',
                         help='the prior\'s parameters file (with -prior)')
+    parser.add_argument('-temperature', default=1.0, type=float, help='audio sampling: softmax temperature (> 0; 1 = off)')
+    parser.add_argument('-top_k', default=0, type=int, help='audio sampling: keep the k most likely classes (0 = off)')
+    parser.add_argument('-top_p', default=1.0, type=float,
+                        help='audio sampling: keep the smallest most-likely set of mass >= p (nucleus, (0, 1]; 1 = off)')
+    parser.add_argument('-prior_temperature', default=1.0, type=float, help='code sampling with -prior: softmax temperature')
+    parser.add_argument('-prior_top_k', default=0, type=int, help='code sampling with -prior: top-k (0 = off)')
+    parser.add_argument('-prior_top_p', default=1.0, type=float, help='code sampling with -prior: top-p (1 = off)')
     args = parser.parse_args()
     if args.prior_path is None and args.audio_path is None:
         parser.error('-audio is required (or -prior to sample codes from a latent prior)')
@@ -46,6 +56,12 @@ def main():
         raise NotImplementedError('decode mode %s not implemented' % args.mode)
 
     pkg = importlib.import_module('vq-vae-wavenet_amd')
+    try:        # every speaker gets the same settings; checked before anything is loaded or built
+        for kind in ('', 'prior_'):
+            pkg.generator.sampling_settings(1, args.mode, getattr(args, kind + 'temperature'), getattr(args, kind + 'top_k'),
+                                            getattr(args, kind + 'top_p'))
+    except ValueError as e:
+        parser.error(str(e))
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', '0')) % max(torch.cuda.device_count(), 1)   # no collective: ranks may share a GPU
@@ -94,7 +110,8 @@ def main():
             rows = slice(b0, min(b0 + 12, B))
             gen = pkg.generator.FastGenerator(model, batch=rows.stop - rows.start)
             audio, _ = gen.generate(enc[rows].contiguous(), length, mode=args.mode, ratio=length // enc.shape[2],
-                                    uniforms=None if uniforms is None else uniforms[rows].contiguous())
+                                    uniforms=None if uniforms is None else uniforms[rows].contiguous(),
+                                    temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
             out[rows] = audio.cpu().numpy()
             gen.close()
         for j, i in enumerate(mine):
@@ -155,12 +172,14 @@ def generate_from_prior(args, pkg, gs, rank, world, dev):
         sl = slice(b0, b0 + len(rows))
         spk = torch.tensor([ids[i] for i in rows], dtype=torch.int64, device=dev)
         pgen = pkg.generator.PriorGenerator(prior, batch=len(rows))
-        codes = pgen.sample(n, spk, mode=args.mode, uniforms=None if u_codes is None else u_codes[sl].contiguous())
+        codes = pgen.sample(n, spk, mode=args.mode, uniforms=None if u_codes is None else u_codes[sl].contiguous(),
+                            temperature=args.prior_temperature, top_k=args.prior_top_k, top_p=args.prior_top_p)
         pgen.close()
         cond = model.condition_from_codes(codes, spk)
         gen = pkg.generator.FastGenerator(model, batch=len(rows))
         audio, _ = gen.generate(cond, length, mode=args.mode, ratio=64,
-                                uniforms=None if u_audio is None else u_audio[sl].contiguous())
+                                uniforms=None if u_audio is None else u_audio[sl].contiguous(),
+                                temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
         gen.close()
         audio, codes = audio.cpu().numpy(), codes.cpu().numpy()
         for j, i in enumerate(rows):

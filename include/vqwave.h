@@ -341,6 +341,30 @@ int vqw_ar_decode_run_group_async(vqw_ar_decoder* const* hs, int n, const float*
                                   int ratio, int n_steps, int mode, const float* const* uniforms,
                                   float* const* audio, int32_t* const* indices, float* const* probs_last,
                                   vqw_stream_t s);
+/* Per-row sampling settings of mode 1 (sample).  For one step of a row with logits z[0..Q):
+ *   1. p = softmax(z / temperature), the max subtracted first;
+ *   2. top_k: order the classes by (p descending, index ascending) and keep the first top_k;
+ *   3. top_p: in the same order, keep the shortest prefix of the kept set whose mass is >= top_p times the kept mass
+ *      (at least one class);
+ *   4. q = p on the kept set, renormalised, zero elsewhere; the class is the first kept index whose ascending cdf of q
+ *      reaches u, or the largest kept index when u lies above the last cdf value.  probs_last receives q.
+ * temperature finite and > 0 (1 = off); top_k >= 0 (0, or >= Q, = off); top_p in (0, 1] (1 = off).  A row with all three
+ * off takes exactly the arithmetic of vqw_ar_decode_run (its indices, audio and probs_last are bitwise the same), whatever
+ * the other rows of the launch use.  Non-default settings need mode 1 and Q <= 1024; invalid settings are an error. */
+typedef struct vqw_ar_sampling {
+    float temperature;
+    int32_t top_k;
+    float top_p;
+} vqw_ar_sampling;
+/* vqw_ar_decode_run_async / _run_group_async with per-row sampling settings: `sampling` is a HOST array of the handle's
+ * batch entries (group: one such array per handle), NULL (as a whole or per handle) = every row at its defaults. */
+int vqw_ar_decode_run_sampled_async(vqw_ar_decoder* h, const float* encoding, int Tz, int ratio,
+                                    int n_steps, int mode, const float* uniforms, const vqw_ar_sampling* sampling,
+                                    float* audio, int32_t* indices, float* probs_last, vqw_stream_t s);
+int vqw_ar_decode_run_group_sampled_async(vqw_ar_decoder* const* hs, int n, const float* const* encoding, int Tz,
+                                          int ratio, int n_steps, int mode, const float* const* uniforms,
+                                          const vqw_ar_sampling* const* sampling, float* const* audio,
+                                          int32_t* const* indices, float* const* probs_last, vqw_stream_t s);
 /* workgroups (= CUs held for the whole run) of the handle's persistent kernel; 0: launch-per-phase path */
 int vqw_ar_decode_workgroups(const vqw_ar_decoder* h);
 int vqw_ar_decode_destroy(vqw_ar_decoder* h);

@@ -53,6 +53,11 @@ class ArWeights(C.Structure):
     ]
 
 
+class ArSampling(C.Structure):
+    """vqw_ar_sampling: per-row temperature / top-k / top-p of mode 1 (sample)."""
+    _fields_ = [('temperature', C.c_float), ('top_k', C.c_int32), ('top_p', C.c_float)]
+
+
 class F16x3GateDesc(C.Structure):
     _fields_ = [
         ('xp', _fp), ('wp', _fp), ('bias', _fp), ('cond', _fp), ('out0', _fp), ('save0', _fp), ('save1', _fp),
@@ -151,6 +156,10 @@ SIGNATURES = {
     'vqw_ar_decode_wait': (_i, [_fp]),
     'vqw_ar_decode_run_group_async': (_i, [C.POINTER(_fp), _i, C.POINTER(_fp), _i, _i, _i, _i, C.POINTER(_fp), C.POINTER(_fp),
                                            C.POINTER(_fp), C.POINTER(_fp), _fp]),
+    'vqw_ar_decode_run_sampled_async': (_i, [_fp, _fp, _i, _i, _i, _i, _fp, C.POINTER(ArSampling), _fp, _fp, _fp, _fp]),
+    'vqw_ar_decode_run_group_sampled_async': (_i, [C.POINTER(_fp), _i, C.POINTER(_fp), _i, _i, _i, _i, C.POINTER(_fp),
+                                                   C.POINTER(C.POINTER(ArSampling)), C.POINTER(_fp), C.POINTER(_fp),
+                                                   C.POINTER(_fp), _fp]),
     'vqw_ar_decode_workgroups': (_i, [_fp]),
     'vqw_ar_decode_destroy': (_i, [_fp]),
     'vqw_ar_prior_create': (_i, [C.POINTER(_fp), C.POINTER(ArWeights), _i, _i, _i]),

@@ -29,6 +29,7 @@ struct ArState {  // device resident
     float* audio;
     int* indices;
     float* probs_last;
+    ArSampleRow samp[MAXB];   // per-row temperature / top-k / top-p (ar_sampling.h); .on = 0: the default path
 };
 
 struct GemvSeg {
@@ -243,6 +244,22 @@ __global__ __launch_bounds__(256) void ar_sample_kernel(ArState* st, const float
     const int i_out = step - st->run_base;
     for (int b = 0; b < B; ++b) {
         const float* lg = logits + (size_t)b * Q;
+        if (st->samp[b].on) {              // block-uniform; wave 0 samples the row (ar_sampling.h), the others wait
+            if (wv == 0) {
+                for (int q = lane; q < Q; q += 64) sp[q] = lg[q];
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // lanes read each other's LDS writes (same wave)
+                const int idx = ar_sample_truncated(sp, Q, st->samp[b], st->uniforms[(size_t)b * st->n_steps + i_out],
+                                                    st->probs_last ? st->probs_last + (size_t)b * Q : probs + (size_t)b * Q);
+                if (lane == 0) {
+                    const float dec = mu_dec((float)idx);
+                    if (st->audio) st->audio[(size_t)b * st->n_steps + i_out] = dec;
+                    if (st->indices) st->indices[(size_t)b * st->n_steps + i_out] = idx;
+                    prev[b] = dec;
+                }
+            }
+            __syncthreads();
+            continue;
+        }
         float m = -INFINITY;
         int mi = 0x7fffffff;
         for (int q = tid; q < Q; q += 256) {
@@ -559,12 +576,18 @@ int project_condition(vqw_ar_decoder* h, const float* encoding, int Tz, hipStrea
 
 }  // namespace
 
-extern "C" int vqw_ar_decode_run_async(vqw_ar_decoder* h, const float* encoding, int Tz, int ratio, int n_steps,
-                                       int mode, const float* uniforms, float* audio, int32_t* indices,
-                                       float* probs_last, vqw_stream_t s) {
+static int run_group(vqw_ar_decoder* const* hs, int n, const float* const* encoding, int Tz, int ratio, int n_steps, int mode,
+                     const float* const* uniforms, const vqw_ar_sampling* const* sampling, float* const* audio,
+                     int32_t* const* indices, float* const* probs_last, vqw_stream_t s);
+
+// one handle; sampling: NULL (every row at its defaults) or h->B host entries
+static int run_single(vqw_ar_decoder* h, const float* encoding, int Tz, int ratio, int n_steps, int mode,
+                      const float* uniforms, const vqw_ar_sampling* sampling, float* audio, int32_t* indices,
+                      float* probs_last, vqw_stream_t s) {
     if (h && h->persist)
-        return vqw_ar_decode_run_group_async(&h, 1, &encoding, Tz, ratio, n_steps, mode, uniforms ? &uniforms : nullptr, &audio,
-                                             indices ? &indices : nullptr, probs_last ? &probs_last : nullptr, s);
+        return run_group(&h, 1, &encoding, Tz, ratio, n_steps, mode, uniforms ? &uniforms : nullptr,
+                         sampling ? &sampling : nullptr, &audio, indices ? &indices : nullptr,
+                         probs_last ? &probs_last : nullptr, s);
     VQW_CHECK(h && encoding, "vqw_ar_decode_run: null pointer");
     if (h->pending) {
         const int rcw = vqw_ar_decode_wait(h);
@@ -572,6 +595,12 @@ extern "C" int vqw_ar_decode_run_async(vqw_ar_decoder* h, const float* encoding,
     }
     VQW_CHECK(Tz > 0 && ratio > 0 && n_steps > 0, "vqw_ar_decode_run: bad Tz/ratio/n_steps");
     VQW_CHECK(mode == 0 || (mode == 1 && uniforms), "vqw_ar_decode_run: mode must be 0 (greedy) or 1 (sample, needs uniforms)");
+    ArSampleRow rows[MAXB];
+    int any = 0;
+    {
+        const int rc = ar_sampling_rows(sampling, h->B, h->w.Q, mode, rows, &any);
+        if (rc) return rc;
+    }
     hipStream_t user = (hipStream_t)s;
     hipStream_t st = h->stream;
     h->run_stream = st;
@@ -586,6 +615,7 @@ extern "C" int vqw_ar_decode_run_async(vqw_ar_decoder* h, const float* encoding,
     memset(&hs, 0, sizeof(hs));
     hs.Tz = Tz; hs.ratio = ratio; hs.mode = mode; hs.n_steps = n_steps;
     hs.uniforms = uniforms; hs.audio = audio; hs.indices = indices; hs.probs_last = probs_last;
+    for (int b = 0; b < MAXB; ++b) hs.samp[b] = (b < h->B) ? rows[b] : ArSampleRow{1.0f, 0, 1.0f, 0};
     // copy everything except `step`; run_base := step is done by a tiny device-side copy
     HIPC(hipMemcpyAsync(reinterpret_cast<char*>(h->st) + offsetof(ArState, Tz), reinterpret_cast<char*>(&hs) + offsetof(ArState, Tz),
                         sizeof(ArState) - offsetof(ArState, Tz), hipMemcpyHostToDevice, st));
@@ -614,10 +644,35 @@ extern "C" int vqw_ar_decode_run_async(vqw_ar_decoder* h, const float* encoding,
     return 0;
 }
 
+extern "C" int vqw_ar_decode_run_async(vqw_ar_decoder* h, const float* encoding, int Tz, int ratio, int n_steps,
+                                       int mode, const float* uniforms, float* audio, int32_t* indices,
+                                       float* probs_last, vqw_stream_t s) {
+    return run_single(h, encoding, Tz, ratio, n_steps, mode, uniforms, nullptr, audio, indices, probs_last, s);
+}
+
+extern "C" int vqw_ar_decode_run_sampled_async(vqw_ar_decoder* h, const float* encoding, int Tz, int ratio, int n_steps,
+                                               int mode, const float* uniforms, const vqw_ar_sampling* sampling, float* audio,
+                                               int32_t* indices, float* probs_last, vqw_stream_t s) {
+    return run_single(h, encoding, Tz, ratio, n_steps, mode, uniforms, sampling, audio, indices, probs_last, s);
+}
+
 extern "C" int vqw_ar_decode_run_group_async(vqw_ar_decoder* const* hs, int n, const float* const* encoding, int Tz,
                                              int ratio, int n_steps, int mode, const float* const* uniforms,
                                              float* const* audio, int32_t* const* indices,
                                              float* const* probs_last, vqw_stream_t s) {
+    return run_group(hs, n, encoding, Tz, ratio, n_steps, mode, uniforms, nullptr, audio, indices, probs_last, s);
+}
+
+extern "C" int vqw_ar_decode_run_group_sampled_async(vqw_ar_decoder* const* hs, int n, const float* const* encoding, int Tz,
+                                                     int ratio, int n_steps, int mode, const float* const* uniforms,
+                                                     const vqw_ar_sampling* const* sampling, float* const* audio,
+                                                     int32_t* const* indices, float* const* probs_last, vqw_stream_t s) {
+    return run_group(hs, n, encoding, Tz, ratio, n_steps, mode, uniforms, sampling, audio, indices, probs_last, s);
+}
+
+static int run_group(vqw_ar_decoder* const* hs, int n, const float* const* encoding, int Tz, int ratio, int n_steps, int mode,
+                     const float* const* uniforms, const vqw_ar_sampling* const* sampling, float* const* audio,
+                     int32_t* const* indices, float* const* probs_last, vqw_stream_t s) {
     VQW_CHECK(hs && encoding && (audio || (hs[0] && hs[0]->n_codes > 0)) && n >= 1 && n <= 8,
               "vqw_ar_decode_run_group: null pointer or n=%d outside 1..8", n);
     VQW_CHECK(Tz > 0 && ratio > 0 && n_steps > 0, "vqw_ar_decode_run: bad Tz/ratio/n_steps");
@@ -629,6 +684,16 @@ extern "C" int vqw_ar_decode_run_group_async(vqw_ar_decoder* const* hs, int n, c
         VQW_CHECK(hs[i]->persist && arp_same_launch(hs[0]->persist, hs[i]->persist),
                   "vqw_ar_decode_run_group: every handle must run the same persistent kernel (start the others one by one)");
         for (int j = 0; j < i; ++j) VQW_CHECK(hs[j] != hs[i], "vqw_ar_decode_run_group: handle %d given twice", i);
+    }
+    ArSampleRow rows[8][MAXB];
+    const ArSampleRow* rowp[8] = {nullptr};
+    for (int i = 0; i < n; ++i) {
+        int any = 0;
+        const int rc = ar_sampling_rows(sampling ? sampling[i] : nullptr, hs[i]->B, hs[i]->w.Q, mode, rows[i], &any);
+        if (rc) return rc;
+        if (any) rowp[i] = rows[i];
+    }
+    for (int i = 0; i < n; ++i) {
         if (hs[i]->pending) {
             const int rcw = vqw_ar_decode_wait(hs[i]);
             if (rcw) return rcw;
@@ -647,7 +712,7 @@ extern "C" int vqw_ar_decode_run_group_async(vqw_ar_decoder* const* hs, int n, c
         ps[i] = hs[i]->persist;
         conds[i] = hs[i]->condenc.data();
     }
-    const int rc = arp_run(ps, n, conds, Tz, ratio, n_steps, mode, uniforms, audio, indices, probs_last, st);
+    const int rc = arp_run(ps, n, conds, Tz, ratio, n_steps, mode, uniforms, audio, indices, probs_last, rowp, st);
     if (rc) return rc;
     for (int i = 0; i < n; ++i) {
         hs[i]->pending = true;

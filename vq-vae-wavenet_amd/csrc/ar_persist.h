@@ -1,5 +1,6 @@
 // Internal interface of the persistent fast-generation kernel (csrc/ar_persist.hip).
 #pragma once
+#include "ar_sampling.h"
 #include "vqw_common.h"
 
 struct ArPersist;
@@ -13,7 +14,7 @@ int arp_reset(ArPersist* h, hipStream_t st);
 // condenc[i]: L+1 device pointers of handle i ([B][2R][Tz] per layer, then [B][S][Tz] of postprocess1)
 int arp_run(ArPersist* const* hs, int n, const float* const* const* condenc, int Tz, int ratio, int n_steps, int mode,
             const float* const* uniforms, float* const* audio /* may be NULL */, int32_t* const* indices, float* const* probs_last,
-            hipStream_t st);
+            const ArSampleRow* const* samp /* NULL, or per handle B rows (ar_sampling_rows) */, hipStream_t st);
 int arp_workgroups(const ArPersist* h);
 bool arp_same_launch(const ArPersist* x, const ArPersist* y);
 int arp_error(ArPersist* h, hipStream_t st);   // 0 ok, 1 a spin-wait timed out, -1 HIP error

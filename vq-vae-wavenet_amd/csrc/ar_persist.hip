@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "ar_persist.h"
+#include "ar_sampling.h"
 
 namespace {
 
@@ -76,6 +77,7 @@ struct PArgs {
     float* audio;
     int* indices;
     float* probs_last;
+    ArSampleRow samp[PB];         // per-row temperature / top-k / top-p (ar_sampling.h); .on = 0: the default path
 #ifdef VQW_AR_TRACE
     u64* trace;                   // [gridDim][16 waves][16] accumulated s_memrealtime ticks (tools/ar_trace.py)
 #endif
@@ -99,6 +101,7 @@ struct PGroup {
     int by_handle;     // 1: workgroup g works for handle g % n (a handle's workgroups share XCDs); 0: for handle g / nwg (the
                        // workgroups with the SAME channels of all handles share an XCD, i.e. one L2 copy of their weights)
 };
+static_assert(sizeof(PGroup) <= 4096, "the kernel argument block of a persistent launch");
 
 // LDS carve (in floats), shared by the host (size) and the device (offsets)
 struct Carve {
@@ -259,6 +262,30 @@ __device__ __forceinline__ float chan_sum(float v) {   // sum over the LPC (32 o
 }
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
+// the sampled class idx of row b at step it (lane 0): the next input, the outputs
+__device__ __forceinline__ void emit_row(const PArgs& a, int bi, int b, int t, int it, int idx, float* xh, const float* dtab) {
+    const int Q = a.Q;
+    const bool last = (it == a.n_steps - 1);
+    if (a.n_codes) {
+        // code mode: u > cdf[Q-1] (the float sum of the probabilities may end below 1) gives Q, which is no code:
+        // clamp it to the last code.  The code itself is the next input (stored as code + 1; 0 = no code yet).
+        if (idx > Q - 1) idx = Q - 1;
+        xh[b * a.pre_k + ((t + 1) % a.pre_k)] = (float)(idx + 1);
+        if (bi == 0) {
+            if (a.audio) a.audio[(size_t)b * a.n_steps + it] = (float)idx;
+            if (a.indices) a.indices[(size_t)b * a.n_steps + it] = idx;
+        }
+        return;
+    }
+    const float dec = dtab[idx];                   // p_mu_dec(idx), p_mu_enc(that): tabulated once per launch
+    xh[b * a.pre_k + ((t + 1) % a.pre_k)] = dtab[Q + 1 + idx];
+    if (bi == 0) {
+        if (a.audio) a.audio[(size_t)b * a.n_steps + it] = dec;
+        if (a.indices) a.indices[(size_t)b * a.n_steps + it] = idx;
+        if (last) a.prev[b] = dec;
+    }
+}
+
 // softmax + sampling + mu-law decode of the batch rows this wave owns (row b -> wave b): utils.py:13-46,
 // mu_law_ops.py:26-31.  Every workgroup does it redundantly (identical bits everywhere); xh receives
 // x_in(t+1) = mu_law_encode(decoded sample)  (wavenet.py:113).
@@ -266,6 +293,13 @@ __device__ __forceinline__ void decode_rows(const PArgs& a, int bi, int tid, int
     const int wv = tid >> 6, lane = tid & 63, Q = a.Q;
     for (int b = wv; b < a.B; b += 8) {
         float* lg = xg + (size_t)b * Q;
+        const bool last = (it == a.n_steps - 1);
+        if (a.samp[b].on) {                                // wave-uniform: row b is this wave's
+            const int idx = ar_sample_truncated(lg, Q, a.samp[b], a.uniforms[(size_t)b * a.n_steps + it],
+                                                (bi == 0 && a.probs_last && last) ? a.probs_last + (size_t)b * Q : nullptr);
+            if (lane == 0) emit_row(a, bi, b, t, it, idx, xh, dtab);
+            continue;
+        }
         float m = -INFINITY;
         int mi = 0x7fffffff;
         for (int q = lane; q < Q; q += 64) {
@@ -278,7 +312,6 @@ __device__ __forceinline__ void decode_rows(const PArgs& a, int bi, int tid, int
             const int oi = __shfl_xor(mi, o);
             if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
         }
-        const bool last = (it == a.n_steps - 1);
         if (a.mode != 0 || (a.probs_last && last)) {
             float s = 0.0f;
             for (int q = lane; q < Q; q += 64) {
@@ -309,24 +342,7 @@ __device__ __forceinline__ void decode_rows(const PArgs& a, int bi, int tid, int
                     if (cdf < u) idx = q + 1;
                 }
             }
-            if (a.n_codes) {
-                // code mode: u > cdf[Q-1] (the float sum of the probabilities may end below 1) gives Q, which is no code:
-                // clamp it to the last code.  The code itself is the next input (stored as code + 1; 0 = no code yet).
-                if (idx > Q - 1) idx = Q - 1;
-                xh[b * a.pre_k + ((t + 1) % a.pre_k)] = (float)(idx + 1);
-                if (bi == 0) {
-                    if (a.audio) a.audio[(size_t)b * a.n_steps + it] = (float)idx;
-                    if (a.indices) a.indices[(size_t)b * a.n_steps + it] = idx;
-                }
-                continue;
-            }
-            const float dec = dtab[idx];                   // p_mu_dec(idx), p_mu_enc(that): tabulated once per launch
-            xh[b * a.pre_k + ((t + 1) % a.pre_k)] = dtab[Q + 1 + idx];
-            if (bi == 0) {
-                if (a.audio) a.audio[(size_t)b * a.n_steps + it] = dec;
-                if (a.indices) a.indices[(size_t)b * a.n_steps + it] = idx;
-                if (last) a.prev[b] = dec;
-            }
+            emit_row(a, bi, b, t, it, idx, xh, dtab);
         }
     }
 }
@@ -1053,7 +1069,7 @@ bool arp_same_launch(const ArPersist* x, const ArPersist* y) {
 
 int arp_run(ArPersist* const* hs, int n, const float* const* const* condenc, int Tz, int ratio, int n_steps, int mode,
             const float* const* uniforms, float* const* audio, int32_t* const* indices, float* const* probs_last,
-            hipStream_t st) {
+            const ArSampleRow* const* samp, hipStream_t st) {
     if (n < 1 || n > PGROUP) return vqw_set_error("vqw_ar_decode_run: 1..%d handles per launch (got %d)", PGROUP, n);
     const int cus = device_cus();
     if (n * hs[0]->nwg > cus)
@@ -1075,6 +1091,7 @@ int arp_run(ArPersist* const* hs, int n, const float* const* const* condenc, int
         a.Tz = Tz; a.ratio = ratio; a.mode = mode; a.n_steps = n_steps;
         a.uniforms = uniforms ? uniforms[i] : nullptr; a.audio = audio ? audio[i] : nullptr;
         a.indices = indices ? indices[i] : nullptr; a.probs_last = probs_last ? probs_last[i] : nullptr;
+        for (int b = 0; b < PB; ++b) a.samp[b] = (samp && samp[i] && b < h->B) ? samp[i][b] : ArSampleRow{1.0f, 0, 1.0f, 0};
 #ifdef VQW_AR_TRACE
         if (!h->trace) h->trace = (u64*)pmalloc(h, (size_t)h->nwg * 16 * 16 * sizeof(u64));
         a.trace = h->trace;

@@ -15,6 +15,40 @@ CU_MARGIN = 8   # CUs left free when handles share a launch: a workgroup of a pe
 #                 chosen only when it fits exactly and is what BASELINE.json configs[3] on one GPU asks for)
 
 
+def sampling_settings(batch, mode, temperature=1.0, top_k=0, top_p=1.0):
+    """Validate the sampling keywords of FastGenerator.generate / PriorGenerator.sample and broadcast them to one
+    (temperature, top_k, top_p) per row.  Each keyword is a scalar (every row) or a sequence of `batch` values.
+    temperature: finite, > 0 (1 = off); top_k: integer >= 0 (0 = off, >= the class count = off); top_p: in (0, 1] (1 = off).
+    They apply to mode 'sample' only: a non-default setting with mode 'greedy' is refused.  Returns None when every row is
+    at its defaults (the plain entry points then run, bit for bit today's sampling), else a list of `batch` tuples."""
+    import math
+
+    def rows(name, v):
+        if isinstance(v, (str, bytes)):
+            raise ValueError('%s must be a number or a sequence of %d numbers' % (name, batch))
+        if hasattr(v, 'tolist'):              # numpy / torch scalars and arrays
+            v = v.tolist()
+        if isinstance(v, (list, tuple)):
+            if len(v) != batch:
+                raise ValueError('%s: %d values for a batch of %d rows' % (name, len(v), batch))
+            return list(v)
+        return [v] * batch
+
+    out = []
+    for t, k, p in zip(rows('temperature', temperature), rows('top_k', top_k), rows('top_p', top_p)):
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) or t <= 0:
+            raise ValueError('temperature must be finite and > 0 (got %r)' % (t,))
+        if isinstance(k, bool) or not (isinstance(k, int) or (isinstance(k, float) and k.is_integer())) or k < 0:
+            raise ValueError('top_k must be an integer >= 0 (got %r)' % (k,))
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0 < p <= 1:
+            raise ValueError('top_p must be in (0, 1] (got %r)' % (p,))
+        out.append((float(t), int(k), float(p)))
+    default = all(t == 1.0 and k == 0 and p == 1.0 for t, k, p in out)
+    if not default and mode != 'sample':
+        raise ValueError('temperature / top_k / top_p apply to mode \'sample\' only (mode is %r)' % (mode,))
+    return None if default else out
+
+
 def pick_layout(batch, R, cus):
     """(rows per handle, channels per workgroup [0 = the library's choice]) of a batch.  Rows never interact
     (generate.py:40,103-113), so how they are grouped into handles is free.  Measured at the reference widths
@@ -107,18 +141,22 @@ class FastGenerator:
         for h in self._hs:
             L.check(L.lib().vqw_ar_decode_reset(h, L.stream()))
 
-    def generate(self, encoding, n_steps, mode='greedy', uniforms=None, ratio=None, return_probs=False):
-        """encoding [B][Cc][Tz] (model.encode); continues from the current queue state.
-        Returns (audio [B][n] float32, indices [B][n] int32[, probs of the last step [B][Q]])."""
+    def generate(self, encoding, n_steps, mode='greedy', uniforms=None, ratio=None, return_probs=False,
+                 temperature=1.0, top_k=0, top_p=1.0):
+        """encoding [B][Cc][Tz] (model.encode); continues from the current queue state.  temperature / top_k / top_p
+        (mode 'sample' only; scalars or one value per row): see sampling_settings and vqw_ar_sampling in include/vqwave.h.
+        Returns (audio [B][n] float32, indices [B][n] int32[, probs of the last step [B][Q]: the distribution sampled])."""
         if mode not in ('greedy', 'sample'):
             raise NotImplementedError('decode mode %s not implemented' % mode)   # utils.py:46
+        settings = sampling_settings(self.B, mode, temperature, top_k, top_p)
         B = encoding.shape[0]
         audio = torch.empty(B, n_steps, device=encoding.device)
-        idx, probs = self._run(encoding, n_steps, mode, uniforms, ratio or 64, audio, return_probs)
+        idx, probs = self._run(encoding, n_steps, mode, uniforms, ratio or 64, audio, return_probs, settings)
         return (audio, idx, probs) if return_probs else (audio, idx)
 
-    def _run(self, encoding, n_steps, mode, uniforms, ratio, audio, return_probs):
-        """One run of every handle over its rows; audio may be None (code mode).  Returns (indices, probs of the last step)."""
+    def _run(self, encoding, n_steps, mode, uniforms, ratio, audio, return_probs, settings=None):
+        """One run of every handle over its rows; audio may be None (code mode).  settings: sampling_settings' per-row list,
+        or None (every row at its defaults: the plain entry points).  Returns (indices, probs of the last step)."""
         B, Cc, Tz = encoding.shape
         if B != self.B or Cc != self.model.Cc:
             raise ValueError('encoding must be [%d][%d][Tz]' % (self.B, self.model.Cc))
@@ -135,6 +173,8 @@ class FastGenerator:
         starts = [sum(self._parts[:i]) for i in range(len(self._parts))]
         rows = [slice(b0, b0 + nb) for b0, nb in zip(starts, self._parts)]
         vp = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])  # noqa: E731
+        if settings is not None:
+            return self._run_sampled(encoding, Tz, n_steps, uniforms, ratio, audio, idx, probs, settings, rows, vp)
         for wave in self._waves:                 # one launch per wave; the waves follow each other
             hs = (C.c_void_p * len(wave))(*[self._hs[i].value for i in wave])
             L.check(L.lib().vqw_ar_decode_run_group_async(
@@ -149,6 +189,34 @@ class FastGenerator:
                     L.ptr(idx[rows[wave[0]]]), L.ptr(probs[rows[wave[0]]]) if probs is not None else None, L.stream()))
             for i in wave:
                 L.check(L.lib().vqw_ar_decode_wait(self._hs[i]))
+        return idx, probs
+
+    def _run_sampled(self, encoding, Tz, n_steps, uniforms, ratio, audio, idx, probs, settings, rows, vp):
+        """_run with per-row sampling settings (mode 'sample'): each handle gets its slice of the rows."""
+        lib = L.lib()
+        per = []
+        for r in rows:
+            a = (L.ArSampling * (r.stop - r.start))()
+            for j, (t, k, p) in enumerate(settings[r]):
+                a[j].temperature, a[j].top_k, a[j].top_p = t, min(k, 0x7fffffff), p
+            per.append(a)
+        for wave in self._waves:
+            if lib.vqw_ar_decode_workgroups(self._hs[wave[0]]) > 0:
+                hs = (C.c_void_p * len(wave))(*[self._hs[i].value for i in wave])
+                sp = (C.POINTER(L.ArSampling) * len(wave))(*[C.cast(per[i], C.POINTER(L.ArSampling)) for i in wave])
+                L.check(lib.vqw_ar_decode_run_group_sampled_async(
+                    hs, len(wave), vp([encoding[rows[i]] for i in wave]), Tz, ratio, n_steps, 1,
+                    vp([uniforms[rows[i]] for i in wave]), sp,
+                    vp([audio[rows[i]] for i in wave]) if audio is not None else None, vp([idx[rows[i]] for i in wave]),
+                    vp([probs[rows[i]] for i in wave]) if probs is not None else None, L.stream()))
+            else:
+                i = wave[0]
+                L.check(lib.vqw_ar_decode_run_sampled_async(
+                    self._hs[i], L.ptr(encoding[rows[i]]), Tz, ratio, n_steps, 1, L.ptr(uniforms[rows[i]]), per[i],
+                    L.ptr(audio[rows[i]]) if audio is not None else None, L.ptr(idx[rows[i]]),
+                    L.ptr(probs[rows[i]]) if probs is not None else None, L.stream()))
+            for i in wave:
+                L.check(lib.vqw_ar_decode_wait(self._hs[i]))
         return idx, probs
 
     def close(self):
@@ -185,17 +253,19 @@ class PriorGenerator(FastGenerator):
         super().reset()
         self._t = 0
 
-    def sample(self, n_frames, spk, mode='greedy', uniforms=None, return_probs=False):
+    def sample(self, n_frames, spk, mode='greedy', uniforms=None, return_probs=False, temperature=1.0, top_k=0, top_p=1.0):
         """n_frames codes per row, continuing from the current state.  spk int64 [B] on the GPU.  mode 'greedy' (argmax) or
         'sample' (searchsorted(cumsum(p), u) with uniforms [B][n_frames], drawn here when None; u above the cdf's last
-        value gives the last code).  Returns codes int32 [B][n_frames][, probabilities of the last step [B][k]]."""
+        value gives the last code), tempered / truncated by temperature, top_k, top_p as in FastGenerator.generate.
+        Returns codes int32 [B][n_frames][, probabilities of the last step [B][k]: the distribution sampled]."""
         if mode not in ('greedy', 'sample'):
             raise NotImplementedError('decode mode %s not implemented' % mode)
+        settings = sampling_settings(self.B, mode, temperature, top_k, top_p)
         if spk.numel() != self.B:
             raise ValueError('%d speaker ids for a batch of %d' % (spk.numel(), self.B))
         ratio = 64                                     # code steps per condition frame (prior.CODES_PER_FRAME)
         Tz = -(-(self._t + n_frames) // ratio)
         cond = self.model.speaker_condition(spk.contiguous(), Tz)
-        idx, probs = self._run(cond, n_frames, mode, uniforms, ratio, None, return_probs)
+        idx, probs = self._run(cond, n_frames, mode, uniforms, ratio, None, return_probs, settings)
         self._t += n_frames
         return (idx, probs) if return_probs else idx
