@@ -16,6 +16,13 @@ generator, and written as `<dir>/<step>_<speaker>_prior.wav` (N x 64 samples) pl
 
 `-temperature / -top_k / -top_p` temper and truncate the audio sampling, `-prior_temperature / -prior_top_k / -prior_top_p`
 the code sampling of `-prior` (mode sample only; the same values for every speaker; the defaults are plain sampling).
+
+Prompted generation (the generators are prefilled from a prompt in one teacher-forced pass, FastGenerator.prefill /
+PriorGenerator.prefill): `-prompt_samples N` with `-audio` continues the first N samples of the (trimmed) utterance for every
+speaker; the wav holds them verbatim, then `length - N` generated samples.  `-prompt_frames N` with `-prior` and `-audio`
+prefills the prior with the utterance's first N codes (encode_codes), samples `-frames` more, and decodes all N + frames codes
+with the audio generator prefilled with the utterance's first N x 64 samples (which the wav holds verbatim); the codes file
+holds all N + frames codes.  With `-seed`, uniforms are drawn for the generated samples / codes only.
 """
 import importlib
 import json
@@ -49,9 +56,19 @@ def main():
     parser.add_argument('-prior_temperature', default=1.0, type=float, help='code sampling with -prior: softmax temperature')
     parser.add_argument('-prior_top_k', default=0, type=int, help='code sampling with -prior: top-k (0 = off)')
     parser.add_argument('-prior_top_p', default=1.0, type=float, help='code sampling with -prior: top-p (1 = off)')
+    parser.add_argument('-prompt_samples', default=0, type=int,
+                        help='with -audio: continue the first N samples of the utterance instead of generating from nothing')
+    parser.add_argument('-prompt_frames', default=0, type=int,
+                        help='with -prior and -audio: continue the first N codes (N x 64 samples) of the utterance')
     args = parser.parse_args()
     if args.prior_path is None and args.audio_path is None:
         parser.error('-audio is required (or -prior to sample codes from a latent prior)')
+    if args.prompt_samples < 0 or args.prompt_frames < 0:
+        parser.error('-prompt_samples / -prompt_frames must be >= 0')
+    if args.prompt_samples and args.prior_path is not None:
+        parser.error('-prompt_samples applies to -audio conversion; with -prior use -prompt_frames')
+    if args.prompt_frames and (args.prior_path is None or args.audio_path is None):
+        parser.error('-prompt_frames needs -prior and -audio (the utterance whose codes and samples are the prompt)')
     if args.mode not in ('sample', 'greedy'):
         raise NotImplementedError('decode mode %s not implemented' % args.mode)
 
@@ -71,18 +88,13 @@ def main():
     gs = int(args.restore_path.split('-')[-1].split('.')[0])
     from scipy.io import wavfile
     if args.prior_path is not None:
-        return generate_from_prior(args, pkg, gs, rank, world, dev)
-    sr, wav = wavfile.read(args.audio_path)
-    if wav.ndim > 1:
-        wav = wav[:, 0]
-    wav = wav.astype(np.float32) / 32768.0 if wav.dtype == np.int16 else wav.astype(np.float32)
-    if sr != 16000:
-        from math import gcd
-        from scipy.signal import resample_poly
-        g = gcd(sr, 16000)
-        wav = resample_poly(wav, 16000 // g, sr // g).astype(np.float32)
-    wav = wav[:len(wav) // 512 * 512]          # generate.py:39 (512 = largest dilation)
+        return generate_from_prior(args, pkg, gs, rank, world, dev, parser)
+    wav = read_wav(args.audio_path)
     length = len(wav)
+    n_prompt = args.prompt_samples
+    if n_prompt >= length:
+        parser.error('-prompt_samples %d is not shorter than the trimmed utterance (%d samples): nothing to generate'
+                     % (n_prompt, length))
 
     num_speakers, ids = speaker_ids(args, pkg)
 
@@ -105,19 +117,38 @@ def main():
         uniforms = None
         if args.mode == 'sample':      # one row of uniforms per requested speaker, whatever the sharding
             g = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
-            uniforms = torch.rand(len(ids), length, generator=g)[mine].contiguous().to(dev)
+            uniforms = torch.rand(len(ids), length - n_prompt, generator=g)[mine].contiguous().to(dev)
+        out[:, :n_prompt] = wav[:n_prompt]
         for b0 in range(0, B, 12):             # 12 rows = three 4-row handles in one persistent launch at R=256
             rows = slice(b0, min(b0 + 12, B))
             gen = pkg.generator.FastGenerator(model, batch=rows.stop - rows.start)
-            audio, _ = gen.generate(enc[rows].contiguous(), length, mode=args.mode, ratio=length // enc.shape[2],
+            if n_prompt:
+                gen.prefill(x[:, :n_prompt].expand(rows.stop - rows.start, n_prompt).contiguous(), enc[rows].contiguous(),
+                            ratio=length // enc.shape[2])
+            audio, _ = gen.generate(enc[rows].contiguous(), length - n_prompt, mode=args.mode, ratio=length // enc.shape[2],
                                     uniforms=None if uniforms is None else uniforms[rows].contiguous(),
                                     temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
-            out[rows] = audio.cpu().numpy()
+            out[rows, n_prompt:] = audio.cpu().numpy()
             gen.close()
         for j, i in enumerate(mine):
             s = 'no_speaker' if args.speakers[i] == 'None' else args.speakers[i]
             wavfile.write(save_path + '/%d_%s.wav' % (gs, s), 16000, out[j])
             print('wrote', save_path + '/%d_%s.wav' % (gs, s))
+
+
+def read_wav(path):
+    """The utterance as float32 at 16 kHz, trimmed to a multiple of 512 samples (generate.py:39, 512 = largest dilation)."""
+    from scipy.io import wavfile
+    sr, wav = wavfile.read(path)
+    if wav.ndim > 1:
+        wav = wav[:, 0]
+    wav = wav.astype(np.float32) / 32768.0 if wav.dtype == np.int16 else wav.astype(np.float32)
+    if sr != 16000:
+        from math import gcd
+        from scipy.signal import resample_poly
+        g = gcd(sr, 16000)
+        wav = resample_poly(wav, 16000 // g, sr // g).astype(np.float32)
+    return wav[:len(wav) // 512 * 512]
 
 
 def speaker_ids(args, pkg):
@@ -151,9 +182,16 @@ def load_vqvae(args, pkg, parameters, wavenet_parameters, num_speakers, dev):
     return model
 
 
-def generate_from_prior(args, pkg, gs, rank, world, dev):
-    """Sample codes from the latent prior, decode them with the VQ-VAE's WaveNet (no input utterance)."""
+def generate_from_prior(args, pkg, gs, rank, world, dev, parser):
+    """Sample codes from the latent prior, decode them with the VQ-VAE's WaveNet (no input utterance; with -prompt_frames
+    the utterance's first codes and samples are the prompt of both generators)."""
     from scipy.io import wavfile
+    n_prompt = args.prompt_frames
+    if n_prompt:
+        wav = read_wav(args.audio_path)
+        if n_prompt * 64 > len(wav):
+            parser.error('-prompt_frames %d (%d samples) is longer than the trimmed utterance (%d samples)'
+                         % (n_prompt, n_prompt * 64, len(wav)))
     num_speakers, ids = speaker_ids(args, pkg)
     parameters, wavenet_parameters = pkg.model.load_configs(args.parameter_path)
     prior_cfg = pkg.prior.load_prior_config(args.prior_params, parameters)
@@ -167,20 +205,32 @@ def generate_from_prior(args, pkg, gs, rank, world, dev):
     g = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
     u_codes = torch.rand(len(ids), n, generator=g)[mine].contiguous().to(dev) if args.mode == 'sample' else None
     u_audio = torch.rand(len(ids), length, generator=g)[mine].contiguous().to(dev) if args.mode == 'sample' else None
+    if n_prompt and mine:
+        x = torch.from_numpy(wav).to(dev).unsqueeze(0).contiguous()
+        prompt_codes = model.encode_codes(x, torch.tensor([ids[mine[0]]], dtype=torch.int64, device=dev))[:, :n_prompt]
+        prompt_audio = x[:, :n_prompt * 64]
     for b0 in range(0, len(mine), 8):
         rows = mine[b0:b0 + 8]
         sl = slice(b0, b0 + len(rows))
         spk = torch.tensor([ids[i] for i in rows], dtype=torch.int64, device=dev)
         pgen = pkg.generator.PriorGenerator(prior, batch=len(rows))
+        if n_prompt:
+            pgen.prefill(prompt_codes.expand(len(rows), n_prompt).contiguous(), spk)
         codes = pgen.sample(n, spk, mode=args.mode, uniforms=None if u_codes is None else u_codes[sl].contiguous(),
                             temperature=args.prior_temperature, top_k=args.prior_top_k, top_p=args.prior_top_p)
         pgen.close()
+        if n_prompt:
+            codes = torch.cat([prompt_codes.expand(len(rows), n_prompt), codes], dim=1).contiguous()
         cond = model.condition_from_codes(codes, spk)
         gen = pkg.generator.FastGenerator(model, batch=len(rows))
+        if n_prompt:
+            gen.prefill(prompt_audio.expand(len(rows), n_prompt * 64).contiguous(), cond, ratio=64)
         audio, _ = gen.generate(cond, length, mode=args.mode, ratio=64,
                                 uniforms=None if u_audio is None else u_audio[sl].contiguous(),
                                 temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
         gen.close()
+        if n_prompt:
+            audio = torch.cat([prompt_audio.expand(len(rows), n_prompt * 64), audio], dim=1)
         audio, codes = audio.cpu().numpy(), codes.cpu().numpy()
         for j, i in enumerate(rows):
             s = 'no_speaker' if args.speakers[i] == 'None' else args.speakers[i]

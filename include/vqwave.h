@@ -365,6 +365,23 @@ int vqw_ar_decode_run_group_sampled_async(vqw_ar_decoder* const* hs, int n, cons
                                           int ratio, int n_steps, int mode, const float* const* uniforms,
                                           const vqw_ar_sampling* const* sampling, float* const* audio,
                                           int32_t* const* indices, float* const* probs_last, vqw_stream_t s);
+/* Prefill: leave the handle in the state it would have after vqw_ar_decode_reset and t_end steps teacher-forced on a
+ * prompt (the input of step t is the prompt's value at t - 1, not a sampled one); the next run continues at step t_end
+ * (sample i of it uses encoding[:, :, (t_end + i) / ratio]).  Sequence: vqw_ar_decode_reset, then
+ * vqw_ar_decode_prefill_layer for every layer l, then vqw_ar_decode_prefill_finish, all on one stream.  Each call first
+ * waits for a pending run of the handle, as reset does.
+ * _layer: x [B][R][ld] (device, the handle's rows) holds layer l's input (the residual stream entering layer l) at steps
+ *   t_first .. t_first + ld - 1; the columns must cover steps [max(0, t_end - (kernel_size-1) d_l), t_end), the ones the
+ *   dilation queue keeps, and t_first >= 0.  The persistent kernel's ring slot tau % ((kernel_size-1) d_l + 1) receives
+ *   the granule {tau + 1, value}; the launch-per-phase ring slot tau % ((kernel_size-1) d_l) the value.
+ * _finish: the input history and the step counter.  audio_tail [B][pre_k] float = a[t_end-pre_k .. t_end) (audio handles:
+ *   the input of step t is mu_law_encode(a[t-1])), or code_tail int32 [B][pre_k] = c[t_end-pre_k .. t_end) in [0, n_codes)
+ *   (vqw_ar_prior_create handles: the input of step t is code c[t-1]); device pointers, entries before step 0 ignored;
+ *   exactly one is non-NULL.  t_end = 0 leaves the handle as reset left it.
+ * A bad layer, t_end < 0, a window that does not cover the steps, or the wrong tail for the handle's mode is an error.   */
+int vqw_ar_decode_prefill_layer(vqw_ar_decoder* h, int l, const float* x, int ld, int t_first, int t_end, vqw_stream_t s);
+int vqw_ar_decode_prefill_finish(vqw_ar_decoder* h, int t_end, const float* audio_tail, const int32_t* code_tail,
+                                 vqw_stream_t s);
 /* workgroups (= CUs held for the whole run) of the handle's persistent kernel; 0: launch-per-phase path */
 int vqw_ar_decode_workgroups(const vqw_ar_decoder* h);
 int vqw_ar_decode_destroy(vqw_ar_decoder* h);

@@ -160,6 +160,8 @@ SIGNATURES = {
     'vqw_ar_decode_run_group_sampled_async': (_i, [C.POINTER(_fp), _i, C.POINTER(_fp), _i, _i, _i, _i, C.POINTER(_fp),
                                                    C.POINTER(C.POINTER(ArSampling)), C.POINTER(_fp), C.POINTER(_fp),
                                                    C.POINTER(_fp), _fp]),
+    'vqw_ar_decode_prefill_layer': (_i, [_fp, _i, _fp, _i, _i, _i, _fp]),
+    'vqw_ar_decode_prefill_finish': (_i, [_fp, _i, _fp, _fp, _fp]),
     'vqw_ar_decode_workgroups': (_i, [_fp]),
     'vqw_ar_decode_destroy': (_i, [_fp]),
     'vqw_ar_prior_create': (_i, [C.POINTER(_fp), C.POINTER(ArWeights), _i, _i, _i]),

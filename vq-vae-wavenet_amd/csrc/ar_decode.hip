@@ -516,6 +516,87 @@ extern "C" int vqw_ar_decode_reset(vqw_ar_decoder* h, vqw_stream_t s) {
     return 0;
 }
 
+namespace {
+
+// Prefill of the launch-per-phase rings: layer l's inputs at steps t_lo .. t_lo+nt-1, slot tau % depth (depth = (ks-1) d:
+// the slot the gate kernel reads as tap x(t - (ks-1) d) and MODE_OUT pushes).  x [B][R][ld], column tau - t_first.
+__global__ void ar_prefill_ring_kernel(float* ring, int depth, int BR, const float* __restrict__ x, int ld, int t_first, int t_lo,
+                                       int nt) {
+    const size_t n = (size_t)BR * nt;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t bc = i / nt;                          // b * R + c
+        const int tau = t_lo + (int)(i - bc * nt);
+        ring[(size_t)(tau % depth) * BR + bc] = x[bc * ld + (tau - t_first)];
+    }
+}
+
+// The preprocess queue (slot tau % pre_k = x_in(tau) = mu_law_encode(a[tau - 1]) for tau in (t_end - pre_k, t_end]), the
+// last sample and the step counter.  tail[b][j] is a[t_end - pre_k + j]; entries before step 0 keep the reset's zeros.
+// audio_tail NULL (a code-mode handle, whose history lives in the persistent kernel): only the step counter.
+__global__ void ar_prefill_finish_kernel(ArState* st, float* prev, float* xring, int B, int pre_k, int t_end,
+                                         const float* audio_tail) {
+    if (audio_tail) {
+        for (int i = threadIdx.x; i < B * pre_k; i += blockDim.x) {
+            const int b = i / pre_k, s = t_end - pre_k + i % pre_k;
+            if (s >= 0) xring[b * pre_k + (s + 1) % pre_k] = mu_enc(audio_tail[i]);
+        }
+        if (t_end > 0)
+            for (int b = threadIdx.x; b < B; b += blockDim.x) prev[b] = audio_tail[b * pre_k + pre_k - 1];
+    }
+    if (threadIdx.x == 0) st->step = t_end;
+}
+
+}  // namespace
+
+extern "C" int vqw_ar_decode_prefill_layer(vqw_ar_decoder* h, int l, const float* x, int ld, int t_first, int t_end,
+                                           vqw_stream_t s) {
+    VQW_CHECK(h, "vqw_ar_decode_prefill_layer: null handle");
+    VQW_CHECK(l >= 0 && l < h->w.n_layers, "vqw_ar_decode_prefill_layer: layer %d outside 0..%d", l, h->w.n_layers - 1);
+    VQW_CHECK(t_end >= 0, "vqw_ar_decode_prefill_layer: t_end=%d < 0", t_end);
+    const int span = (h->w.kernel_size - 1) * h->dil[l];
+    const int t_lo = t_end > span ? t_end - span : 0;
+    VQW_CHECK(t_first >= 0 && t_first <= t_lo && ld >= t_end - t_first,
+              "vqw_ar_decode_prefill_layer: columns [%d, %d) do not cover layer %d's steps [%d, %d)", t_first, t_first + ld, l,
+              t_lo, t_end);
+    if (t_end == t_lo) return 0;
+    VQW_CHECK(x, "vqw_ar_decode_prefill_layer: null x");
+    if (h->pending) {
+        const int rcw = vqw_ar_decode_wait(h);
+        if (rcw) return rcw;
+    }
+    hipStream_t st = (hipStream_t)s;
+    if (h->persist) return arp_prefill_layer(h->persist, l, x, ld, t_first, t_lo, t_end, st);
+    const int BR = h->B * h->w.R, nt = t_end - t_lo;
+    const int blocks = (int)(((size_t)BR * nt + 255) / 256 < 2048 ? ((size_t)BR * nt + 255) / 256 : 2048);
+    hipLaunchKernelGGL(ar_prefill_ring_kernel, dim3(blocks), dim3(256), 0, st, h->rings[l], span, BR, x, ld, t_first, t_lo, nt);
+    VQW_LAUNCH_CHECK("vqw_ar_decode_prefill_layer");
+    return 0;
+}
+
+extern "C" int vqw_ar_decode_prefill_finish(vqw_ar_decoder* h, int t_end, const float* audio_tail, const int32_t* code_tail,
+                                            vqw_stream_t s) {
+    VQW_CHECK(h, "vqw_ar_decode_prefill_finish: null handle");
+    VQW_CHECK(t_end >= 0, "vqw_ar_decode_prefill_finish: t_end=%d < 0", t_end);
+    VQW_CHECK((audio_tail == nullptr) != (code_tail == nullptr),
+              "vqw_ar_decode_prefill_finish: exactly one of audio_tail / code_tail must be given");
+    VQW_CHECK(h->n_codes > 0 ? code_tail != nullptr : audio_tail != nullptr,
+              "vqw_ar_decode_prefill_finish: a %s handle takes %s", h->n_codes > 0 ? "code-input" : "audio",
+              h->n_codes > 0 ? "code_tail" : "audio_tail");
+    if (h->pending) {
+        const int rcw = vqw_ar_decode_wait(h);
+        if (rcw) return rcw;
+    }
+    hipStream_t st = (hipStream_t)s;
+    if (h->persist) {
+        const int rc = arp_prefill_finish(h->persist, t_end, audio_tail, code_tail, st);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(ar_prefill_finish_kernel, dim3(1), dim3(256), 0, st, h->st, h->prev, h->xring, h->B, h->w.pre_k, t_end,
+                       audio_tail);
+    VQW_LAUNCH_CHECK("vqw_ar_decode_prefill_finish");
+    return 0;
+}
+
 extern "C" int vqw_ar_decode_wait(vqw_ar_decoder* h) {
     VQW_CHECK(h, "vqw_ar_decode_wait: null handle");
     if (!h->pending) return 0;

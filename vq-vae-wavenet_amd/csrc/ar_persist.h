@@ -15,6 +15,10 @@ int arp_reset(ArPersist* h, hipStream_t st);
 int arp_run(ArPersist* const* hs, int n, const float* const* const* condenc, int Tz, int ratio, int n_steps, int mode,
             const float* const* uniforms, float* const* audio /* may be NULL */, int32_t* const* indices, float* const* probs_last,
             const ArSampleRow* const* samp /* NULL, or per handle B rows (ar_sampling_rows) */, hipStream_t st);
+// prefill after arp_reset (vqw_ar_decode_prefill_layer / _finish): layer l's ring slots t_lo .. t_end-1 from x [B][R][ld]
+// (column tau - t_first); then the input history, the last sample and the step counter
+int arp_prefill_layer(ArPersist* h, int l, const float* x, int ld, int t_first, int t_lo, int t_end, hipStream_t st);
+int arp_prefill_finish(ArPersist* h, int t_end, const float* audio_tail, const int32_t* code_tail, hipStream_t st);
 int arp_workgroups(const ArPersist* h);
 bool arp_same_launch(const ArPersist* x, const ArPersist* y);
 int arp_error(ArPersist* h, hipStream_t st);   // 0 ok, 1 a spin-wait timed out, -1 HIP error

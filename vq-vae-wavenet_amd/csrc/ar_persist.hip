@@ -31,6 +31,7 @@
 // bounded by a wall-clock timeout (s_memrealtime) that sets an error word and drains the grid.
 #include <string.h>
 
+#include <algorithm>
 #include <type_traits>
 #include <vector>
 
@@ -922,6 +923,7 @@ struct ArPersist {
     const void* kfn = nullptr;
     size_t lds_bytes = 0;
     std::vector<std::pair<void*, size_t>> zero_on_reset;
+    std::vector<int> dil_h, roff_h;  // host copies of the dilations and ring offsets (prefill)
 #ifdef VQW_AR_TRACE
     u64* trace = nullptr;
     int trace_steps = 0;
@@ -1024,6 +1026,8 @@ int arp_create(ArPersist** out, const vqw_ar_weights* w, const int* dil, const f
             hipMemcpy(dtab + L, roff.data(), L * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
             return fail("hipMemcpy failed");
         a.dil = dtab; a.ring_off = dtab + L;
+        h->dil_h.assign(dil, dil + L);
+        h->roff_h = roff;
         a.rings = (u64*)pmalloc(h, (size_t)total * sizeof(u64));
         if (!a.rings) return fail("hipMalloc failed");
         h->zero_on_reset.push_back({a.rings, (size_t)total * sizeof(u64)});
@@ -1058,6 +1062,56 @@ int arp_create(ArPersist** out, const vqw_ar_weights* w, const int* dil, const f
 
 int arp_reset(ArPersist* h, hipStream_t st) {
     for (auto& z : h->zero_on_reset) PHIPC(hipMemsetAsync(z.first, 0, z.second, st));
+    return 0;
+}
+
+namespace {
+
+// Prefill (vqw_ar_decode_prefill_layer): layer l's inputs at steps t_lo .. t_lo+nt-1 into its ring, slot tau % depth, as the
+// granule {tau + 1, bits} the run loop's own publish leaves there (same relaxed agent-scope store).  x [B][R][ld], column
+// tau - t_first.  One thread per (row, channel, step), the step fastest: the reads of a wave are contiguous.
+__global__ void arp_prefill_layer_kernel(u64* ring, int depth, int BR, const float* __restrict__ x, int ld, int t_first,
+                                         int t_lo, int nt) {
+    const size_t n = (size_t)BR * nt;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t bc = i / nt;                          // b * R + c
+        const int tau = t_lo + (int)(i - bc * nt);
+        publish(ring + (size_t)(tau % depth) * BR + bc, (unsigned)tau + 1u, x[bc * ld + (tau - t_first)]);
+    }
+}
+
+// The input history the run loop would have saved after step t_end - 1: slot tau % pre_k holds x_in(tau) for
+// tau in (t_end - pre_k, t_end], x_in(tau) = mu_law_encode(a[tau - 1]) (audio) or c[tau - 1] + 1 (codes; 0 = no code).
+// tail[b][j] is prompt entry t_end - pre_k + j; entries before step 0 keep the reset's zeros.
+__global__ void arp_prefill_finish_kernel(float* xhist, float* prev, int* state, int B, int pre_k, int t_end,
+                                          const float* audio_tail, const int32_t* code_tail) {
+    for (int i = threadIdx.x; i < B * pre_k; i += blockDim.x) {
+        const int b = i / pre_k, s = t_end - pre_k + i % pre_k;
+        if (s < 0) continue;
+        xhist[b * pre_k + (s + 1) % pre_k] = audio_tail ? p_mu_enc(audio_tail[i]) : (float)(code_tail[i] + 1);
+    }
+    if (audio_tail && t_end > 0)
+        for (int b = threadIdx.x; b < B; b += blockDim.x) prev[b] = audio_tail[b * pre_k + pre_k - 1];
+    if (threadIdx.x == 0) { state[0] = t_end; state[1] = 0; }
+}
+
+}  // namespace
+
+int arp_prefill_layer(ArPersist* h, int l, const float* x, int ld, int t_first, int t_lo, int t_end, hipStream_t st) {
+    const int nt = t_end - t_lo, BR = h->B * h->w.R;
+    if (nt <= 0) return 0;
+    const int depth = (h->w.kernel_size - 1) * h->dil_h[l] + 1;
+    const int blocks = (int)std::min<size_t>(((size_t)BR * nt + 255) / 256, 2048);
+    hipLaunchKernelGGL(arp_prefill_layer_kernel, dim3(blocks), dim3(256), 0, st, h->args.rings + h->roff_h[l], depth, BR, x, ld,
+                       t_first, t_lo, nt);
+    VQW_LAUNCH_CHECK("vqw_ar_decode_prefill_layer(persistent)");
+    return 0;
+}
+
+int arp_prefill_finish(ArPersist* h, int t_end, const float* audio_tail, const int32_t* code_tail, hipStream_t st) {
+    hipLaunchKernelGGL(arp_prefill_finish_kernel, dim3(1), dim3(256), 0, st, h->args.xhist, h->args.prev, h->args.state, h->B,
+                       h->args.pre_k, t_end, audio_tail, code_tail);
+    VQW_LAUNCH_CHECK("vqw_ar_decode_prefill_finish(persistent)");
     return 0;
 }
 

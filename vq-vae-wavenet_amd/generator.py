@@ -141,6 +141,47 @@ class FastGenerator:
         for h in self._hs:
             L.check(L.lib().vqw_ar_decode_reset(h, L.stream()))
 
+    def prefill(self, prompt, encoding, ratio=None):
+        """Leave every row in the state it would have after reset() and T = prompt.shape[1] steps teacher-forced on its prompt
+        (the input of step t is mu_law_encode(prompt[t-1]), zero at t = 0): the next generate() continues at step T, sample T + i
+        using condition frame (T + i) // ratio of the encoding it is given.  prompt float32 [B][T] in [-1, 1] on the GPU;
+        encoding [B][Cc][Tz] (model.encode), the one the later generate calls use, with Tz * ratio >= T.  T = 0 is reset().
+        One teacher-forced pass over at most model.prefill_window's window (VQVAE.decoder_states), scattered into the rings."""
+        ratio = ratio or 64
+        if not isinstance(prompt, torch.Tensor) or prompt.dtype != torch.float32 or prompt.dim() != 2 or prompt.shape[0] != self.B:
+            raise ValueError('prompt must be a float32 [%d][T] tensor' % self.B)
+        if (not isinstance(encoding, torch.Tensor) or encoding.dtype != torch.float32 or encoding.dim() != 3
+                or encoding.shape[0] != self.B or encoding.shape[1] != self.model.Cc):
+            raise ValueError('encoding must be a float32 [%d][%d][Tz] tensor' % (self.B, self.model.Cc))
+        T = prompt.shape[1]
+        if T > encoding.shape[2] * ratio:
+            raise ValueError('a prompt of %d samples is longer than the encoding (%d frames x %d)' % (T, encoding.shape[2], ratio))
+        L.require_cuda(prompt.contiguous(), encoding.contiguous())
+        self._prefill(prompt.contiguous(), encoding.contiguous(), T, ratio, audio=True)
+
+    def _prefill(self, x, cond, T, ratio, audio):
+        """reset, then the prompt's layer inputs into every handle's rings (each handle its slice of the rows), then the input
+        history and the step counter (vqw_ar_decode_prefill_layer / _finish)."""
+        lib, st = L.lib(), L.stream()
+        for h in self._hs:
+            L.check(lib.vqw_ar_decode_reset(h, st))
+        starts = [sum(self._parts[:i]) for i in range(len(self._parts))]
+        rows = [slice(b0, b0 + nb) for b0, nb in zip(starts, self._parts)]
+        if T == 0:
+            return
+        x = x.contiguous()
+
+        def sink(l, net, s0):
+            for h, r in zip(self._hs, rows):
+                L.check(lib.vqw_ar_decode_prefill_layer(h, l, L.ptr(net[r]), net.shape[2], s0, T, st))
+        self.model.decoder_states(x, cond, T, sink, ratio)
+        pk = self.model.pre_k
+        n = min(T, pk)
+        tail = torch.zeros(self.B, pk, dtype=x.dtype, device=x.device)
+        tail[:, pk - n:] = x[:, T - n:T]
+        for h, r in zip(self._hs, rows):
+            L.check(lib.vqw_ar_decode_prefill_finish(h, T, L.ptr(tail[r]) if audio else None, None if audio else L.ptr(tail[r]), st))
+
     def generate(self, encoding, n_steps, mode='greedy', uniforms=None, ratio=None, return_probs=False,
                  temperature=1.0, top_k=0, top_p=1.0):
         """encoding [B][Cc][Tz] (model.encode); continues from the current queue state.  temperature / top_k / top_p
@@ -252,6 +293,23 @@ class PriorGenerator(FastGenerator):
         """Empty history ("no code yet": a zero one-hot, not code 0); the next sample is step 0."""
         super().reset()
         self._t = 0
+
+    def prefill(self, codes, spk):
+        """Leave every row in the state it would have after reset() and T = codes.shape[1] steps teacher-forced on its codes
+        (the input of step t is c[t-1], no code at t = 0): the next sample() continues at step T.  codes int32 [B][T] in [0, k)
+        on the GPU, spk int64 [B] (the speakers the later sample calls use).  T = 0 is reset()."""
+        if (not isinstance(codes, torch.Tensor) or codes.dtype != torch.int32 or codes.dim() != 2 or codes.shape[0] != self.B
+                or not codes.is_cuda):
+            raise ValueError('codes must be an int32 [%d][T] tensor on the GPU' % self.B)
+        if spk.numel() != self.B:
+            raise ValueError('%d speaker ids for a batch of %d' % (spk.numel(), self.B))
+        T = codes.shape[1]
+        if T and (int(codes.min()) < 0 or int(codes.max()) >= self.model.Q):
+            raise ValueError('codes must lie in [0, %d)' % self.model.Q)
+        ratio = 64                                     # code steps per condition frame (prior.CODES_PER_FRAME)
+        cond = self.model.speaker_condition(spk.contiguous(), max(1, -(-T // ratio)))
+        self._prefill(codes.contiguous(), cond, T, ratio, audio=False)
+        self._t = T
 
     def sample(self, n_frames, spk, mode='greedy', uniforms=None, return_probs=False, temperature=1.0, top_k=0, top_p=1.0):
         """n_frames codes per row, continuing from the current state.  spk int64 [B] on the GPU.  mode 'greedy' (argmax) or

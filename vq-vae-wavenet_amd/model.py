@@ -37,6 +37,22 @@ def load_configs(model_json='model_parameters.json', wavenet_json=None):
     return m, w
 
 
+def prefill_window(t_end, ks, dilations, pre_k, ratio):
+    """The window of a prompt of t_end steps that a prefill computes (VQVAE.decoder_states): (W, s0, end).
+    W = (ks-1) * sum(dilations) + pre_k is how far back a step can reach into the generator's state after the prompt: layer l's
+    oldest queued step t_end - (ks-1) d_l looks back (ks-1) * sum_{j<l} d_j + pre_k - 1 inputs more, and the input of step t
+    is the prompt's value at t - 1.  s0 = max(0, t_end - W) rounded down to a multiple of ratio (whole condition frames);
+    end = t_end rounded up to a multiple of ratio (the columns past t_end are zeros: the convs are causal, nothing before
+    t_end sees them).  The zero history that the window's left edge brings (its first input included) only reaches steps
+    before t_end - W + 1, which the state does not keep.  t_end = 0: an empty window (0, 0)."""
+    if t_end < 0 or ratio < 1:
+        raise ValueError('prefill_window: t_end must be >= 0 and ratio >= 1 (got %d, %d)' % (t_end, ratio))
+    W = (ks - 1) * sum(dilations) + pre_k
+    s0 = max(0, t_end - W) // ratio * ratio
+    end = -(-t_end // ratio) * ratio
+    return W, s0, end
+
+
 def same_pads(n, k, s):
     """TF 'SAME' padding (left, right) -- SURVEY.md Appendix A-4."""
     out = -(-n // s)
@@ -1466,6 +1482,55 @@ class VQVAE:
         K.speaker_tile_fwd(self.P['speaker_embedding'] if self.spk_table else self.onehot, spk, cond,
                            cond_bstride=self.Cc * Tz, row0=self.D, Cs=self.Cs_eff, Tz=Tz)
         return cond
+
+    def decoder_states(self, x, cond, t_end, sink, ratio=64):
+        """The decoder's teacher-forced states after a prompt, for a generator's prefill: the input stage and the residual
+        stack over prefill_window's window [s0, end) of x (x [B][>= t_end]: raw audio in [-1, 1], or codes for the prior, the
+        _decode_input hook's input), with the condition cond [B][Cc][Tz] of the whole utterance (Tz * ratio >= end).  Hands
+        net[l] (the input of layer l, [B][R][end - s0], column t - s0) to sink(l, net_l, s0) for l = 0 .. L-1 as soon as it is
+        made; a buffer is reused two layers later, so sink must consume it (enqueue its reads) before it returns.  Runs on the
+        fp32-MFMA engine (the generator is fp32) and never touches the encoder or the training workspace.  Returns (s0, end)."""
+        self.finish_steps()
+        B = x.shape[0]
+        Cc, Tz = cond.shape[1], cond.shape[2]
+        W, s0, end = prefill_window(t_end, self.ks, self.dil, self.pre_k, ratio)
+        if x.dim() != 2 or x.shape[1] < t_end or cond.shape[0] != B or Cc != self.Cc or Tz * ratio < end:
+            raise ValueError('decoder_states: x [B][>= %d] and cond [B][%d][>= %d] expected (got %s, %s)'
+                             % (t_end, self.Cc, -(-end // ratio), tuple(x.shape), tuple(cond.shape)))
+        Tw = end - s0
+        if Tw == 0:
+            return s0, end
+        P, R, L, Mall = self.P, self.R, self.L, self.Mall
+        dev = self.dev
+        xw = torch.zeros(B, Tw, dtype=x.dtype, device=dev)
+        xw[:, :t_end - s0] = x[:, s0:t_end]
+        Tzw = Tw // ratio
+        cw = cond[:, :, s0 // ratio:end // ratio].contiguous()
+        ce = torch.empty(B, Mall, Tzw, device=dev)
+        if self.cond_proj:
+            K.cond_proj_fwd(cw, P['cond_w'], ce, B=B, Cc=Cc, Mall=Mall, Tz=Tzw)
+        else:
+            K.conv_gemm(x0=cw, w=P['cond_w'], out0=ce, B=B, T_in=Tzw, T_out=Tzw, M=Mall, C0=Cc, taps=[0])
+        ce_flat = ce.view(-1)
+        net = [torch.empty(B, R, Tw, device=dev) for _ in range(2)]
+        gated = torch.empty(B, R, Tw, device=dev)
+        ws = {'B': B, 'T': Tw, 'Tz': Tzw, 'inputs': torch.empty(B, Tw, device=dev),
+              'labels': torch.empty(B, Tw, dtype=torch.int32, device=dev), 'net': [net[0]]}
+        self._decode_input(xw, ws)
+        sink(0, net[0], s0)
+        S = self.S
+        for l in range(L - 1):           # the top layer's output is not part of the state
+            cur, nxt = net[l & 1], net[(l + 1) & 1]
+            d = self.dil[l]
+            K.conv_gemm(x0=cur, w=P['gated_w'][l], bias=P['gated_b'][l], out0=gated, cond=ce_flat[l * 2 * R * Tzw:],
+                        cond_T=Tzw, cond_bstride=Mall * Tzw, B=B, T_in=Tw, T_out=Tw, M=2 * R, C0=R,
+                        taps=[-(self.ks - 1 - j) * d for j in range(self.ks)], epilogue=K.EPI_GATE)
+            # the residual half of the 1x1 skip | residual conv only (the skip sum is not part of the state): M0 = 0, every
+            # row goes to out1 = aux1 + conv (out0 is never written)
+            K.conv_gemm(x0=gated, w=P['out_w'][l].view(-1)[S:], ldw=S + R, bias=P['out_b'][l][S:], out1=nxt, aux1=cur,
+                        out0=nxt, B=B, T_in=Tw, T_out=Tw, M=R, M0=0, C0=R, taps=[0], epilogue=K.EPI_ACCUM_SPLIT)
+            sink(l + 1, nxt, s0)
+        return s0, end
 
     def free_workspaces(self):
         """Drop the cached (B, T) workspaces (a long-running host changing shapes would otherwise keep them all)."""
