@@ -428,7 +428,10 @@ int vqw_prior_input_wgrad(const int32_t* order, const int32_t* starts, const flo
  *   vqw_f16x3_amax           amax[i] = max(amax[i], bits(max |x_i|)) over `count` strided matrices [rows][cols]
  *                            (row stride ld, matrix stride mstride); raises *flag on inf / NaN;
  *   vqw_f16x3_update_scales  scale[i] = 2^k with amax[i] * scale[i] in [2^(target_exp-1), 2^target_exp); a slot whose
- *                            amax is 0 keeps its scale; reset != 0 zeroes amax[] for the next collection.
+ *                            amax is 0 keeps its scale (a scale of 0 becomes 1); a non-finite amax raises *flag and keeps
+ *                            the scale; reset != 0 zeroes amax[] for the next collection.  k is held to [-100, 100]: an amax
+ *                            below 2^(target_exp-101) (fp32 subnormals included) or from 2^(target_exp+100) on gets
+ *                            2^100 / 2^-100 and misses the interval.
  * Kernels that WRITE planes take the scale from a device slot (`*_scale` / `scale_dev` below), report the max-abs of
  * their fp32 values into `out_amax` (the scale of the NEXT step comes from it) and raise *flag (|= 1) when an element
  * leaves fp16's range or is not finite: the host then repeats the step on the fp32 engine (model.py).  Every guard

@@ -38,9 +38,14 @@ __device__ __forceinline__ void split8(const float (&x)[8], uint4& p0, uint4& p1
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         if (BF) { a[e] = bf16_bits(x[e]); b[e] = 0; continue; }
-        const _Float16 h1 = (_Float16)x[e];            // round to nearest even
+        // Both pieces come from ONE fp32 value the compiler cannot look through: left to itself it rounds the caller's scale * x once more
+        // as v_fma_mixlo_f16(scale, x, 0) for the residual of two of the eight elements, and (-0) * scale + 0 = +0 makes the residual
+        // of x = -0 come out as -0 there instead of +0 (tests/test_x3_range_gpu.py, plane bytes).  No instruction is emitted.
+        float xe = x[e];
+        asm volatile("" : "+v"(xe));
+        const _Float16 h1 = (_Float16)xe;              // round to nearest even
         a[e] = f16_bits(h1);
-        b[e] = f16_bits((_Float16)(x[e] - (float)h1)); // the difference is exact in fp32
+        b[e] = f16_bits((_Float16)(xe - (float)h1));   // the difference is exact in fp32
     }
     p0 = make_uint4(a[0] | ((unsigned)a[1] << 16), a[2] | ((unsigned)a[3] << 16), a[4] | ((unsigned)a[5] << 16), a[6] | ((unsigned)a[7] << 16));
     p1 = make_uint4(b[0] | ((unsigned)b[1] << 16), b[2] | ((unsigned)b[3] << 16), b[4] | ((unsigned)b[5] << 16), b[6] | ((unsigned)b[7] << 16));
