@@ -245,6 +245,28 @@ int vqw_softmax_xent_bwd(const float* logits, const int32_t* labels, float* dlog
                          int B, int Q, int T, vqw_stream_t s);
 
 /* ------------------------------------------------------------------------------------
+ * Held-out scoring: logits -> scores, no gradients.
+ * logits [B][Q][T], labels int32 [B][T]; t_begin / t_end int32 [B] on the device (either may be NULL: 0 / T).  Position
+ * (b, t) is SCORED iff t_begin[b] <= t < t_end[b].  In nats:
+ *   nll[b][t]     = logsumexp_q z - z[label]                 (optional; positions that are not scored read 0)
+ *   entropy[b][t] = logsumexp_q z - sum_q softmax(z)_q z_q   (optional; positions that are not scored read 0)
+ *   row_sums   double [B][2] = { sum of nll, sum of entropy } over the row's scored positions
+ *   row_counts int32  [B][2] = { scored positions, hits }; a hit: the label is the LOWEST index among the maxima of the
+ *                              position's logits (the generators' greedy decision)
+ * The row sums are bitwise reproducible and depend on that row's logits only (one partial per 64-step tile from a fixed
+ * shuffle tree, tiles added in a fixed order in double precision; no floating-point atomics): row b scored alone gives
+ * the same bits as inside a batch.  scratch: 4 * B * ceil(T / 64) floats, 16-byte aligned (the tile partials).
+ * Q % 4 == 0, 4 <= Q <= 1024; any T.  A label outside [0, Q) scores as logit 0 and never hits.                    */
+int vqw_softmax_score(const float* logits, const int32_t* labels, const int32_t* t_begin, const int32_t* t_end,
+                      float* nll, float* entropy, double* row_sums, int32_t* row_counts, float* scratch,
+                      int64_t scratch_floats, int B, int Q, int T, vqw_stream_t s);
+/* counts[c] += #{(b, f) : idx[b][f] == c, f < f_end[b]} for the int64 [B][Tz] indices vqw_vq_nearest_fwd writes (f_end int32
+ * [B] on the device, or NULL: all Tz frames).  Integer atomics: exact.  counts int32 [K] is ADDED to (zero it for a fresh
+ * histogram).  An index outside [0, K) is counted nowhere and sets flag[0] (device int32) non-zero.                 */
+int vqw_code_histogram(const int64_t* idx, const int32_t* f_end, int32_t* counts, int32_t* flag, int B, int Tz, int K,
+                       vqw_stream_t s);
+
+/* ------------------------------------------------------------------------------------
  * The decoder's local-condition projections -- add_condition, wavenet_ops.py:93-101: a 1x1 conv1d_v2 of the condition
  * per gated_cnn and for postprocess1 (wavenet.py:58-100).  All L + 1 kernels side by side are one matrix
  * w[Cc][Mall] (Mall = L * 2R + S); cond [B][Cc][Tz], out / dce [B][Mall][Tz], dcond [B][Cc][Tz].

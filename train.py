@@ -7,6 +7,12 @@
 Differences from the reference: `-dataset synthetic` needs no files; checkpoints are torch
 files `<save>-<global_step>.pt` (the reference writes TF checkpoints `<save>-<global_step>`);
 TF summaries are replaced by the console line.
+
+`-eval_list FILE -eval_interval N [-eval_batches M]`: every N steps rank 0 scores the same M held-out batches with the EMA
+weights (VQVAE.evaluate, forward only: the first `-length` samples of the first M x batch files of the list that are long
+enough, so the curve is comparable from step to step), adds `[eval bits ...]` to the console line and an `eval` object to
+that step's line of summaries.jsonl.  The list is in the format of the `<name>_train.txt` lists, read under `-data_root` as
+`-eval_dataset` (default: `-dataset`; VCTK when that is synthetic).
 """
 import importlib
 import json
@@ -43,7 +49,26 @@ def main():
     parser.add_argument('-restore', dest='restore_path', metavar='string', help='path to restore weights')
     parser.add_argument('-save', default='saved_model/weights', dest='save_path', metavar='string', help='path to save weights')
     parser.add_argument('-params', default='model_parameters.json', dest='parameter_path', metavar='str', help='path to parameters file')
+    parser.add_argument('-eval_list', dest='eval_list', metavar='string', help='held-out file list scored during training')
+    parser.add_argument('-eval_interval', default=0, type=int, dest='eval_interval', metavar='int', help='score the list every N steps (0 = never)')
+    parser.add_argument('-eval_batches', default=4, type=int, dest='eval_batches', metavar='int', help='held-out batches per evaluation')
+    parser.add_argument('-eval_dataset', default=None, dest='eval_dataset', metavar='DATASET', help='dataset the list belongs to (default: -dataset)')
+    parser.add_argument('-data_root', default='data/', dest='data_root', metavar='string', help='where the held-out wavs and *_speakers.txt are')
     args = parser.parse_args()
+    if args.eval_interval < 0 or args.eval_batches < 1:
+        parser.error('-eval_interval must be >= 0 and -eval_batches >= 1')
+    if args.eval_interval > 0 and args.eval_list is None:
+        parser.error('-eval_interval needs -eval_list')
+    if args.eval_list is not None:
+        if args.eval_interval == 0:
+            parser.error('-eval_list needs -eval_interval N (N > 0): the list would never be scored')
+        if not os.path.isfile(args.eval_list):
+            parser.error('-eval_list: no such file: %s' % args.eval_list)
+        args.eval_dataset = args.eval_dataset or ('VCTK' if args.dataset == 'synthetic' else args.dataset)
+        if args.eval_dataset not in ('VCTK', 'LibriSpeech', 'Aishell'):
+            parser.error('-eval_dataset must be VCTK, LibriSpeech or Aishell')
+    elif args.eval_dataset is not None:
+        parser.error('-eval_dataset needs -eval_list')
 
     pkg = importlib.import_module('vq-vae-wavenet_amd')
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -89,21 +114,41 @@ def main():
     if rank == 0 and not os.path.isdir(save_dir):
         os.mkdir(save_dir)
 
+    eval_set = None
+    if args.eval_list is not None and rank == 0:      # the same crops at every evaluation, read once
+        ratio = 320 if parameters['encoder'] == '2019' else 64
+        if args.max_len % ratio:
+            raise ValueError('-length must be a multiple of %d to score a held-out list' % ratio)
+        held = D.HeldOutList(args.eval_dataset, args.eval_list, relative_path=args.data_root, ratio=ratio)
+        if held.num_speakers != dataset.num_speakers:
+            raise ValueError('-eval_list: %d speakers under %s, the model has %d' % (held.num_speakers, args.data_root, dataset.num_speakers))
+        crops, _ = held.crops(args.max_len, limit=args.eval_batches * args.batch_size)
+        if not crops:
+            raise ValueError('-eval_list: no file of %s has %d samples' % (args.eval_list, args.max_len))
+        eval_set = list(D.fixed_batches(crops, args.batch_size))
+
     for step in range(1, 1 + args.num_steps):
         t = time.time()
         x, spk = dataset.next()
         ws = model.train_step(x, spk)
         gs = model.global_step
-        if rank == 0 and (gs % args.interval == 0 or step == args.num_steps):
+        eval_now = eval_set is not None and gs % args.eval_interval == 0
+        if rank == 0 and (gs % args.interval == 0 or step == args.num_steps or eval_now):
             loss, rl, vq, commit = model.losses(ws)          # synchronises: only every `interval` steps
+            extra = {}
+            if eval_now:
+                extra['eval'] = pkg.scoring.score_batches(model, eval_set, dev, weights='ema').report(
+                    'sample', latent_dim=model.D if model.use_vq else 0)
             t = time.time() - t
             progress = '\r[step %d] %.2f' % (gs, step / args.num_steps * 100) + '%'
             msg = ' [recons %.5f] [vq %.5f] [lr %.5f]' % (rl, vq, model.lr_at(gs - 1))
+            if eval_now:
+                msg += ' [eval bits %.5f]' % extra['eval']['bits_per_sample']
             print(progress + msg + display_time(t, (args.num_steps - step) * t), end='', flush=True)
             # the reference writes its merged summaries to a TensorBoard event file here (train.py:104-109); without
             # TensorFlow the same tags go to <save_dir>/summaries.jsonl, one line per logged step
             with open(os.path.join(save_dir, 'summaries.jsonl'), 'a') as f:
-                f.write(json.dumps({'global_step': gs, 'learning_rate': model.lr_at(gs - 1), **model.summaries(ws)}) + '\n')
+                f.write(json.dumps({'global_step': gs, 'learning_rate': model.lr_at(gs - 1), **model.summaries(ws), **extra}) + '\n')
     if rank == 0:
         torch.cuda.synchronize()
         path = '%s-%d.pt' % (args.save_path, model.global_step)

@@ -190,3 +190,89 @@ class Aishell(WavDataset):     # dataset.py:136-144
 
     def __init__(self, batch_size, max_len, relative_path='data/', **kw):
         super().__init__(batch_size, max_len, relative_path, 'aishell_train.txt', 'aishell_speakers.txt', **kw)
+
+
+# ---------------------------------------------------------------------------- held-out lists (evaluate.py, train.py -eval_list)
+DATASETS = {'VCTK': VCTK, 'LibriSpeech': LibriSpeech, 'Aishell': Aishell}
+
+
+class HeldOutList:
+    """A list file in the format of the `<name>_train.txt` lists (one path per line, relative to the dataset's wav directory
+    under `relative_path`), read in FILE ORDER with no random crops; speaker ids come from the path and
+    `<relative_path>/<name>_speakers.txt`, as in WavDataset.  `ratio`: the encoder's samples per latent frame (64; 320 for
+    the '2019' encoder): whole utterances are trimmed to a multiple of it."""
+
+    def __init__(self, dataset, list_path, relative_path='data/', ratio=64, sr=16000):
+        if dataset not in DATASETS:
+            raise NotImplementedError('dataset %s has no file lists' % dataset)
+        cls = DATASETS[dataset]
+        self.reader = cls.__new__(cls)            # WavDataset._read / speaker_of, without its training list
+        self.reader.root, self.reader.sr = relative_path, sr
+        self.reader.data_dir = 'VCTK-Corpus/wav48/' if dataset == 'VCTK' else ''
+        with open(list_path) as f:
+            self.files = [ln.strip() for ln in f if ln.strip()]
+        speakers = {'VCTK': 'vctk_speakers.txt', 'LibriSpeech': 'librispeech_speakers.txt', 'Aishell': 'aishell_speakers.txt'}[dataset]
+        self.speaker_to_int = get_speaker_to_int(os.path.join(relative_path, speakers))
+        self.num_speakers = len(self.speaker_to_int)
+        self.ratio = ratio
+
+    def speaker(self, rel):
+        return self.speaker_to_int[self.reader.speaker_of(rel)]
+
+    def read(self, rel):
+        return self.reader._read(rel)
+
+    def utterances(self, files=None):
+        """[(file, speaker id, samples trimmed to a multiple of ratio)] in file order; files shorter than one frame are
+        left out (second result: how many)."""
+        out, skipped = [], 0
+        for rel in (self.files if files is None else files):
+            wav = self.read(rel)
+            n = len(wav) // self.ratio * self.ratio
+            if n == 0:
+                skipped += 1
+                continue
+            out.append((rel, self.speaker(rel), wav[:n]))
+        return out, skipped
+
+    def crops(self, length, limit=None, files=None):
+        """[(file, speaker id, the first `length` samples)] of the files that are long enough, in file order, at most
+        `limit` of them; the second result counts the files that were too short."""
+        out, skipped = [], 0
+        for rel in (self.files if files is None else files):
+            if limit is not None and len(out) >= limit:
+                break
+            wav = self.read(rel)
+            if len(wav) < length:
+                skipped += 1
+                continue
+            out.append((rel, self.speaker(rel), wav[:length]))
+        return out, skipped
+
+
+def padded_length(n, multiple=256):
+    """The batch length for a longest row of n samples: n rounded up to a multiple of `multiple` (the plane engine's tiles)."""
+    return -(-n // multiple) * multiple
+
+
+def padded_batches(utts, batch_size, multiple=256):
+    """Sort utterances [(file, speaker, samples)] by length (stable: file order among equals), cut them into batches of
+    batch_size and zero-pad each batch to its longest row rounded up to `multiple`.  Yields (files, x float32 [B][T],
+    speaker ids int64 [B], lengths [B]) as host tensors / lists."""
+    order = sorted(range(len(utts)), key=lambda i: len(utts[i][2]))
+    for i0 in range(0, len(order), batch_size):
+        rows = [utts[i] for i in order[i0:i0 + batch_size]]
+        lengths = [len(r[2]) for r in rows]
+        x = np.zeros((len(rows), padded_length(max(lengths), multiple)), dtype=np.float32)
+        for j, r in enumerate(rows):
+            x[j, :lengths[j]] = r[2]
+        yield [r[0] for r in rows], torch.from_numpy(x), torch.tensor([r[1] for r in rows], dtype=torch.int64), lengths
+
+
+def fixed_batches(utts, batch_size):
+    """Batches of equally long crops [(file, speaker, samples)] in list order, as padded_batches yields them (lengths None:
+    whole rows are scored)."""
+    for i0 in range(0, len(utts), batch_size):
+        rows = utts[i0:i0 + batch_size]
+        yield ([r[0] for r in rows], torch.from_numpy(np.stack([r[2] for r in rows])),
+               torch.tensor([r[1] for r in rows], dtype=torch.int64), None)

@@ -632,6 +632,53 @@ def softmax_xent_bwd(logits, labels, *, dlogits, grad_scale=1.0):
     L.check(L.lib().vqw_softmax_xent_bwd(L.ptr(logits), L.ptr(labels), L.ptr(dlogits), float(grad_scale), B, Q, T, L.stream()))
 
 
+def _need_i32(t, n, name):
+    if t is not None and (t.dtype != torch.int32 or t.numel() < n):
+        raise ValueError('%s must be int32 with at least %d elements' % (name, n))
+
+
+def softmax_score(logits, labels, *, t_begin=None, t_end=None, nll=None, entropy=None, row_sums=None, row_counts=None):
+    """vqw_softmax_score: scores of logits [B][Q][T] against labels int32 [B][T] over t_begin[b] <= t < t_end[b] (device
+    int32 [B]; None: the whole row).  nll / entropy: optional fp32 [B][T] outputs (0 where not scored).  Returns
+    (row_sums float64 [B][2] = sums of nll and entropy, row_counts int32 [B][2] = scored positions and hits)."""
+    B, Q, T = logits.shape
+    dev = logits.device
+    if row_sums is None:
+        row_sums = torch.empty(B, 2, dtype=torch.float64, device=dev)
+    if row_counts is None:
+        row_counts = torch.empty(B, 2, dtype=torch.int32, device=dev)
+    L.require_cuda(logits, labels, t_begin, t_end, nll, entropy, row_sums, row_counts)
+    if logits.dtype != torch.float32:
+        raise ValueError('logits must be float32 [B][Q][T]')
+    if labels.dtype != torch.int32 or labels.numel() != B * T:
+        raise ValueError('labels must be int32 [B][T]')
+    _need_i32(t_begin, B, 't_begin')
+    _need_i32(t_end, B, 't_end')
+    _need_i32(row_counts, 2 * B, 'row_counts')
+    if row_sums.dtype != torch.float64 or row_sums.numel() < 2 * B:
+        raise ValueError('row_sums must be float64 [B][2]')
+    for t, nm in ((nll, 'nll'), (entropy, 'entropy')):
+        if t is not None:
+            _need(t, B * T, nm)
+    scratch = torch.empty(4 * B * ((T + 63) // 64), device=dev)
+    L.check(L.lib().vqw_softmax_score(L.ptr(logits), L.ptr(labels), L.ptr(t_begin), L.ptr(t_end), L.ptr(nll), L.ptr(entropy),
+                                      L.ptr(row_sums), L.ptr(row_counts), L.ptr(scratch), scratch.numel(), B, Q, T, L.stream()))
+    return row_sums, row_counts
+
+
+def code_histogram(idx, counts, flag, *, f_end=None):
+    """vqw_code_histogram: counts[c] += occurrences of c in idx int64 [B][Tz] over frames f < f_end[b] (device int32 [B];
+    None: all).  flag (device int32) is set non-zero by an index outside [0, len(counts)), which is counted nowhere."""
+    B, Tz = idx.shape
+    L.require_cuda(idx, counts, flag, f_end)
+    if idx.dtype != torch.int64:
+        raise ValueError('idx must be int64 [B][Tz]')
+    _need_i32(counts, 1, 'counts')
+    _need_i32(flag, 1, 'flag')
+    _need_i32(f_end, B, 'f_end')
+    L.check(L.lib().vqw_code_histogram(L.ptr(idx), L.ptr(f_end), L.ptr(counts), L.ptr(flag), B, Tz, counts.numel(), L.stream()))
+
+
 def cond_proj_fwd(cond, w, out, *, B, Cc, Mall, Tz):
     """out[b][m][t] = sum_c w[c][m] cond[b][c][t]: every add_condition projection of the decoder in one launch (wavenet_ops.py:93-101)."""
     _need(cond, B * Cc * Tz, 'cond')

@@ -386,7 +386,8 @@ class VQVAE:
     def _workspace(self, B, T, train=True):
         """Buffers of one (B, T) problem, cached.  train=False: only what the encoder + VQ forward pass writes
         (model.encoding of generate.py:92) -- about 3 KB per audio sample instead of the 136 KB per sample of the
-        training workspace (saved decoder activations of 30 layers + backward buffers)."""
+        training workspace (saved decoder activations of 30 layers + backward buffers).  train='score': the forward-only
+        workspace of evaluate() (_score_workspace)."""
         key = (B, T, train)
         if key in self._ws:
             return self._ws[key]
@@ -400,9 +401,11 @@ class VQVAE:
         return ws
 
     def _build_workspace(self, B, T, train):
-        ws = self._front_workspace(B, T, train)
+        ws = self._front_workspace(B, T, train is True)
         if not train:
             return ws
+        if train == 'score':
+            return self._score_workspace(ws)
         dev, R, S, Q, L, T = self.dev, self.R, self.S, self.Q, self.L, ws['T']
         e = lambda *s: A.empty(*s, device=dev)  # noqa: E731
         ws['condenc'] = e(B, self.Mall, ws['Tz'])
@@ -450,6 +453,37 @@ class VQVAE:
         ws['dcond'] = e(B, self.Cc, ws['Tz'])
         ws['bskip'] = e(S)
         self._front_workspace_train(ws)
+        return ws
+
+    def _score_workspace(self, ws):
+        """The decoder's buffers for a pass with save=False on top of the encoder + VQ forward buffers (evaluate): no per-layer
+        fp32 activations (two ping-pong net buffers and one gated buffer, aliased into the lists _decode_layers indexes), ONE
+        input-plane buffer for all layers (the keep_xp = False path), the gated planes of all layers (the skip contraction
+        over K = L*R reads them), no tanh / sigmoid and no backward buffers."""
+        dev, R, S, Q, L, B, T = self.dev, self.R, self.S, self.Q, self.L, ws['B'], ws['T']
+        e = lambda *s: A.empty(*s, device=dev)  # noqa: E731
+        h = lambda n: A.empty(n, dtype=torch.float16, device=dev)  # noqa: E731
+        ws['condenc'] = e(B, self.Mall, ws['Tz'])
+        pong = [e(B, R, T), e(B, R, T)]
+        ws['net'] = [pong[l & 1] for l in range(L + 1)]
+        ws['skip'] = e(B, S, T)
+        ws['gated'] = [e(B, R, T)] * L
+        if self.gate_f16x3:
+            ws['xp'] = h(2 * B * R * T)
+            ws['wp_all'] = A.empty(L, 2 * self.ks * R * 2 * R, dtype=torch.float16, device=dev)
+            ws['wp'] = [ws['wp_all'][l] for l in range(L)]
+            ws['gp'] = h(2 * B * R * T * (L if self.skip_f16x3 else 1))
+            if self.skip_f16x3:
+                ws['wskip'] = h(2 * L * R * S)
+                ws['wres'] = A.empty(L, 2 * R * R, dtype=torch.float16, device=dev)
+                if (self.x3_guard or self.bf16) and self.gbwd_f16x3 and S % 256 == 0 and Q % 256 == 0:
+                    ws['hp'], ws['hp2'] = h(2 * B * S * T), h(2 * B * S * T)
+                    ws['wskip0'], ws['wpost1'], ws['wpost2'] = h(2 * R * S), h(2 * S * S), h(2 * S * Q)
+            ws['wop_all'] = A.empty(L, 2 * R * (S + R), dtype=torch.float16, device=dev)
+            ws['wop'] = [ws['wop_all'][l] for l in range(L)]
+        ws['h1'] = e(B, S, T)
+        ws['logits'] = e(B, Q, T)
+        ws['nll'], ws['entropy'] = e(B, T), e(B, T)
         return ws
 
     def _front_workspace(self, B, T, train):
@@ -823,6 +857,98 @@ class VQVAE:
             finally:
                 self._x3_active = True
         return ws
+
+    # ------------------------------------------------------------------ held-out scoring
+    def _length_unit(self):
+        """What a row's scored length must be a multiple of: the encoder's ratio (hook: the prior has no encoder)."""
+        return 320 if self.enc == '2019' else 64
+
+    def evaluate(self, x, spk, lengths=None, weights='ema', per_position=False):
+        """Score held-out rows: the decoder's teacher-forced pass over the padded batch x [B][T] (forward only, on the score
+        workspace), restricted per row to t < lengths[b] -- what oracle.ref_model.forward gives for the same padded input.
+        Returns a scoring.Score: per row nll_sum / entropy_sum (nats, float64), count, hits (the label is the lowest index
+        among the maxima of its logits, the generators' greedy decision); with use_vq the per-row sum of VQ distances over the
+        frames f < lengths[b] // ratio, their number, the batch's code counts [k] and the codes [B][Tz] themselves; with per_position the nll / entropy
+        [B][T] device tensors (0 where not scored).
+        lengths: None (whole rows) or B positive multiples of the encoder's ratio (64; 320 for '2019'), at most T; anything
+        else raises before a launch.  The decoder is causal: its padding never reaches a scored position.  The encoder is NOT
+        causal: the last latent frames of a row shorter than T do see the zero padding behind it (Encoder_64's strided convs
+        reach about 190 samples ahead), so such a row scores as that padded input does, not as the utterance alone would.
+        weights: 'ema' scores with the EMA shadows (what generate.py uses), 'live' with the live parameters.  The pass behaves
+        like forward_checked (range flag zeroed, read once, a flagged pass repeated on the fp32 engine).  Afterwards -- also
+        when the call raises -- the parameters, EMA shadows, optimiser state, step counter, BatchNorm statistics, the guard's
+        scales, max-abs collectors, range flag and the sticky void flag are bit-identical to what they were: an evaluation
+        between two training steps leaves the second step what it would have been.  Synchronises."""
+        from . import scoring
+        if weights not in ('ema', 'live'):
+            raise ValueError("evaluate: weights must be 'ema' or 'live' (got %r)" % (weights,))
+        if x.dim() != 2 or spk.numel() != x.shape[0]:
+            raise ValueError('evaluate: x [B][T] and B speaker ids expected (got %s, %d ids)' % (tuple(x.shape), spk.numel()))
+        B, T = x.shape
+        unit = self._length_unit()
+        lens = None
+        if lengths is not None:
+            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+            if len(lens) != B:
+                raise ValueError('evaluate: %d lengths for a batch of %d' % (len(lens), B))
+            bad = [v for v in lens if v <= 0 or v > T or v % unit]
+            if bad:
+                raise ValueError('evaluate: lengths must be positive multiples of %d and at most T = %d (got %s)' % (unit, T, bad[:5]))
+        self.finish_steps()
+        ws = self._workspace(B, T, 'score')
+        t_end = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=self.dev)
+        f_end = None if lens is None else torch.tensor([v // ws['ratio'] for v in lens], dtype=torch.int32, device=self.dev)
+        guard = [(t, t.clone()) for t in (self.x3_scale, self.x3_amax, self.x3_flag, self.x3_void)]
+        live = self.flat.clone() if weights == 'ema' else None
+        try:
+            if live is not None:
+                self.flat.copy_(self.ema)
+            self.x3_flag.zero_()
+            self._score_pass(x, spk, ws)
+            if self.x3_guard and (ws.get('x3_used') or ws.get('enc_x3')) and int(self.x3_flag.item()) != 0:
+                self._x3_active = False
+                try:
+                    self._score_pass(x, spk, ws)
+                finally:
+                    self._x3_active = True
+            sums, counts = K.softmax_score(ws['logits'], ws['labels'], t_end=t_end, nll=ws['nll'] if per_position else None,
+                                           entropy=ws['entropy'] if per_position else None)
+            out = scoring.Score(nll_sum=sums[:, 0].cpu(), entropy_sum=sums[:, 1].cpu(), count=counts[:, 0].cpu().long(),
+                                hits=counts[:, 1].cpu().long())
+            if per_position:
+                out.nll, out.entropy = ws['nll'].clone(), ws['entropy'].clone()
+            if self.use_vq:
+                self._score_codes(ws, f_end, out)
+            return out
+        finally:
+            if live is not None:
+                self.flat.copy_(live)
+            for t, saved in guard:
+                t.copy_(saved)
+            self._tt_done = set()          # (transposed kernels cached from the parameters: made again on next use)
+
+    def _score_pass(self, x, spk, ws):
+        if A.POISON:
+            A.repoison(ws['_poison'])
+        plan = self._decode_prologue(x, ws, save=False)
+        self._encode(x, spk, ws, save=False)
+        self._decode_layers(ws, plan)
+
+    def _score_codes(self, ws, f_end, out):
+        """Codebook statistics of a scored batch: code counts and per-row VQ distance sums over the valid frames."""
+        B, Tz = ws['B'], ws['Tz']
+        counts = torch.zeros(self.Kc, dtype=torch.int32, device=self.dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        K.code_histogram(ws['idx'], counts, flag, f_end=f_end)
+        mind = ws['mind'].double()
+        if f_end is not None:
+            mind = mind * (torch.arange(Tz, device=self.dev)[None, :] < f_end[:, None])
+        out.vq_sum = mind.sum(1).cpu()
+        out.frames = torch.full((B,), Tz, dtype=torch.int64) if f_end is None else f_end.cpu().long()
+        out.code_counts = counts.cpu().long()
+        out.codes = ws['idx'].clone()
+        if int(flag.item()) != 0:
+            raise RuntimeError('evaluate: a VQ index outside [0, %d)' % self.Kc)
 
     def losses(self, ws):
         """(loss, reconstruction, vq, commitment) as python floats (synchronises; hook)."""

@@ -160,6 +160,16 @@ class LatentPrior(VQVAE):
         self._check_codes(codes, spk)
         return super().train_step(codes, spk, on_forward)
 
+    def _length_unit(self):
+        return 1
+
+    def evaluate(self, codes, spk, lengths=None, weights='ema', per_position=False):
+        """Score held-out code rows (codes int32 [B][T], T % 64 == 0, row b restricted to t < lengths[b]): per row nll_sum,
+        entropy_sum (nats), count and hits of the next code, as VQVAE.evaluate (forward only, EMA or live weights, every piece
+        of training state left bit-identical).  No codebook statistics: the prior has no codebook."""
+        self._check_codes(codes, spk)
+        return super().evaluate(codes, spk, lengths=lengths, weights=weights, per_position=per_position)
+
     def speaker_condition(self, spk, Tz):
         """[B][Cc][Tz]: the speaker embedding tiled over Tz frames (the generator's condition)."""
         B = spk.numel()
