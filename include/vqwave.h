@@ -618,7 +618,10 @@ typedef struct vqw_f16x3_wgrad_desc {
     int32_t nsplit;         /* 0 = one round of blocks                                                      */
     int64_t dw_tap_stride;  /* 0 = Cp * lddw                                                                */
     /* optional sums of q over time, formed from the registers that hold q anyway (no extra pass over q):           */
-    float* q_total;         /* q_total[o] += sum_{b,t} q[b][o][t] for o in [total_o0, total_o1) (bias gradients)     */
+    float* q_total;         /* q_total[o] += sum_{b,t} q[b][o][t] for o in [total_o0, total_o1) (bias gradients).  The sums
+                             * (q_seg too) take q as it ARRIVES: fp32 q is summed before it is split or rounded to bf16 -- the
+                             * sums are fp32-accurate in either mode --, q given as planes is summed from the planes, with
+                             * VQW_X3_BF16 the sum of the bf16-rounded values                                          */
     float* q_seg;           /* q_seg[b*seg_bstride + o*seg_T + t/(T/seg_T)] += q[b][o][t]: the gradient of add_condition's
                              * projected condition (wavenet_ops.py:98-100); (T/seg_T) % 32 == 0; the caller zeroes it    */
     int64_t seg_bstride;

@@ -4,12 +4,18 @@ Tolerances: integer / index outputs are compared bit-exactly; fp32 MFMA results 
 torch-CPU fp32 oracle within 2e-4 of the tensor max (`close`; both sides accumulate K<=2304 fp32
 products in different orders); weight gradients (53 248-term sums) 5e-4, 1e-3 at the full size.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import ref_ops as R
 from oracle import ref_model as M
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import x3_ref as X  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -977,9 +983,28 @@ def test_wgrad_f16x3_batch_of_layers_in_one_launch(K):
             res[qp] = (dws, segs, tots)
         for i in range(len(dils)):
             assert torch.equal(res[True][0][i], res[False][0][i]), 'q from planes: dW of layer %d differs (bf16=%s)' % (i, bf)
+            if bf:
+                # One bf16 plane: the sums formed from the planes are sums of the ROUNDED q, the sums formed from fp32 q are taken
+                # before it is rounded (include/vqwave.h, q_total) -- each against its own float64 sum, in the bound form of
+                # test_wgrad_f16x3_matches_fp64 (per column 1e-5 sum |q|; 1e-5 * 32 max |q| per 32 steps of a segment).  The sums
+                # are of order 6e-4 and 8e-5: a tolerance of the old 3e-3 passed an all-zero output.
+                sq = float(scales[5 + i])
+                q_r = torch.from_numpy(X.bf16_round(X.scaled(dpres[i].cpu().numpy(), sq))).to(DEV) / sq
+                for qp, q64 in ((False, dpres[i].double()), (True, q_r)):
+                    tot_err = (res[qp][2][i].double() - q64.sum((0, 2))).abs()
+                    assert bool((tot_err <= 1e-5 * q64.abs().sum((0, 2))).all()), 'bias sums (q planes: %s), layer %d: %.3e' % (qp, i, float(tot_err.max()))
+                    seg_err = float((res[qp][1][i].double() - q64.view(B, 2 * R, Tz, T // Tz).sum(-1)).abs().max())
+                    assert seg_err <= 1e-5 * float(q64.abs().max()) * 32 * (T // Tz // 32), 'condition sums (q planes: %s), layer %d: %.3e' % (qp, i, seg_err)
+                d, sp = dils[i], float(scales[i])
+                for (j, c, o) in ((0, 3, 500), (1, 255, 0), (2, 100, 257)):       # dW against float64 of the rounded operands
+                    sh = (2 - j) * d
+                    p_r = X.bf16_round(X.scaled(nets[i][:, c, :T - sh].cpu().numpy(), sp)) / sp
+                    w64 = float((p_r * q_r[:, o, sh:].cpu().numpy()).sum())
+                    assert abs(res[True][0][i][j, c, o].item() - w64) <= 2e-6 * res[True][0][i].abs().max().item(), (i, j, c, o)
+                continue
             for qp in (False, True):
-                close(res[qp][2][i], dpres[i].sum((0, 2)), rtol=3e-3 if bf else 1e-4, atol=3e-3 if bf else 1e-6, what='bias sums (q planes: %s), layer %d' % (qp, i))
-            close(res[True][1][i], dpres[i].view(B, 2 * R, Tz, T // Tz).sum(-1), rtol=3e-3 if bf else 1e-4, atol=3e-3 if bf else 1e-4,
+                close(res[qp][2][i], dpres[i].sum((0, 2)), rtol=1e-4, atol=1e-6, what='bias sums (q planes: %s), layer %d' % (qp, i))
+            close(res[True][1][i], dpres[i].view(B, 2 * R, Tz, T // Tz).sum(-1), rtol=1e-4, atol=1e-4,
                   what='condition sums from planes, layer %d' % i)
     # odd dilations (unaligned windows of p) with q from planes
     dwa, dwb = torch.zeros(3, R, 2 * R, device=DEV), torch.zeros(3, R, 2 * R, device=DEV)

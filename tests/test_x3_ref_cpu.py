@@ -1,5 +1,6 @@
-"""Pins tests/x3_ref.py, the CPU statement of the fp16x3 number format that test_x3_range_gpu.py holds the kernels to: if
-one of these fails, a GPU failure of that module says nothing about the kernels.  No GPU, numpy only."""
+"""Pins tests/x3_ref.py, the CPU statement of the fp16x3 number format that test_x3_range_gpu.py holds the kernels to (and of
+the bf16 engine's one-plane format, test_bf16_kernels_gpu.py): if one of these fails, a GPU failure of those modules says nothing
+about the kernels.  No GPU, numpy only (torch.bfloat16 once, as a witness)."""
 import math
 import os
 import sys
@@ -193,3 +194,81 @@ def test_update_scales_every_exponent_and_target():
     assert s.tolist() == [5.0, 1.0, 7.0, 7.0, 8192.0] and flag == 1
     assert X.amax_bits(np.float32([[0.5, -3.0], [2.0, -0.0]])) == 0x40400000
     assert math.ldexp(1.0, 13) * 1.0 == 8192.0
+
+
+# ----------------------------------------------------------------------------- the bf16 engine's reference
+def test_bf16_round_is_the_value_of_bf16_bits():
+    """bf16_round against bf16_bits bit for bit, planted ties (to even, both ways), negative values, values that round up
+    across a power of two, and torch.bfloat16 as a witness that shares no code with either."""
+    import torch
+    rng = np.random.RandomState(5)
+    one = np.float32(1.0)
+    planted = np.float32([1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, -(1.0 + 2.0 ** -8), -(1.0 + 3 * 2.0 ** -8),       # ties: down to even, up to even
+                          2.0 - 2.0 ** -8, -(2.0 - 2.0 ** -8), 2.0 - 2.0 ** -9, np.nextafter(np.float32(2.0), one),  # up across a power of two
+                          1.0 + 2.0 ** -8 + 2.0 ** -23, 1.0 + 2.0 ** -8 - 2.0 ** -16, 0.0, -0.0, 2.0 ** -126, -2.5, 3.0e38, 2.0 ** -130])
+    want = np.float64([1.0, 1.0 + 2.0 ** -6, -1.0, -(1.0 + 2.0 ** -6), 2.0, -2.0, 2.0, 2.0,
+                       1.0 + 2.0 ** -7, 1.0, 0.0, -0.0, 2.0 ** -126, -2.5, 0, 2.0 ** -130])
+    got = X.bf16_round(planted)
+    keep = np.arange(len(planted)) != 14
+    assert np.array_equal(got[keep], want[keep]) and np.array_equal(np.signbit(got), np.signbit(planted))
+    x = np.concatenate([spread(rng, 300000, -60, 60), planted])
+    r = X.bf16_round(x)
+    assert r.dtype == np.float64 and r.shape == x.shape
+    r32 = r.astype(np.float32)
+    assert np.array_equal(r32.astype(np.float64), r), 'a bf16 value that is no float32'
+    assert np.array_equal(r32.view(np.uint32), X.bf16_bits(x).astype(np.uint32) << 16)
+    assert (np.abs(r - x.astype(np.float64)) <= 2.0 ** -8 * np.abs(x.astype(np.float64))).all()      # half an ulp (2^-7) of 8 significand bits
+    assert np.array_equal(X.bf16_round(r32), r), 'rounding is not idempotent'
+    witness = torch.from_numpy(x).to(torch.bfloat16).to(torch.float64).numpy()
+    assert np.array_equal(witness, r)
+    assert X.bf16_round(x.reshape(4, -1)).shape == (4, x.size // 4)
+    # truncation (the wrong conversion the GPU tests must catch) differs from it exactly where the dropped bits are more than half
+    t = X.bf16_truncate(x)
+    assert (np.abs(t) <= np.abs(x.astype(np.float64))).all() and 0.4 < (t != r).mean() < 0.6
+    # exact operands give the exact product at any scale, and rounding happens AFTER the scale
+    e = np.float32([[1.0, 2.0, -0.5, 3.0]])
+    assert X.contract_bf16(e, e.T, 2.0 ** 10, 2.0 ** -4).tolist() == [[14.25]]
+    a = np.float32([[1.0 + 2.0 ** -8 + 2.0 ** -20]])
+    assert X.contract_bf16(a, np.float32([[3.0]])).tolist() == [[3.0 * (1.0 + 2.0 ** -7)]]
+
+
+def _wrong_variants():
+    return (('operands truncated, not rounded to nearest even', dict(rnd=X.bf16_truncate)),
+            ('tap 0 not zeroed before the start of the batch row', dict(leak_tap=0)),
+            ('operands left unrounded', dict(rnd=X.unrounded)))
+
+
+def test_gate_bar_tells_a_wrong_bf16_kernel_from_a_right_one():
+    """The gate conv's bar in test_bf16_kernels_gpu.py (2e-5 absolute on tanh * sigmoid, tanh and sigmoid) at its case
+    (B=2, T=512, R=128, ks=3, d=7): every deliberately wrong evaluation lies at least 10 bars from the reference in the output
+    the GPU test compares, so a kernel inside the bar made none of these mistakes."""
+    B, T, R, ks, d = 2, 512, 128, 3, 7
+    bar = 2e-5
+    x, w, bias, cond = X.gate_case(B, T, R, ks, d)
+    taps = [-(ks - 1 - j) * d for j in range(ks)]
+    want = X.gate_outputs(X.conv_bf16(x, w, taps, 1.0, 256.0), bias, cond, T)
+    for what, kw in _wrong_variants():
+        got = X.gate_outputs(X.conv_bf16(x, w, taps, 1.0, 256.0, **kw), bias, cond, T)
+        dist = [float(np.abs(g_ - w_).max()) for g_, w_ in zip(got, want)]
+        print('%-52s gated %.2e tanh %.2e sigmoid %.2e (bar %.0e)' % (what, dist[0], dist[1], dist[2], bar))
+        assert min(dist) >= 10 * bar, (what, dist)
+    # the leaked tap is wrong ONLY in the first 2 d steps of the rows behind the first: a test that samples must sample there
+    got = X.gate_outputs(X.conv_bf16(x, w, taps, 1.0, 256.0, leak_tap=0), bias, cond, T)[0]
+    assert np.array_equal(got[0], want[0][0]) and np.array_equal(got[1][:, 2 * d:], want[0][1][:, 2 * d:])
+
+
+def test_wgrad_bar_tells_a_wrong_bf16_kernel_from_a_right_one():
+    """The weight gradient's bar (2e-6 of the largest update + 1e-6 of the largest dw accumulated into) at its case
+    (B=2, T=512, d=1, Cp=256, Q=512+256): each wrong evaluation is at least 10 bars away."""
+    B, T, d, Q1 = 2, 512, 1, 256
+    p, q0, q1, dw0, sc = X.wgrad_case(B, T, d, Q1, False)
+    q = np.concatenate([q0, q1], 1)
+    taps = [-2 * d, -d, 0]
+    want = X.wgrad_bf16(p, q, taps)
+    bar = 2e-6 * float(np.abs(want).max()) + 1e-6 * float(np.abs(dw0).max())
+    for what, kw in _wrong_variants():
+        dist = float(np.abs(X.wgrad_bf16(p, q, taps, **kw) - want).max())
+        print('%-52s %.2e (bar %.2e)' % (what, dist, bar))
+        assert dist >= 10 * bar, (what, dist, bar)
+    leak = X.wgrad_bf16(p, q, taps, leak_tap=0)
+    assert np.array_equal(leak[1:], want[1:]) and not np.array_equal(leak[0], want[0])

@@ -2,7 +2,8 @@
 test_x3_ref_cpu.py and test_x3_range_gpu.py.  numpy only; everything that computes does so in float64, everything that
 describes device memory returns the exact uint16 image.  Written from the header's sentences, not from the kernels' index
 arithmetic: an operand x is held as two fp16 planes h1 = fp16(s x), h2 = fp16(s x - h1) of ONE power-of-two scale s per
-tensor, planes are [plane][chunk of 8 channels][row][8], and a product is a1 b1 + a1 b2 + a2 b1 over s_a s_b."""
+tensor, planes are [plane][chunk of 8 channels][row][8], and a product is a1 b1 + a1 b2 + a2 b1 over s_a s_b.  VQW_X3_BF16: ONE
+plane bf16(s x), rounded to nearest even, and one product a b (exact in fp32) -- bf16_round, contract_bf16, conv_bf16, wgrad_bf16."""
 import math
 
 import numpy as np
@@ -36,6 +37,11 @@ def bf16_bits(x32):
     """uint16 image of bf16(x), round to nearest even (finite x)."""
     u = np.ascontiguousarray(x32, np.float32).view(np.uint32).astype(np.uint64)
     return ((u + 0x7fff + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+
+
+def bf16_round(x32):
+    """float64 value of bf16(x): the 16 bits of bf16_bits(x) are the upper half of a float32."""
+    return (bf16_bits(x32).astype(np.uint32) << 16).view(np.float32).astype(np.float64).reshape(np.shape(x32))
 
 
 def plane_bits(x32, bf16=False):
@@ -121,6 +127,88 @@ def contract(a, b, sa=1.0, sb=1.0, flush=False):
     a1, a2 = (h.astype(np.float64) for h in split(scaled(a, sa), flush))
     b1, b2 = (h.astype(np.float64) for h in split(scaled(b, sb), flush))
     return (a1 @ b1 + a1 @ b2 + a2 @ b1) / (float(np.float32(sa)) * float(np.float32(sb)))
+
+
+def contract_bf16(a, b, sa=1.0, sb=1.0):
+    """The bf16 engine's product of a [M][K] and b [K][N] (fp32): both operands scaled as in the fp16 path, each rounded to its
+    ONE bf16 plane, multiplied in float64 (a bf16 x bf16 product is exact in fp32, so only the summation is left to the device),
+    divided by sa * sb."""
+    return (bf16_round(scaled(a, sa)) @ bf16_round(scaled(b, sb))) / (float(np.float32(sa)) * float(np.float32(sb)))
+
+
+def bf16_truncate(x32):
+    """float64 value of x with the lower 16 bits of its float32 image dropped: what a conversion that forgets to round gives."""
+    u = np.ascontiguousarray(x32, np.float32).view(np.uint32) & np.uint32(0xffff0000)
+    return u.view(np.float32).astype(np.float64).reshape(np.shape(x32))
+
+
+def unrounded(x32):
+    """float64 value of x itself: an operand that never went through bf16."""
+    return np.asarray(x32, np.float32).astype(np.float64)
+
+
+def shifted(x, sh, leak=False):
+    """x [B][C][T] read at t + sh (sh <= 0, -sh < T), zero before the start of the batch row.  leak: the check is missing -- the
+    flat (batch, time) rows before the batch row are read instead (the previous batch row's end; nothing lies before batch 0)."""
+    B, C, T = x.shape
+    if sh == 0:
+        return x.copy()
+    assert -T < sh < 0
+    out = np.zeros_like(x)
+    out[:, :, -sh:] = x[:, :, :T + sh]
+    if leak:
+        out[1:, :, :-sh] = x[:-1, :, T + sh:]
+    return out
+
+
+def conv_bf16(x, w, taps, sx=1.0, sw=1.0, rnd=bf16_round, leak_tap=None):
+    """Causal dilated conv on the bf16 engine, float64 sums: out[b][m][t] = sum_j sum_c rnd(sx x)[b][c][t + taps[j]] rnd(sw w)[j][c][m]
+    / (sx sw); x [B][C][T], w [taps][C][M].  rnd / leak_tap build the deliberately wrong evaluations of test_x3_ref_cpu.py."""
+    xr, wr = rnd(scaled(x, sx)), rnd(scaled(w, sw))
+    out = 0.0
+    for j, sh in enumerate(taps):
+        out = out + np.einsum('bct,cm->bmt', shifted(xr, sh, leak=(j == leak_tap)), wr[j], optimize=True)
+    return out / (float(np.float32(sx)) * float(np.float32(sw)))
+
+
+def wgrad_bf16(p, q, taps, sp=1.0, sq=1.0, rnd=bf16_round, leak_tap=None):
+    """Weight gradient on the bf16 engine, float64 sums: dw[j][c][o] = sum_{b,t} rnd(sp p)[b][c][t + taps[j]] rnd(sq q)[b][o][t] / (sp sq)."""
+    pr, qr = rnd(scaled(p, sp)), rnd(scaled(q, sq))
+    dw = np.stack([np.einsum('bct,bot->co', shifted(pr, sh, leak=(j == leak_tap)), qr, optimize=True) for j, sh in enumerate(taps)])
+    return dw / (float(np.float32(sp)) * float(np.float32(sq)))
+
+
+def gate_case(B, T, R, ks, d):
+    """Inputs of the bf16 gate-conv tests (test_bf16_kernels_gpu.py, and the discrimination tests of test_x3_ref_cpu.py):
+    x [B][R][T], w [ks][R][2R], bias [2R], cond [B][2R][cond_T] with cond_T = T / 64 (T / 32 where 64 does not divide T)."""
+    rng = np.random.RandomState(1000 + d + T)
+    cond_T = T // 64 if T % 64 == 0 else T // 32
+    x = rng.standard_normal((B, R, T)).astype(np.float32)
+    w = (rng.standard_normal((ks, R, 2 * R)) * 0.05).astype(np.float32)
+    bias = (rng.standard_normal(2 * R) * 0.3).astype(np.float32)
+    cond = (rng.standard_normal((B, 2 * R, cond_T)) * 0.3).astype(np.float32)
+    return x, w, bias, cond
+
+
+def gate_outputs(pre, bias, cond, T):
+    """(tanh(f) * sigmoid(g), tanh(f), sigmoid(g)) of the float64 pre-activation [B][2R][T] + bias + the condition held for
+    T / cond_T steps per frame; filter rows first, then the gate rows."""
+    R = pre.shape[1] // 2
+    pre = pre + bias.astype(np.float64)[None, :, None] + np.repeat(cond.astype(np.float64), T // cond.shape[2], axis=2)
+    th, sg = np.tanh(pre[:, :R]), 1.0 / (1.0 + np.exp(-pre[:, R:]))
+    return th * sg, th, sg
+
+
+def wgrad_case(B, T, d, Q1, scaled_, Cp=256, Q0=512, ks=3):
+    """Inputs of the bf16 weight-gradient tests: p [B][Cp][T], q = [q0; q1] [B][Q0 + Q1][T], the dw [ks][Cp][Q0 + Q1] accumulated
+    into, the power-of-two guard scales (p, q0, q1); scaled_: gradients of 1e-6 lifted by 2^30 / 2^28."""
+    rng = np.random.RandomState(100 + d)
+    p = rng.standard_normal((B, Cp, T)).astype(np.float32)
+    q0 = (rng.standard_normal((B, Q0, T)) * (1e-6 if scaled_ else 1.0)).astype(np.float32)
+    q1 = (rng.standard_normal((B, Q1, T)) * (3e-6 if scaled_ else 1.0)).astype(np.float32)
+    dw0 = rng.standard_normal((ks, Cp, Q0 + Q1)).astype(np.float32)
+    sc = np.float32([4.0, 2.0 ** 30, 2.0 ** 28] if scaled_ else [1.0, 1.0, 1.0])
+    return p, q0, q1, dw0, sc
 
 
 def row_rel_l2(got, want, axis=-1):

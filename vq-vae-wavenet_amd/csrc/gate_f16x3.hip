@@ -388,7 +388,9 @@ __device__ __forceinline__ void f16x3_mainloop(f32x16 (&acc)[MR][2], char* smem,
     const int l31 = lane & 31, lhi = lane >> 5;
     const int KCA = (TAB ? g.wks : g.ks) * g.Cin / 8, KCB = g.Cin / 8, spt = g.Cin / 16;   // spt: K steps per tap
     const int nsteps = TAB ? g.sn : g.ks * spt;
-    const __amdgpu_buffer_rsrc_t ra = vqw_make_rsrc(g.wp, (unsigned)((size_t)2 * KCA * g.M * 16));
+    // (NP planes: the requests past the last K step must fall outside the resource -- and read as zero -- in bf16 mode too, where the
+    // weight planes end after ONE plane)
+    const __amdgpu_buffer_rsrc_t ra = vqw_make_rsrc(g.wp, (unsigned)((size_t)NP * KCA * g.M * 16));
     // One buffer resource per activation plane, based at the contraction's first chunk: 32-bit offsets then only span the
     // chunks this contraction reads (checked by the callers: Cin / 8 * NB * 16 < 2 GiB), not the planes tensor -- the gated planes
     // of all layers side by side are 3.3 GB at batch 16 and neither their size nor the distance between the two planes may

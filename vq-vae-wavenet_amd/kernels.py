@@ -221,6 +221,11 @@ def _need_planes(t, n_halves, what):
 X3_BF16, X3_HALF_BLOCKS, X3_S2D = 1, 2, 4      # VQW_X3_* mode bits of include/vqwave.h
 
 
+def _npl(mode):
+    """Planes per operand: two fp16 pieces, or the one bf16 plane (a bf16 buffer is half the size)."""
+    return 1 if mode & X3_BF16 else 2
+
+
 def x3_mode(mode=None, bf16=False):
     """mode bits of the vqw_f16x3_* calls; None: fp16x3 (or bf16) with the block height chosen by VQW_X3_HALF (default: see
     model.py / DESIGN 3.3)."""
@@ -268,7 +273,7 @@ def f16x3_split_activations(x, planes, B, Cc, T, scale=1.0, kc0=0, KC=0, scale_d
     """scale * scale_dev * x [B][C][T] fp32 -> planes [2][KC or C/8][B*T][8] fp16, chunks kc0..."""
     mode = x3_mode(mode)
     _need(x, B * Cc * T, 'x')
-    _need_planes(planes, 2 * B * T * (KC * 8 if KC else Cc), 'planes')
+    _need_planes(planes, _npl(mode) * B * T * (KC * 8 if KC else Cc), 'planes')
     L.check(L.lib().vqw_f16x3_split_activations(L.ptr(x), L.ptr(planes), B, Cc, T, float(scale), kc0, KC, _slot(scale_dev, 'scale_dev'),
                                                 _slot(amax, 'amax', torch.int32), _slot(flag, 'flag', torch.int32), mode, L.stream()))
 
@@ -277,7 +282,7 @@ def f16x3_pack_gate_weights(w, planes, ks, R, ldw, scale, count=1, scale_dev=Non
     """`count` layers back to back in `w` ([count][ks][R][ldw]) and in `planes`."""
     mode = x3_mode(mode)
     _need(w, (count - 1) * ks * R * ldw + (ks * R - 1) * ldw + 2 * R, 'w')
-    _need_planes(planes, count * 2 * ks * R * 2 * R, 'planes')
+    _need_planes(planes, count * _npl(mode) * ks * R * 2 * R, 'planes')
     L.check(L.lib().vqw_f16x3_pack_gate_weights(L.ptr(w), L.ptr(planes), ks, R, ldw, float(scale), count, _slot(scale_dev, 'scale_dev'), mode, L.stream()))
 
 
@@ -285,7 +290,7 @@ def f16x3_pack_weights(w, planes, Kd, M, ldw, scale, count=1, scale_dev=None, mo
     """w [count][K][ldw] fp32 -> planes [count][2][K/8][M][8] fp16 of scale * scale_dev * w."""
     mode = x3_mode(mode)
     _need(w, (count - 1) * Kd * ldw + (Kd - 1) * ldw + M, 'w')
-    _need_planes(planes, count * 2 * Kd * M, 'planes')
+    _need_planes(planes, count * _npl(mode) * Kd * M, 'planes')
     L.check(L.lib().vqw_f16x3_pack_weights(L.ptr(w), L.ptr(planes), Kd, M, ldw, float(scale), count, _slot(scale_dev, 'scale_dev'), mode, L.stream()))
 
 
@@ -295,7 +300,7 @@ def f16x3_pack_weights_t(w, planes, Kd, M, k_inner, ld_src, blk_stride, scale, c
     mode = x3_mode(mode)
     nblk = Kd // k_inner
     _need(w, (count - 1) * nblk * blk_stride + (nblk - 1) * blk_stride + (M - 1) * ld_src + k_inner, 'w')
-    _need_planes(planes, count * 2 * Kd * M, 'planes')
+    _need_planes(planes, count * _npl(mode) * Kd * M, 'planes')
     L.check(L.lib().vqw_f16x3_pack_weights_t(L.ptr(w), L.ptr(planes), Kd, M, k_inner, ld_src, blk_stride, float(scale), count,
                                              _slot(scale_dev, 'scale_dev'), mode, L.stream()))
 
@@ -310,8 +315,8 @@ def f16x3_out_conv(*, xp, wp, B, T, R, S, w_scale_inv, skip=None, net_in=None, n
     mode = x3_mode(mode)
     cin = Cin if Cin > 0 else R
     kc_all = xp_KC if xp_KC > 0 else cin // 8
-    _need_planes(xp, 2 * kc_all * 8 * B * T, 'xp')
-    _need_planes(wp, 2 * ks * cin * (S + R), 'wp')
+    _need_planes(xp, _npl(mode) * kc_all * 8 * B * T, 'xp')
+    _need_planes(wp, _npl(mode) * ks * cin * (S + R), 'wp')
     if S:
         _need(skip, B * S * T, 'skip')
     if R:
@@ -321,7 +326,7 @@ def f16x3_out_conv(*, xp, wp, B, T, R, S, w_scale_inv, skip=None, net_in=None, n
             _need(net_out, B * R * T * (2 if epi == 1 else 1), 'net_out')
     if epi == 1:
         if aux0_planes is not None:      # the gated planes of the forward pass instead of fp32 tanh / gated
-            _need_planes(aux0_planes, (1 if mode & X3_BF16 else 2) * (aux0_KC or R // 8) * 8 * B * T, 'aux0_planes')
+            _need_planes(aux0_planes, _npl(mode) * (aux0_KC or R // 8) * 8 * B * T, 'aux0_planes')
         else:
             _need(aux0, B * R * T, 'aux0')
         _need(aux1, B * R * T, 'aux1')
@@ -330,7 +335,7 @@ def f16x3_out_conv(*, xp, wp, B, T, R, S, w_scale_inv, skip=None, net_in=None, n
     if bias is not None:
         _need(bias, S + R, 'bias')
     if net_out_planes is not None:
-        _need_planes(net_out_planes, 2 * B * T * (planes_KC * 8 if planes_KC else R * (2 if epi == 1 else 1)), 'net_out_planes')
+        _need_planes(net_out_planes, _npl(mode) * B * T * (planes_KC * 8 if planes_KC else R * (2 if epi == 1 else 1)), 'net_out_planes')
     d = L.F16x3OutDesc()
     d.xp, d.wp = xp.data_ptr(), wp.data_ptr()
     d.bias = None if bias is None else bias.data_ptr()
@@ -397,8 +402,8 @@ def f16x3_gate_conv(*, xp, wp, out0, B, T, R, ks, dilation, w_scale_inv, bias=No
     """vqw_f16x3_gate_conv: dilated causal conv over the layer input planes + bias + upsampled condition, tanh(filter) * sigmoid(gate)
     -> out0 (and as planes), tanh / sigmoid saved for the backward pass when save0 / save1 are given."""
     mode = x3_mode(mode)
-    _need_planes(xp, 2 * B * R * T, 'xp')
-    _need_planes(wp, 2 * ks * R * 2 * R, 'wp')
+    _need_planes(xp, _npl(mode) * B * R * T, 'xp')
+    _need_planes(wp, _npl(mode) * ks * R * 2 * R, 'wp')
     if out0 is not None or out_planes is None or save1 is None:       # (out0 may be left out where every reader takes the planes)
         _need(out0, B * R * T, 'out0')
     for t, nm in ((save0, 'save0'), (save1, 'save1')):
@@ -418,7 +423,7 @@ def f16x3_gate_conv(*, xp, wp, out0, B, T, R, ks, dilation, w_scale_inv, bias=No
     d.save0 = None if save0 is None else save0.data_ptr()
     d.save1 = None if save1 is None else save1.data_ptr()
     if out_planes is not None:
-        _need_planes(out_planes, 2 * B * T * (out_planes_KC * 8 if out_planes_KC else R), 'out_planes')
+        _need_planes(out_planes, _npl(mode) * B * T * (out_planes_KC * 8 if out_planes_KC else R), 'out_planes')
     d.out_planes = None if out_planes is None else out_planes.data_ptr()
     d.out_planes_kc0, d.out_planes_KC = out_planes_kc0, out_planes_KC
     d.cond_bstride = cond_bstride
@@ -439,14 +444,14 @@ def _wgrad_desc(d, *, dw, slab, B, T, Cp, Q0, taps, p=None, q0=None, q1=None, Q1
     lddw = (Q0 + Q1) if lddw is None else lddw
     dw_tap_stride = Cp * lddw if dw_tap_stride is None else dw_tap_stride
     if p_planes is not None:
-        _need_planes(p_planes, (1 if mode & X3_BF16 else 2) * (p_planes_KC or Cp // 8) * 8 * B * T, 'p_planes')
+        _need_planes(p_planes, _npl(mode) * (p_planes_KC or Cp // 8) * 8 * B * T, 'p_planes')
         d.p_planes, d.p_planes_KC, d.p_planes_kc0, d.p_planes_scale = p_planes.data_ptr(), p_planes_KC, p_planes_kc0, float(p_planes_scale)
         for j, kc in enumerate(p_tap_chunk or ()):       # (space-to-depth planes of a stride-2 conv's input: the tap's parity block)
             d.p_tap_chunk[j] = int(kc)
     else:
         _need(p, B * Cp * T_p, 'p')
     if q_planes is not None:
-        _need_planes(q_planes, (1 if mode & X3_BF16 else 2) * (q_planes_KC or Q0 // 8) * 8 * B * T, 'q_planes')
+        _need_planes(q_planes, _npl(mode) * (q_planes_KC or Q0 // 8) * 8 * B * T, 'q_planes')
         d.q_planes, d.q_planes_KC, d.q_planes_kc0, d.q_planes_scale = q_planes.data_ptr(), q_planes_KC, q_planes_kc0, float(q_planes_scale)
     else:
         _need(q0, B * Q0 * T, 'q0')
