@@ -299,6 +299,38 @@ int vqw_adam_ema_step(float* param, const float* grad, float* m, float* v, float
 int vqw_adam_ema_step_guarded(float* param, const float* grad, float* m, float* v, float* ema,
                               size_t n, float lr_t, float beta1, float beta2, float eps,
                               float decay, float grad_scale, const int32_t* skip, vqw_stream_t s);
+/* ... and with a device-side gradient scale: the step runs on (grad * grad_scale) * *scale, multiplied in that order, where
+ * scale is a device float read when the kernel RUNS (out[1] of vqw_grad_norm_segmented: clipping by global norm with no host
+ * read).  scale NULL = vqw_adam_ema_step_guarded, the same arithmetic as before this entry existed; skip as there.          */
+int vqw_adam_ema_step_scaled(float* param, const float* grad, float* m, float* v, float* ema,
+                             size_t n, float lr_t, float beta1, float beta2, float eps,
+                             float decay, float grad_scale, const int32_t* skip, const float* scale, vqw_stream_t s);
+
+/* ------------------------------------------------------------------------------------
+ * Global and per-segment L2 norms of a flat fp32 buffer and the scale of tf.clip_by_global_norm, left on the device.
+ *   g[i]        = buf[i] * grad_scale                (fp32, as the optimiser forms it; 1/world under data parallel)
+ *   seg_norm[k] = sqrt(sum of g[i]^2 over the chunks of segment k)
+ *   norm        = sqrt(sum over k, ascending, of segment k's sum of squares)
+ *   scale       = 1 if norm <= clip else clip / norm (norm rounded to fp32 first; a buffer under the threshold passes bit for
+ *                 bit).  clip = +inf: measure only, scale is exactly 1.  A non-finite norm is not treated specially: a NaN
+ *                 norm gives a NaN scale.
+ *   out         = [norm, scale, seg_norm[0 .. n_seg)]   (n_seg + 2 floats)
+ * chunks: the static chunk table on the device, n_chunks entries.  Chunk c covers buf[start, start + length) and belongs to
+ * segment seg in [0, n_seg); the chunks of one segment are consecutive in the table, every segment has at least one, and no
+ * element is in two chunks (kernels.grad_norm_plan builds it; a segment need not be contiguous in the buffer).  start needs no
+ * alignment: 16-byte loads run on the aligned interior of a chunk, scalar loads on its head and tail.
+ * partial: n_chunks doubles of scratch.  Two launches: one workgroup per chunk squares and accumulates in fp64 (an fp32 square
+ * is 0 below 1e-19 and inf above 1.8e19) in a fixed order and writes partial[c]; one workgroup then sums each segment's partials
+ * in ascending chunk order with a fixed tree, and the segments in ascending order.  No floating-point atomics: the output is
+ * bitwise reproducible, a segment's norm does not depend on the other segments, and every result is within 2^-22 relative of
+ * the exact value (sqrt and the cast to fp32 round once each).  n_seg <= 2048; clip > 0 (NaN is refused).              */
+typedef struct vqw_norm_chunk {
+    int64_t start;      /* first element */
+    int32_t length;     /* elements (> 0) */
+    int32_t seg;        /* segment id */
+} vqw_norm_chunk;
+int vqw_grad_norm_segmented(const float* buf, const vqw_norm_chunk* chunks, int n_chunks, int n_seg, double* partial,
+                            float grad_scale, float clip, float* out, vqw_stream_t s);
 
 /* ------------------------------------------------------------------------------------
  * Fast autoregressive generation -- wavenet.py:103-172, wavenet_ops.py:147-267,

@@ -13,6 +13,10 @@ weights (VQVAE.evaluate, forward only: the first `-length` samples of the first 
 enough, so the curve is comparable from step to step), adds `[eval bits ...]` to the console line and an `eval` object to
 that step's line of summaries.jsonl.  The list is in the format of the `<name>_train.txt` lists, read under `-data_root` as
 `-eval_dataset` (default: `-dataset`; VCTK when that is synthetic).
+
+`-clip_norm C`: gradients are clipped to the global norm C (tf.clip_by_global_norm; norm and scale stay on the device).
+`-grad_norm`: the norms are measured and logged, nothing is clipped.  Either adds `[gnorm ...]` to the console line and
+`grad_norm`, `grad_clip_scale` and a per-variable `grad_norms` object to summaries.jsonl, on logged steps.
 """
 import importlib
 import json
@@ -54,7 +58,11 @@ def main():
     parser.add_argument('-eval_batches', default=4, type=int, dest='eval_batches', metavar='int', help='held-out batches per evaluation')
     parser.add_argument('-eval_dataset', default=None, dest='eval_dataset', metavar='DATASET', help='dataset the list belongs to (default: -dataset)')
     parser.add_argument('-data_root', default='data/', dest='data_root', metavar='string', help='where the held-out wavs and *_speakers.txt are')
+    parser.add_argument('-clip_norm', default=None, type=float, dest='clip_norm', metavar='float', help='clip gradients to this global norm (> 0)')
+    parser.add_argument('-grad_norm', action='store_true', dest='grad_norm', help='log gradient norms without clipping')
     args = parser.parse_args()
+    if args.clip_norm is not None and not args.clip_norm > 0:
+        parser.error('-clip_norm must be > 0 (got %r)' % args.clip_norm)
     if args.eval_interval < 0 or args.eval_batches < 1:
         parser.error('-eval_interval must be >= 0 and -eval_batches >= 1')
     if args.eval_interval > 0 and args.eval_list is None:
@@ -107,6 +115,7 @@ def main():
     if world > 1:
         model.grad_sync = pkg.parallel.GradAllReduce(model.grad)
     model.defer_guard = os.environ.get('VQW_DEFER_GUARD', '1') != '0'     # the engine's range flag is read one step late (no host sync per step)
+    model.clip_norm = args.clip_norm if args.clip_norm is not None else (float('inf') if args.grad_norm else None)
     gs, lr = model.global_step, model.lr_at(model.global_step)
     if rank == 0:
         print('[restore] last global step: %d, learning rate: %.5f' % (gs, lr))
@@ -142,6 +151,10 @@ def main():
             t = time.time() - t
             progress = '\r[step %d] %.2f' % (gs, step / args.num_steps * 100) + '%'
             msg = ' [recons %.5f] [vq %.5f] [lr %.5f]' % (rl, vq, model.lr_at(gs - 1))
+            if model.clip_norm is not None:       # measured on the device by the step itself; read here, on logged steps only
+                gn = model.grad_norms()
+                extra.update(grad_norm=gn['global'], grad_clip_scale=gn['scale'], grad_norms=gn['segments'])
+                msg += ' [gnorm %.4f]' % gn['global']
             if eval_now:
                 msg += ' [eval bits %.5f]' % extra['eval']['bits_per_sample']
             print(progress + msg + display_time(t, (args.num_steps - step) * t), end='', flush=True)

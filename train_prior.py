@@ -7,6 +7,8 @@
 Every step encodes fresh audio crops of `length` x 64 samples with the VQ-VAE's EMA weights (encoder + VQ: one code per 64
 samples) and runs one prior training step on those codes and their speakers.  Checkpoints are `<save>-<step>.pt` (+ a
 `<name>.json` with the prior's config and speaker count).  One GPU: data-parallel prior training is not supported.
+`-clip_norm C` clips the gradients to the global norm C, `-grad_norm` only measures it; either adds `[gnorm ...]` to the
+console line (as train.py).
 """
 import importlib
 import json
@@ -34,7 +36,11 @@ def main():
     parser.add_argument('-params', default='prior_parameters.json', dest='prior_params', metavar='str', help='prior parameters file')
     parser.add_argument('-vqvae_params', default='model_parameters.json', dest='vqvae_params', metavar='str',
                         help='the VQ-VAE\'s parameters file')
+    parser.add_argument('-clip_norm', default=None, type=float, dest='clip_norm', metavar='float', help='clip gradients to this global norm (> 0)')
+    parser.add_argument('-grad_norm', action='store_true', dest='grad_norm', help='log gradient norms without clipping')
     args = parser.parse_args()
+    if args.clip_norm is not None and not args.clip_norm > 0:
+        parser.error('-clip_norm must be > 0 (got %r)' % args.clip_norm)
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         raise NotImplementedError('train_prior.py runs on one GPU (multi-GPU prior training is not supported)')
 
@@ -68,6 +74,7 @@ def main():
     if args.prior_path is not None:
         prior.load_state_dict(torch.load(args.prior_path, map_location='cpu', weights_only=True))
     prior.defer_guard = os.environ.get('VQW_DEFER_GUARD', '1') != '0'
+    prior.clip_norm = args.clip_norm if args.clip_norm is not None else (float('inf') if args.grad_norm else None)
     gs = prior.global_step
     print('[restore] last global step: %d, learning rate: %.5f' % (gs, prior.lr_at(gs)))
     save_dir, save_name = os.path.split(args.save_path)
@@ -84,8 +91,9 @@ def main():
             ws = prior._workspace(args.batch_size, args.frames)
             loss = prior.losses(ws)[0]             # synchronises: only every `interval` steps
             t = time.time() - t
-            print('\r[step %d] %.2f%% [prior %.5f] [lr %.5f] [BATCH %.3fs]     '
-                  % (gs, step / args.num_steps * 100, loss, prior.lr_at(gs - 1), t), end='', flush=True)
+            gnorm = ' [gnorm %.4f]' % prior.grad_norms()['global'] if prior.clip_norm is not None else ''
+            print('\r[step %d] %.2f%% [prior %.5f] [lr %.5f]%s [BATCH %.3fs]     '
+                  % (gs, step / args.num_steps * 100, loss, prior.lr_at(gs - 1), gnorm, t), end='', flush=True)
     torch.cuda.synchronize()
     path = '%s-%d.pt' % (args.save_path, prior.global_step)
     torch.save(prior.state_dict(), path)

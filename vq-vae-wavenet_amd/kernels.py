@@ -716,13 +716,108 @@ def cond_proj_dgrad(w, dce, dcond, scratch, *, B, Cc, Mall, Tz):
 
 
 def adam_ema_step(param, grad, m, v, ema, *, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, decay=0.999,
-                  grad_scale=1.0, skip=None):
-    """skip: device int32 read when the kernel runs; non-zero = the step changes nothing (vqw_adam_ema_step_guarded)."""
+                  grad_scale=1.0, skip=None, scale=None):
+    """skip: device int32 read when the kernel runs; non-zero = the step changes nothing (vqw_adam_ema_step_guarded).
+    scale: device float read when the kernel runs; the step runs on (grad * grad_scale) * scale (vqw_adam_ema_step_scaled:
+    grad_norm's clipping scale).  None: the arithmetic of a step without clipping."""
     n = param.numel()
     for t, nm in ((grad, 'grad'), (m, 'm'), (v, 'v'), (ema, 'ema')):
         _need(t, n, nm)
     if skip is not None and (skip.dtype != torch.int32 or skip.numel() < 1 or not skip.is_cuda):
         raise ValueError('adam_ema_step: skip must be a device int32')
-    L.check(L.lib().vqw_adam_ema_step_guarded(L.ptr(param), L.ptr(grad), L.ptr(m), L.ptr(v), L.ptr(ema), n, float(lr_t),
-                                              float(beta1), float(beta2), float(eps), float(decay), float(grad_scale),
-                                              L.ptr(skip), L.stream()))
+    if scale is not None:
+        _need(scale, 1, 'scale')
+    L.check(L.lib().vqw_adam_ema_step_scaled(L.ptr(param), L.ptr(grad), L.ptr(m), L.ptr(v), L.ptr(ema), n, float(lr_t),
+                                             float(beta1), float(beta2), float(eps), float(decay), float(grad_scale),
+                                             L.ptr(skip), L.ptr(scale), L.stream()))
+
+
+GRAD_NORM_CHUNK = 16384      # floats per workgroup of the norm pass: ~2100 chunks for the 35 M parameters, several per CU
+GRAD_NORM_MAX_SEG = 2048     # vqw_grad_norm_segmented keeps the segments' ranges and sums in LDS
+
+
+class GradNormPlan:
+    """The static chunk table of vqw_grad_norm_segmented (include/vqwave.h: vqw_norm_chunk): numpy arrays start (int64),
+    length and seg (int32), one entry per chunk, the chunks of a segment consecutive; n_seg; end = one past the last element
+    any chunk touches.  device(dev): the table and the fp64 partial scratch on that device (made once)."""
+
+    def __init__(self, start, length, seg, n_seg):
+        import numpy as np
+        self.start, self.length, self.seg = (np.asarray(start, np.int64), np.asarray(length, np.int32), np.asarray(seg, np.int32))
+        self.n_seg, self.n_chunks = int(n_seg), len(self.start)
+        self.end = int((self.start + self.length).max()) if self.n_chunks else 0
+        self._dev = {}
+
+    def device(self, dev):
+        import numpy as np
+        key = str(dev)
+        if key not in self._dev:
+            tab = np.zeros(self.n_chunks, dtype=np.dtype([('start', '<i8'), ('length', '<i4'), ('seg', '<i4')]))
+            tab['start'], tab['length'], tab['seg'] = self.start, self.length, self.seg
+            self._dev[key] = (torch.from_numpy(tab.view(np.int32).reshape(-1, 4).copy()).to(dev),
+                              torch.empty(self.n_chunks, dtype=torch.float64, device=dev))
+        return self._dev[key]
+
+
+def grad_norm_plan_runs(runs, n_seg, chunk=GRAD_NORM_CHUNK):
+    """Chunk table for segments given as runs [(start, length, seg)]: the runs of a segment one after another, segments in
+    ascending order, every segment present, no two runs overlapping (a segment need not be contiguous: the reference's
+    variables are column blocks of the grouped kernels).  Every run is cut into chunks of at most `chunk` elements."""
+    if chunk < 1:
+        raise ValueError('grad_norm_plan: chunk must be >= 1')
+    if not 1 <= n_seg <= GRAD_NORM_MAX_SEG:
+        raise ValueError('grad_norm_plan: %d segments (1 .. %d supported)' % (n_seg, GRAD_NORM_MAX_SEG))
+    start, length, seg = [], [], []
+    seen, prev = 0, -1
+    for s0, n, k in runs:
+        if n <= 0 or s0 < 0:
+            raise ValueError('grad_norm_plan: empty or negative run (%d, %d) of segment %d' % (s0, n, k))
+        if k != prev:
+            if k != prev + 1:
+                raise ValueError('grad_norm_plan: segment %d is empty or the runs are not sorted by segment' % (prev + 1))
+            prev, seen = k, seen + 1
+        for o in range(0, n, chunk):
+            start.append(s0 + o)
+            length.append(min(chunk, n - o))
+            seg.append(k)
+    if seen != n_seg:
+        raise ValueError('grad_norm_plan: segment %d is empty' % seen)
+    order = sorted(range(len(start)), key=start.__getitem__)
+    for a, b in zip(order, order[1:]):
+        if start[a] + length[a] > start[b]:
+            raise ValueError('grad_norm_plan: runs overlap at element %d' % start[b])
+    return GradNormPlan(start, length, seg, n_seg)
+
+
+def grad_norm_plan(seg_bounds, chunk=GRAD_NORM_CHUNK):
+    """Chunk table for contiguous segments laid end to end: segment k is [seg_bounds[k], seg_bounds[k + 1]).  No chunk crosses
+    a segment boundary or is longer than `chunk`; chunks are in ascending order; a zero-length segment is refused."""
+    b = [int(v) for v in seg_bounds]
+    if len(b) < 2:
+        raise ValueError('grad_norm_plan: at least one segment (two bounds) is needed')
+    for k in range(len(b) - 1):
+        if b[k + 1] <= b[k]:
+            raise ValueError('grad_norm_plan: segment %d is empty (bounds %d, %d)' % (k, b[k], b[k + 1]))
+    return grad_norm_plan_runs([(b[k], b[k + 1] - b[k], k) for k in range(len(b) - 1)], len(b) - 1, chunk)
+
+
+def clip_as_fp32(clip):
+    """The threshold as vqw_grad_norm_segmented receives it: rounded to fp32 (a value below fp32's smallest denormal is 0 there,
+    one above its largest finite value is inf = measure only; NaN stays NaN)."""
+    return C.c_float(float(clip)).value
+
+
+def grad_norm(buf, plan, *, grad_scale=1.0, clip=float('inf'), out=None):
+    """vqw_grad_norm_segmented: out = [norm, scale, seg_norm[0 .. n_seg)] (fp32, on the device, no host read) of
+    g = buf * grad_scale over plan's segments; scale = 1 if norm <= clip else clip / norm (clip = inf: measure only)."""
+    _need(buf, plan.end, 'buf')
+    if not clip_as_fp32(clip) > 0.0:
+        raise ValueError('grad_norm: clip must be > 0 in fp32 (inf = measure only), got %r' % clip)
+    clip = float(clip)
+    if out is None:
+        out = torch.empty(plan.n_seg + 2, device=buf.device)
+    _need(out, plan.n_seg + 2, 'out')
+    table, partial = plan.device(buf.device)
+    L.check(L.lib().vqw_grad_norm_segmented(L.ptr(buf), L.ptr(table), plan.n_chunks, plan.n_seg, L.ptr(partial),
+                                            float(grad_scale), clip, L.ptr(out), L.stream()))
+    return out

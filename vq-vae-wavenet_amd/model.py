@@ -91,6 +91,7 @@ class VQVAE:
         self.receptive_field = sum(self.dil) * (self.ks - 1) + 1 + self.pre_k - 1  # wavenet.py:16-17
         self.schedule = [(int(k), float(v)) for k, v in model_cfg['learning_rate_schedule'].items()]
         self.global_step = 0
+        self._clip_norm, self._gn = None, None     # clipping by global norm (clip_norm): off
         self.grad_sync = None   # parallel.GradAllReduce when training data-parallel
         self.overlap_wgrad = os.environ.get('VQW_OVERLAP', '1') != '0'   # decoder backward on two streams
         # Engine of the decoder's contractions.  VQW_ENGINE=f16x3: fp32 operands as two fp16 planes, three
@@ -1433,14 +1434,79 @@ class VQVAE:
                 lr = value
         return lr
 
+    @property
+    def clip_norm(self):
+        """Clipping by global norm (tf.clip_by_global_norm on grad * grad_scale).  None: off, the step is what it
+        was without this attribute.  A float > 0: the threshold.  float('inf'): the norms are measured (grad_norms), nothing
+        is clipped.  Settable at any time; not part of state_dict."""
+        return self._clip_norm
+
+    @clip_norm.setter
+    def clip_norm(self, value):
+        if value is not None:
+            value = float(value)
+            if not K.clip_as_fp32(value) > 0.0:       # (the kernels take the threshold as fp32: 1e-50 would be 0 there)
+                raise ValueError('clip_norm must be None, a threshold > 0 in fp32 or inf (got %r)' % value)
+        elif self._gn is not None:
+            self._gn['steps'] = 0                     # what a step measured before clipping was switched off is not reported later
+        self._clip_norm = value
+
+    def _grad_norm_state(self):
+        """Chunk table and output buffer of the norm pass, made at the first clipped step.  Segment k is the k-th trainable
+        variable under its reference name: the flat elements its view (_named) covers, a column block of a grouped kernel
+        being one run per row.  What no variable covers (alignment padding, the zero-padded condition rows, an unused
+        codebook: gradients that are always zero) is one more, unnamed segment, so that the global norm is that of the whole
+        buffer the optimiser sees."""
+        if self._gn is None:
+            import numpy as np
+            idx = torch.arange(self.n_flat, dtype=torch.int32)
+            owner = np.full(self.n_flat, -1, dtype=np.int32)
+            names = []
+            for k, (name, view) in enumerate(self._named(self._views(idx), bn_stats=False).items()):
+                owner[view.reshape(-1).numpy()] = k
+                names.append(name)
+            rest = len(names)
+            if (owner < 0).any():
+                owner[owner < 0] = rest
+            cut = np.flatnonzero(np.diff(owner)) + 1
+            starts = np.concatenate(([0], cut))
+            ends = np.concatenate((cut, [self.n_flat]))
+            segs = owner[starts]
+            order = np.lexsort((starts, segs))
+            runs = [(int(starts[i]), int(ends[i] - starts[i]), int(segs[i])) for i in order]
+            plan = K.grad_norm_plan_runs(runs, int(segs.max()) + 1)
+            self._gn = {'plan': plan, 'names': names, 'out': torch.zeros(plan.n_seg + 2, device=self.dev), 'steps': 0}
+        return self._gn
+
     def apply_gradients(self, grad_scale=1.0, skip=None):
-        """TF-1.x Adam + EMA(0.999) (model.py:116-128).  skip: device int32, non-zero when the kernel runs = nothing changes."""
+        """TF-1.x Adam + EMA(0.999) (model.py:116-128).  skip: device int32, non-zero when the kernel runs = nothing changes.
+        With clip_norm set, the two launches of the norm pass run first on the same stream and the optimiser reads their scale
+        on the device (no host read; a voided step measures a norm too, and its repeat overwrites it)."""
         t = self.global_step + 1
         lr = self.lr_at(self.global_step)
         lr_t = lr * math.sqrt(1.0 - 0.999 ** t) / (1.0 - 0.9 ** t)
-        K.adam_ema_step(self.flat, self.grad, self.adam_m, self.adam_v, self.ema, lr_t=lr_t, grad_scale=grad_scale, skip=skip)
+        scale = None
+        if self._clip_norm is not None:
+            gn = self._grad_norm_state()
+            K.grad_norm(self.grad, gn['plan'], grad_scale=grad_scale, clip=self._clip_norm, out=gn['out'])
+            gn['steps'] += 1
+            scale = gn['out'][1:2]
+        K.adam_ema_step(self.flat, self.grad, self.adam_m, self.adam_v, self.ema, lr_t=lr_t, grad_scale=grad_scale, skip=skip,
+                        scale=scale)
         self.global_step = t
         return lr
+
+    def grad_norms(self):
+        """Gradient norms of the last step, measured on the device before the optimiser ran (clip_norm set):
+        {'global': norm of grad * grad_scale, 'scale': what the step multiplied it by (1.0 = not clipped),
+         'segments': {reference variable name: norm}} with the trainable names of named_parameters().  Synchronises."""
+        if self._clip_norm is None:
+            raise ValueError('grad_norms: clip_norm is None (set a threshold, or inf to measure only)')
+        self.finish_steps()
+        if self._gn is None or self._gn['steps'] == 0:
+            raise ValueError('grad_norms: no step has run since clip_norm was set')
+        out = self._gn['out'].tolist()
+        return {'global': out[0], 'scale': out[1], 'segments': OrderedDict(zip(self._gn['names'], out[2:]))}
 
     def train_step(self, x, spk, on_forward=None):
         """One sess.run(train_op) (train.py:104-114).  on_forward(ws): called between the forward and the backward pass of the
