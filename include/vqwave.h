@@ -229,6 +229,22 @@ int vqw_speaker_tile_bwd(const float* dcond, int64_t dcond_bstride, int row0,
                          vqw_stream_t s);
 
 /* ------------------------------------------------------------------------------------
+ * Time-jitter regularisation of the latents (arXiv 1901.08810; the reference's unused
+ * Decoder/decoder_ops.py:5-28, but per utterance: rows are independent).
+ * zq [B][D][Tz] at batch stride zq_bstride, u fp32 [B][Tz] in [0, 1); lo = fp32(p / 2), hi = fp32(1 - p / 2):
+ *   move = -1 if u < lo, +1 if u >= hi, else 0 (fp32 compares);  src = t + move, reflected into [0, Tz)
+ *   (src < 0: += 2; src >= Tz: -= 2; Tz == 1: 0).
+ * Forward: out[b][d][t] = zq[b][d][src[b][t]] (a copy, no arithmetic) at batch stride out_bstride, and src int32 [B][Tz].
+ * Backward: dzq[b][d][s] = sum of dout[b][d][t] over t in {s-1, s, s+1} inside [0, Tz) with src[b][t] == s, added in
+ * ascending t in fp32 from +0.0f; every element of dzq is written, nothing is atomic: bitwise reproducible.
+ * Any D >= 1 and Tz >= 1; batch strides >= D * Tz (the tensors may be the first D rows of wider [B][C][Tz] buffers).
+ * out must not alias zq, dzq must not alias dout.                                                                  */
+int vqw_time_jitter_fwd(const float* zq, int64_t zq_bstride, const float* u, float lo, float hi, float* out,
+                        int64_t out_bstride, int32_t* src, int B, int D, int Tz, vqw_stream_t s);
+int vqw_time_jitter_bwd(const float* dout, int64_t dout_bstride, const int32_t* src, float* dzq, int64_t dzq_bstride,
+                        int B, int D, int Tz, vqw_stream_t s);
+
+/* ------------------------------------------------------------------------------------
  * Softmax cross-entropy over the channel axis -- model.py:91-94.
  * logits [B][Q][T], labels int32 [B][T].  loss_sum[0] += sum_{b,t} CE;
  * dlogits (optional, may alias logits) = (softmax - onehot) * grad_scale;

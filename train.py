@@ -17,6 +17,11 @@ that step's line of summaries.jsonl.  The list is in the format of the `<name>_t
 `-clip_norm C`: gradients are clipped to the global norm C (tf.clip_by_global_norm; norm and scale stay on the device).
 `-grad_norm`: the norms are measured and logged, nothing is clipped.  Either adds `[gnorm ...]` to the console line and
 `grad_norm`, `grad_clip_scale` and a per-variable `grad_norms` object to summaries.jsonl, on logged steps.
+
+`-time_jitter P`: in training, every latent frame the decoder reads is replaced with probability P by its left or right
+neighbour of the same utterance (arXiv 1901.08810; overrides `time_jitter` of the parameters file, 0 = off).  Adds
+`[jitter ...]` to the console line and `jitter_moved` (the share of frames that moved in that step) to summaries.jsonl, on
+logged steps.
 """
 import importlib
 import json
@@ -60,9 +65,13 @@ def main():
     parser.add_argument('-data_root', default='data/', dest='data_root', metavar='string', help='where the held-out wavs and *_speakers.txt are')
     parser.add_argument('-clip_norm', default=None, type=float, dest='clip_norm', metavar='float', help='clip gradients to this global norm (> 0)')
     parser.add_argument('-grad_norm', action='store_true', dest='grad_norm', help='log gradient norms without clipping')
+    parser.add_argument('-time_jitter', default=None, type=float, dest='time_jitter', metavar='float',
+                        help='probability in [0, 1] that a latent frame the decoder reads is its neighbour (0 = off)')
     args = parser.parse_args()
     if args.clip_norm is not None and not args.clip_norm > 0:
         parser.error('-clip_norm must be > 0 (got %r)' % args.clip_norm)
+    if args.time_jitter is not None and not 0.0 <= args.time_jitter <= 1.0:
+        parser.error('-time_jitter must be a probability in [0, 1] (got %r)' % args.time_jitter)
     if args.eval_interval < 0 or args.eval_batches < 1:
         parser.error('-eval_interval must be >= 0 and -eval_batches >= 1')
     if args.eval_interval > 0 and args.eval_list is None:
@@ -106,6 +115,8 @@ def main():
     parameters, wavenet_parameters = pkg.model.load_configs(args.parameter_path)
     if parameters['encoder'] not in ('64', 'Magenta', '2019'):                      # train.py:52-60
         raise NotImplementedError('encoder %s not implemented' % parameters['encoder'])
+    if args.time_jitter is not None:
+        parameters['time_jitter'] = args.time_jitter
     model = pkg.model.VQVAE(parameters, wavenet_parameters, dataset.num_speakers, device=dev, seed=0)
     if args.restore_path is not None:
         if args.restore_path.endswith(('.safetensors', '.npz')):      # TF variable names (checkpoint.py)
@@ -145,6 +156,8 @@ def main():
         if rank == 0 and (gs % args.interval == 0 or step == args.num_steps or eval_now):
             loss, rl, vq, commit = model.losses(ws)          # synchronises: only every `interval` steps
             extra = {}
+            if model.time_jitter > 0:             # from the step's source frames; read here, on logged steps only
+                extra['jitter_moved'] = model.jitter_moved(ws)
             if eval_now:
                 extra['eval'] = pkg.scoring.score_batches(model, eval_set, dev, weights='ema').report(
                     'sample', latent_dim=model.D if model.use_vq else 0)
@@ -155,6 +168,8 @@ def main():
                 gn = model.grad_norms()
                 extra.update(grad_norm=gn['global'], grad_clip_scale=gn['scale'], grad_norms=gn['segments'])
                 msg += ' [gnorm %.4f]' % gn['global']
+            if 'jitter_moved' in extra:
+                msg += ' [jitter %.3f]' % extra['jitter_moved']
             if eval_now:
                 msg += ' [eval bits %.5f]' % extra['eval']['bits_per_sample']
             print(progress + msg + display_time(t, (args.num_steps - step) * t), end='', flush=True)

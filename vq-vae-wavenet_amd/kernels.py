@@ -581,6 +581,43 @@ def vq_nearest_bwd(z_e, e_k, idx, *, dzq, dzq_bstride, dz_e, demb, cscale, escal
                                        L.ptr(demb), float(cscale), float(escale), B, D, Tz, K, L.stream()))
 
 
+def jitter_thresholds(p):
+    """(lo, hi) of vqw_time_jitter_fwd for a jitter probability p in [0, 1]: fp32(p / 2) and fp32(1 - p / 2), each computed
+    in float64 and rounded once.  A frame moves left where u < lo, right where u >= hi."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError('time_jitter must be a probability in [0, 1] (got %r)' % p)
+    return C.c_float(p / 2.0).value, C.c_float(1.0 - p / 2.0).value
+
+
+def time_jitter_fwd(zq, u, out, src, *, p, D, zq_bstride=0, out_bstride=0):
+    """vqw_time_jitter_fwd: out[b][d][t] = zq[b][d][src[b][t]] for d < D, src (int32 [B][Tz]) from u [B][Tz] and p.  zq / out
+    are [B][>= D][Tz] buffers whose first D rows are used (batch strides default to D * Tz)."""
+    B, Tz = u.shape
+    L.require_cuda(zq, u, out, src)
+    lo, hi = jitter_thresholds(p)
+    zq_bstride, out_bstride = zq_bstride or D * Tz, out_bstride or D * Tz
+    _need(u, B * Tz, 'u')
+    _need(zq, (B - 1) * zq_bstride + D * Tz, 'zq')
+    _need(out, (B - 1) * out_bstride + D * Tz, 'out')
+    _need_i32(src, B * Tz, 'src')
+    L.check(L.lib().vqw_time_jitter_fwd(L.ptr(zq), zq_bstride, L.ptr(u), lo, hi, L.ptr(out), out_bstride, L.ptr(src),
+                                        B, D, Tz, L.stream()))
+
+
+def time_jitter_bwd(dout, src, dzq, *, D, dout_bstride=0, dzq_bstride=0):
+    """vqw_time_jitter_bwd: dzq[b][d][s] = sum of dout[b][d][t] over the t in {s-1, s, s+1} with src[b][t] == s, in ascending
+    t (gather form: no atomics, bitwise reproducible).  Strides as time_jitter_fwd."""
+    B, Tz = src.shape
+    L.require_cuda(dout, src, dzq)
+    dout_bstride, dzq_bstride = dout_bstride or D * Tz, dzq_bstride or D * Tz
+    _need(dout, (B - 1) * dout_bstride + D * Tz, 'dout')
+    _need(dzq, (B - 1) * dzq_bstride + D * Tz, 'dzq')
+    _need_i32(src, B * Tz, 'src')
+    L.check(L.lib().vqw_time_jitter_bwd(L.ptr(dout), dout_bstride, L.ptr(src), L.ptr(dzq), dzq_bstride, B, D, Tz,
+                                        L.stream()))
+
+
 def _need_speakers(spk, table, Cs):
     if spk.dtype != torch.int64:
         raise ValueError('speaker ids must be int64, got %s' % spk.dtype)

@@ -72,6 +72,10 @@ class VQVAE:
     """model.py:7-159.  encoder '64' + VQ + speaker embedding + WaveNet decoder."""
 
     scope = 'decoder'      # name scope of the WaveNet's variables (named_parameters)
+    _time_jitter = 0.0     # probability that a latent frame the decoder reads is its neighbour's (time_jitter; 0 = off)
+    jitter_seed = 0        # seed of the jitter draws (jitter_uniforms); not part of state_dict
+    _jitter_gen = None     # the device generator of jitter_uniforms
+    _jitter_step = None    # the step whose forward pass is running inside train_step; None: no jitter (forward(), evaluate, ...)
 
     def __init__(self, model_cfg, wavenet_cfg, num_speakers, device='cuda', seed=0):
         self.m, self.w = model_cfg, wavenet_cfg
@@ -173,6 +177,7 @@ class VQVAE:
         self.Cs = model_cfg['speaker_embedding']
         self.beta = float(model_cfg['beta'])
         self.use_vq = bool(model_cfg.get('use_vq', True))     # false: z_q = e_k = z_e, reconstruction loss only (model.py:139-141)
+        self.time_jitter = model_cfg.get('time_jitter', 0.0)  # train_step only: latent frames the decoder reads move
         # speaker_embedding = 0: the one-hot speaker vector itself is the global condition (model.py:19-27 leaves self.h
         # as [B, 1, num_speakers]); its width is padded to a multiple of 16 channels for the conv engine (the extra
         # condition rows are always zero, their kernel rows never receive a gradient)
@@ -641,15 +646,79 @@ class VQVAE:
     def _quantise(self, spk, ws):
         """model.py:57-74 (VQ) + model.py:22-27 / decoder_ops.py:39-43 (speaker embedding tiled over time)."""
         P, D, Tz = self.P, self.D, ws['Tz']
+        # time jitter (a train_step's passes only): z_q goes to a buffer of its own and the jitter kernel fills the
+        # condition's first D rows from it; idx, e_k, mind (the VQ / commitment losses) are those of the un-jittered latents
+        jit = ws['jittered'] = self._jitter_step is not None and self._time_jitter > 0.0
+        zq, zq_bs = (self._jitter_buffers(ws)['zq'], D * Tz) if jit else (ws['cond'], self.Cc * Tz)
         if self.use_vq:
-            K.vq_nearest_fwd(ws['z_e'], P['embedding'], idx=ws['idx'], e_k=ws['e_k'], zq=ws['cond'],
-                             zq_bstride=self.Cc * Tz, mind=ws['mind'])
+            K.vq_nearest_fwd(ws['z_e'], P['embedding'], idx=ws['idx'], e_k=ws['e_k'], zq=zq, zq_bstride=zq_bs, mind=ws['mind'])
         else:                       # z_q = e_k = z_e (model.py:139-141): a copy, no quantisation losses
-            ws['cond'][:, :D].copy_(ws['z_e'])
+            (zq if jit else zq[:, :D]).copy_(ws['z_e'])
             ws['idx'].zero_()
             ws['mind'].zero_()
+        if jit:
+            ws['jitter_u'].copy_(self.jitter_uniforms(ws['B'], Tz, self._jitter_step))
+            K.time_jitter_fwd(zq, ws['jitter_u'], ws['cond'], ws['jitter_src'], p=self._time_jitter, D=D,
+                              out_bstride=self.Cc * Tz)
         K.speaker_tile_fwd(P['speaker_embedding'] if self.spk_table else self.onehot, spk, ws['cond'],
                            cond_bstride=self.Cc * Tz, row0=D, Cs=self.Cs_eff, Tz=Tz)
+
+    # ------------------------------------------------------------------ time jitter (DESIGN 3.10)
+    @property
+    def time_jitter(self):
+        """Probability that a latent frame the decoder reads in train_step is replaced by its left or right neighbour of the
+        same utterance (p / 2 each; arXiv 1901.08810).  0: off, the step is what it was without this attribute.
+        forward() called directly, evaluate, encode and the generators never jitter.  Not part of state_dict."""
+        return self._time_jitter
+
+    @time_jitter.setter
+    def time_jitter(self, value):
+        K.jitter_thresholds(value)                    # (refuses what is not a probability)
+        self._time_jitter = float(value)
+
+    def _jitter_buffers(self, ws):
+        """z_q before the jitter, its gradient, the step's uniforms and source frames: made at the first jittered step."""
+        if 'zq' not in ws:
+            B, D, Tz = ws['B'], self.D, ws['Tz']
+            with A.record(ws['_poison']):
+                ws['zq'], ws['dzq'] = A.empty(B, D, Tz, device=self.dev), A.empty(B, D, Tz, device=self.dev)
+                ws['jitter_u'] = A.empty(B, Tz, device=self.dev)
+            ws['jitter_src'] = torch.zeros(B, Tz, dtype=torch.int32, device=self.dev)
+        return ws
+
+    def jitter_uniforms(self, B, Tz, step):
+        """The uniforms [B][Tz] (fp32 in [0, 1), on the device) that decide step `step`'s jitter: a pure function of
+        (jitter_seed, step, data-parallel rank) -- a device generator of its own, seeded again at every call, so the global
+        torch RNG is never touched and every pass that belongs to one step (the fp16x3 attempt, its fp32 repeat, a deferred
+        step run again) draws the same values.  No host sync.  Each data-parallel rank draws its own stream: a sharded batch
+        is not the same draw as the full batch."""
+        if self._jitter_gen is None:
+            self._jitter_gen = torch.Generator(device=self.dev)
+        rank = self.grad_sync.rank if self.grad_sync is not None else 0
+        seed = 0
+        for v in (self.jitter_seed, step, rank):      # splitmix64 over the three words
+            seed = (seed ^ (int(v) & 0xFFFFFFFFFFFFFFFF)) + 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF
+            seed = (seed ^ (seed >> 30)) * 0xBF58476D1CE4E5B9 & 0xFFFFFFFFFFFFFFFF
+            seed = (seed ^ (seed >> 27)) * 0x94D049BB133111EB & 0xFFFFFFFFFFFFFFFF
+            seed ^= seed >> 31
+        self._jitter_gen.manual_seed(seed >> 1)
+        return torch.rand(B, Tz, generator=self._jitter_gen, device=self.dev)
+
+    def jitter_moved(self, ws):
+        """Share of the (b, t) whose frame moved (src != t) in the last jittered pass on ws (synchronises); 0.0 without jitter."""
+        if not ws.get('jittered'):
+            return 0.0
+        self.finish_steps()
+        src = ws['jitter_src']
+        return float((src != torch.arange(ws['Tz'], dtype=torch.int32, device=self.dev)).float().mean())
+
+    def _forward_step(self, x, spk, step):
+        """forward() as a pass of training step `step`: the only passes that jitter the latents."""
+        self._jitter_step = step
+        try:
+            return self.forward(x, spk)
+        finally:
+            self._jitter_step = None
 
     def _decode_train(self, x, ws, save=True):
         """wavenet.py:24-100 -> ws['logits'] [B][Q][T], ws['labels']."""
@@ -1318,10 +1387,14 @@ class VQVAE:
         if self.spk_table:
             K.speaker_tile_bwd(ws['dcond'], spk, G['speaker_embedding'], dcond_bstride=self.Cc * Tz, row0=D, Cs=self.Cs, Tz=Tz)
         nd = float(B * Tz * D)
+        dzq, dzq_bs = ws['dcond'], self.Cc * Tz
+        if ws.get('jittered'):      # d z_q from d cond through the transposed gather (straight into dz where nothing is quantised)
+            dzq, dzq_bs = ws['dzq'] if self.use_vq else ws['dz'], D * Tz
+            K.time_jitter_bwd(ws['dcond'], ws['jitter_src'], dzq, D=D, dout_bstride=self.Cc * Tz)
         if self.use_vq:
-            K.vq_nearest_bwd(ws['z_e'], ws['e_k'], ws['idx'], dzq=ws['dcond'], dzq_bstride=self.Cc * Tz, dz_e=ws['dz'],
+            K.vq_nearest_bwd(ws['z_e'], ws['e_k'], ws['idx'], dzq=dzq, dzq_bstride=dzq_bs, dz_e=ws['dz'],
                              demb=G['embedding'], cscale=2.0 * self.beta / nd, escale=2.0 / nd, K=self.Kc)
-        else:
+        elif not ws.get('jittered'):
             ws['dz'].copy_(ws['dcond'][:, :D])
         if self.enc != '64':
             self.magenta.backward(x, ws, P, G, Tt)
@@ -1524,10 +1597,11 @@ class VQVAE:
         """The step with its range flag read on the spot.  known_flagged: the fp16x3 attempt of this step already ran and
         raised the flag (deferred mode): go straight to the repeat."""
         guarded, world, ws = self.x3_guard and known_flagged, 1, None
+        gs0 = self.global_step           # (every pass of this step draws the same jitter: jitter_uniforms)
         if not known_flagged:
             if self.x3_guard:
                 self.x3_flag.zero_()
-            ws = self.forward(x, spk)
+            ws = self._forward_step(x, spk, gs0)
             if on_forward is not None:
                 on_forward(ws)
             self.backward(x, spk, ws)
@@ -1541,7 +1615,7 @@ class VQVAE:
                 self._x3_active = False
                 try:
                     self.x3_amax.zero_()
-                    ws = self.forward(x, spk)
+                    ws = self._forward_step(x, spk, gs0)
                     for l in range(1, self.L):       # what the layer-input planes would have held (net[L] feeds nothing)
                         K.f16x3_amax(ws['net'][l], self.x3_amax[self.SL['X'] + l:self.SL['X'] + l + 1])
                     K.f16x3_amax(ws['skip'], self.x3_amax[self.SL['SK']:self.SL['SK'] + 1])
@@ -1576,7 +1650,7 @@ class VQVAE:
         self.x3_flag.zero_()
         self._in_step = True
         try:
-            ws = self.forward(x, spk)
+            ws = self._forward_step(x, spk, self.global_step)
             self.backward(x, spk, ws)
         finally:
             self._in_step = False

@@ -18,6 +18,7 @@ class GradAllReduce:
         self.flat = flat_grad
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0       # (seeds this rank's time-jitter draws)
         self.active = self.world > 1 or (force and dist.is_initialized())
         self.buckets = []           # (lo, hi) of every bucket exchanged since the last finish(), in launch order
         self.cuda = flat_grad.is_cuda
