@@ -15,7 +15,7 @@ import math
 import os
 import time
 import sys
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 
@@ -25,6 +25,23 @@ from .encoders import Encoder2019, EncoderMagenta
 
 BN_EPS = 1e-3  # Keras BatchNormalization default epsilon
 DEFAULT_ENGINE = 'f16x3'
+
+# The model's VQW_* switches (tools/README.md), read ONCE, when a model is constructed (VQVAE.sw): field name = variable name.
+_ON = 'overlap wgrad_pp head_x3 cond_proj enc_x3 sconv_split wgrad_batch wgrad_x3 wgrad_qp enc_wgrad_x3'.split()         # off with '0'
+_IS1 = dict(x3_half='1', x3_half_skip='0', x3_half_bwd='1', x3_half_dgrad='0', x3_half_head='1', defer_guard='0', save_tanh='0', save_gated='0')  # on with '1'
+Switches = namedtuple('Switches', ['engine', 'gate_f16x3', 'dtype', 'skip_groups', 'wg_gate_batch', 'wg_res_batch'] + _ON + list(_IS1))
+StepPlan = namedtuple('StepPlan', 'save f16x3 f16x3_out f16x3_skip x3_used gd calib ngrp WS GS GSh head_x3 keep_xp drop_th drop_g dgrad_x3 gbwd_x3 '
+                      'wg_x3 batched qp pp gate_batch res_batch enc_x3 enc_wg3 why')      # which engine carries what in one pass (VQVAE._step_plan)
+
+
+def read_switches(dtype='f32'):
+    """The environment's switches with their defaults (dtype: the config's; VQW_DTYPE overrides it)."""
+    env = lambda name, dflt: os.environ.get('VQW_' + name.upper(), dflt)                           # noqa: E731
+    batch = lambda name, dflt: max(1, min(K.WGRAD_MAX_BATCH, int(env(name, dflt))))                 # noqa: E731
+    return Switches(engine=env('engine', DEFAULT_ENGINE), gate_f16x3=env('gate_f16x3', '0'), dtype=env('dtype', dtype), skip_groups=max(1, int(env('skip_groups', '1'))),
+                    wg_gate_batch=batch('wg_gate_batch', '6'), wg_res_batch=batch('wg_res_batch', '29'), **{n: env(n, '1') != '0' for n in _ON},
+                    **{n: env(n, d) == '1' for n, d in _IS1.items()})
+
 
 
 def load_configs(model_json='model_parameters.json', wavenet_json=None):
@@ -97,31 +114,31 @@ class VQVAE:
         self.global_step = 0
         self._clip_norm, self._gn = None, None     # clipping by global norm (clip_norm): off
         self.grad_sync = None   # parallel.GradAllReduce when training data-parallel
-        self.overlap_wgrad = os.environ.get('VQW_OVERLAP', '1') != '0'   # decoder backward on two streams
+        sw = self.sw = read_switches(model_cfg.get('dtype', 'f32'))      # after this line nothing in the class reads the environment
+        self.overlap_wgrad = sw.overlap                                  # decoder backward on two streams
         # Engine of the decoder's contractions.  VQW_ENGINE=f16x3: fp32 operands as two fp16 planes, three
         # MFMA terms on the fp16 matrix pipe, fp32 accumulate, with device-side range guards (per-tensor power-of-two
         # scales from measured max-abs values; a step whose planes would leave fp16's range is repeated on the fp32
         # engine).  VQW_ENGINE=fp32: the fp32-MFMA engine everywhere.  VQW_GATE_F16X3=1..5 (development ladder, fixed
         # scales, no guards): 1 gate convs; 2 + the 1x1 skip/residual convs; 3 skip path as ONE contraction; 4 + the gate
         # convs' input gradient; 5 + gate backward.
-        engine = os.environ.get('VQW_ENGINE', DEFAULT_ENGINE)
+        engine, ladder = sw.engine, sw.gate_f16x3
         if engine not in ('fp32', 'f16x3'):
             raise ValueError("VQW_ENGINE must be 'fp32' or 'f16x3' (got %r)" % engine)
-        ladder = os.environ.get('VQW_GATE_F16X3', '0')
         # VQW_DTYPE=bf16 (BASELINE.json configs[4]: bf16 storage + fp32 accumulate): the same kernels with ONE bf16 plane per
         # operand and one bf16 MFMA per product; master weights, optimiser state and the residual stream stay fp32
-        self.bf16 = os.environ.get('VQW_DTYPE', model_cfg.get('dtype', 'f32')) == 'bf16'
+        self.bf16 = sw.dtype == 'bf16'
         # mode bits of the plane engine: bf16, and the block height of its conv kernels per call site -- 128-row blocks (two
         # per CU) for the forward gate conv + residual 1x1 (decoder forward loop 6.05 vs 7.13 ms, tools/x3_chain.py) and for
         # gate backward, 256-row blocks for the K = 7680 skip contraction and the input gradient (whole step, same box:
         # 34.1 ms against 35.0 with 256-row blocks everywhere): VQW_X3_HALF, _SKIP, _BWD, _DGRAD
         self.x3_mode = K.X3_BF16 if self.bf16 else 0
-        half = lambda name, dflt: self.x3_mode | (K.X3_HALF_BLOCKS if os.environ.get(name, dflt) == '1' else 0)  # noqa: E731
-        self.x3_mode_fwd = half('VQW_X3_HALF', '1')                                        # gate conv + residual 1x1
-        self.x3_mode_skip = half('VQW_X3_HALF_SKIP', '0')                                  # the all-layers skip contraction
-        self.x3_mode_bwd = half('VQW_X3_HALF_BWD', '1')                                    # gate backward
-        self.x3_mode_dgrad = half('VQW_X3_HALF_DGRAD', '0')                                # input gradient
-        self.x3_mode_head = half('VQW_X3_HALF_HEAD', '1')                                  # postprocess1 / 2 and their input gradients
+        half = lambda on: self.x3_mode | (K.X3_HALF_BLOCKS if on else 0)  # noqa: E731
+        self.x3_mode_fwd = half(sw.x3_half)                # gate conv + residual 1x1
+        self.x3_mode_skip = half(sw.x3_half_skip)          # the all-layers skip contraction
+        self.x3_mode_bwd = half(sw.x3_half_bwd)            # gate backward
+        self.x3_mode_dgrad = half(sw.x3_half_dgrad)        # input gradient
+        self.x3_mode_head = half(sw.x3_half_head)          # postprocess1 / 2 and their input gradients
         self.x3_guard = engine == 'f16x3' and ladder == '0' and not self.bf16
         self.x3_all = self.x3_guard or self.bf16          # the plane engine carries every decoder contraction, or none
         if self.x3_all:
@@ -131,7 +148,7 @@ class VQVAE:
         self.skip_f16x3 = ladder in ('3', '4', '5')
         self.dgrad_f16x3 = ladder in ('4', '5')
         self.gbwd_f16x3 = ladder == '5'
-        self.wg_planes = os.environ.get('VQW_WGRAD_PP', '1') != '0'      # weight gradients read p from operand planes too
+        self.wg_planes = sw.wgrad_pp    # weight gradients read p from operand planes too
         self._x3_active = True         # False while a step is being repeated on the fp32 engine
         self._x3_warned = set()        # (B, T) shapes already reported as running on the fp32 engine
         self.x3_fallbacks = 0          # steps repeated on the fp32 engine because a plane left fp16's range
@@ -156,14 +173,14 @@ class VQVAE:
         self.x3_scale[self.SL['G']] = 2.0 ** 20          # first step: |d loss / d logits| <= 1 / (B T)
         self.x3_scale[self.SL['DP']:self.SL['SK']] = 2.0 ** 20
         self.x3_scale[self.SL['DH']] = 2.0 ** 20
-        self.head_x3 = os.environ.get('VQW_HEAD_X3', '1') != '0'
+        self.head_x3 = sw.head_x3
         self.x3_amax = torch.zeros(self.SL['N'], dtype=torch.int32, device=self.dev)
         self.x3_flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self.x3_void = torch.zeros(1, dtype=torch.int32, device=self.dev)      # deferred mode: a flagged step is waiting to be repeated
-        self.defer_guard = os.environ.get('VQW_DEFER_GUARD', '0') == '1'       # read the range flag one step late (train_step)
+        self.defer_guard = sw.defer_guard       # read the range flag one step late (train_step)
         self._pending, self._void_host, self._void_slot, self._in_step = [], None, 0, False
         # the condition projections (K = Cc ~ 80, rows of Tz ~ 104 frames) on their own fp32-MFMA kernels (csrc/cond_proj.hip)
-        self.cond_proj = self.Cc <= 128 and self.Mall % 4 == 0 and os.environ.get('VQW_COND_PROJ', '1') != '0'
+        self.cond_proj = self.Cc <= 128 and self.Mall % 4 == 0 and sw.cond_proj
         self.host_enqueue_ms = None
 
     def _setup_front(self, model_cfg, num_speakers):
@@ -420,34 +437,7 @@ class VQVAE:
         ws['gated'] = [e(B, R, T) for _ in range(L)]
         ws['th'] = [e(B, R, T) for _ in range(L)]
         ws['sg'] = [e(B, R, T) for _ in range(L)]
-        if self.gate_f16x3:
-            ws['xp'] = A.empty(2 * B * R * T, dtype=torch.float16, device=dev)
-            # the input planes of EVERY layer are kept (1.6 GB at B = 8) where the weight gradients read them (backward: p_planes)
-            if self.x3_all and self.wg_planes:
-                ws['xp_all'] = [ws['xp']] + [A.empty(2 * B * R * T, dtype=torch.float16, device=dev) for _ in range(L)]
-            ws['wp_all'] = A.empty(L, 2 * self.ks * R * 2 * R, dtype=torch.float16, device=dev)
-            ws['wp'] = [ws['wp_all'][l] for l in range(L)]
-            ws['gp'] = A.empty(2 * B * R * T * (L if self.skip_f16x3 else 1), dtype=torch.float16, device=dev)
-            if self.dgrad_f16x3:
-                ws['dp'] = A.empty(2 * B * 2 * R * T, dtype=torch.float16, device=dev)
-                ws['wdg'] = A.empty(L, 2 * self.ks * 2 * R * R, dtype=torch.float16, device=dev)
-                if self.gbwd_f16x3:
-                    ws['gr'] = A.empty(2 * B * (S + R) * T, dtype=torch.float16, device=dev)   # [dskip | dnet] lifted planes
-                    ws['wgb'] = A.empty(L, 2 * (S + R) * R, dtype=torch.float16, device=dev)
-                    ws['wgb_top'] = A.empty(2 * S * R, dtype=torch.float16, device=dev)
-            if self.skip_f16x3:
-                ws['wskip'] = A.empty(2 * L * R * S, dtype=torch.float16, device=dev)
-                ws['wres'] = A.empty(L, 2 * R * R, dtype=torch.float16, device=dev)
-                if (self.x3_guard or self.bf16) and self.gbwd_f16x3 and S % 256 == 0 and Q % 256 == 0:     # the convs around the stack on the engine too
-                    ws['hp'] = A.empty(2 * B * S * T, dtype=torch.float16, device=dev)     # relu(skip) / d postprocess1 planes
-                    ws['hp2'] = A.empty(2 * B * S * T, dtype=torch.float16, device=dev)    # relu(postprocess1) / d logits planes
-                    for name, n_ in (('wskip0', R * S), ('wpost1', S * S), ('wpost2', S * Q)):
-                        ws[name] = A.empty(2 * n_, dtype=torch.float16, device=dev)
-                        ws[name + 't'] = A.empty(2 * n_, dtype=torch.float16, device=dev)
-                    # |d loss / d logits| <= 1 / (B T): a fixed power-of-two scale, max-abs below 2^13
-                    ws['dl_scale'] = torch.full((1,), 2.0 ** math.floor(math.log2(2.0 ** 13 * B * T)), device=dev)
-            ws['wop_all'] = A.empty(L, 2 * R * (S + R), dtype=torch.float16, device=dev)
-            ws['wop'] = [ws['wop_all'][l] for l in range(L)]
+        self._plane_buffers(ws, True)
         ws['h1'] = e(B, S, T)
         ws['logits'] = e(B, Q, T)
         # backward
@@ -461,6 +451,43 @@ class VQVAE:
         self._front_workspace_train(ws)
         return ws
 
+    def _head_on_engine(self):          # the convs around the stack (skip start, postprocess1 / 2) can run on the plane engine
+        return self.x3_all and self.S % 256 == 0 and self.Q % 256 == 0
+
+    def _keeps_layer_planes(self):      # the input planes of EVERY layer are kept (1.6 GB at B = 8) for the weight gradients (p_planes)
+        return self.x3_all and self.wg_planes
+
+    def _enc_on_engine(self):           # Encoder_64's long strided layers can run on the guarded fp16x3 engine (_front_workspace)
+        return self.x3_guard and self.enc == '64' and self.F % 256 == 0
+
+    def _plane_buffers(self, ws, train):
+        """The decoder's operand planes (fp16 pairs / bf16) of a training workspace (train: with what only the backward pass reads) or a score workspace."""
+        if not self.gate_f16x3:
+            return
+        R, S, Q, L, ks, B, T = self.R, self.S, self.Q, self.L, self.ks, ws['B'], ws['T']
+        h = lambda *s: A.empty(*s, dtype=torch.float16, device=self.dev)  # noqa: E731
+        ws['xp'] = h(2 * B * R * T)
+        if train and self._keeps_layer_planes():
+            ws['xp_all'] = [ws['xp']] + [h(2 * B * R * T) for _ in range(L)]
+        ws['wp_all'] = h(L, 2 * ks * R * 2 * R)
+        ws['wp'] = [ws['wp_all'][l] for l in range(L)]
+        ws['gp'] = h(2 * B * R * T * (L if self.skip_f16x3 else 1))
+        if train and self.dgrad_f16x3:
+            ws['dp'], ws['wdg'] = h(2 * B * 2 * R * T), h(L, 2 * ks * 2 * R * R)
+            if self.gbwd_f16x3:     # gr: the [dskip | dnet] lifted planes
+                ws['gr'], ws['wgb'], ws['wgb_top'] = h(2 * B * (S + R) * T), h(L, 2 * (S + R) * R), h(2 * S * R)
+        if self.skip_f16x3:
+            ws['wskip'], ws['wres'] = h(2 * L * R * S), h(L, 2 * R * R)
+            if self._head_on_engine():
+                ws['hp'], ws['hp2'] = h(2 * B * S * T), h(2 * B * S * T)   # relu(skip) / d postprocess1, relu(postprocess1) / d logits
+                for name, n_ in (('wskip0', R * S), ('wpost1', S * S), ('wpost2', S * Q)):
+                    for sfx in (('', 't') if train else ('',)):      # (+ 't': the transposed kernel of the input gradient)
+                        ws[name + sfx] = h(2 * n_)
+                if train:     # |d loss / d logits| <= 1 / (B T): a fixed power-of-two scale, max-abs below 2^13
+                    ws['dl_scale'] = torch.full((1,), 2.0 ** math.floor(math.log2(2.0 ** 13 * B * T)), device=self.dev)
+        ws['wop_all'] = h(L, 2 * R * (S + R))
+        ws['wop'] = [ws['wop_all'][l] for l in range(L)]
+
     def _score_workspace(self, ws):
         """The decoder's buffers for a pass with save=False on top of the encoder + VQ forward buffers (evaluate): no per-layer
         fp32 activations (two ping-pong net buffers and one gated buffer, aliased into the lists _decode_layers indexes), ONE
@@ -468,25 +495,12 @@ class VQVAE:
         over K = L*R reads them), no tanh / sigmoid and no backward buffers."""
         dev, R, S, Q, L, B, T = self.dev, self.R, self.S, self.Q, self.L, ws['B'], ws['T']
         e = lambda *s: A.empty(*s, device=dev)  # noqa: E731
-        h = lambda n: A.empty(n, dtype=torch.float16, device=dev)  # noqa: E731
         ws['condenc'] = e(B, self.Mall, ws['Tz'])
         pong = [e(B, R, T), e(B, R, T)]
         ws['net'] = [pong[l & 1] for l in range(L + 1)]
         ws['skip'] = e(B, S, T)
         ws['gated'] = [e(B, R, T)] * L
-        if self.gate_f16x3:
-            ws['xp'] = h(2 * B * R * T)
-            ws['wp_all'] = A.empty(L, 2 * self.ks * R * 2 * R, dtype=torch.float16, device=dev)
-            ws['wp'] = [ws['wp_all'][l] for l in range(L)]
-            ws['gp'] = h(2 * B * R * T * (L if self.skip_f16x3 else 1))
-            if self.skip_f16x3:
-                ws['wskip'] = h(2 * L * R * S)
-                ws['wres'] = A.empty(L, 2 * R * R, dtype=torch.float16, device=dev)
-                if (self.x3_guard or self.bf16) and self.gbwd_f16x3 and S % 256 == 0 and Q % 256 == 0:
-                    ws['hp'], ws['hp2'] = h(2 * B * S * T), h(2 * B * S * T)
-                    ws['wskip0'], ws['wpost1'], ws['wpost2'] = h(2 * R * S), h(2 * S * S), h(2 * S * Q)
-            ws['wop_all'] = A.empty(L, 2 * R * (S + R), dtype=torch.float16, device=dev)
-            ws['wop'] = [ws['wop_all'][l] for l in range(L)]
+        self._plane_buffers(ws, False)
         ws['h1'] = e(B, S, T)
         ws['logits'] = e(B, Q, T)
         ws['nll'], ws['entropy'] = e(B, T), e(B, T)
@@ -508,7 +522,7 @@ class VQVAE:
         ws['labels'] = A.empty(B, T, dtype=torch.int32, device=dev)
         if self.enc == '64':
             ws['X'] = [e(B, F, t) for t in ws['Tl']]      # BN outputs of encoder layers 0..5
-            if self.x3_guard and not self.bf16 and F % 256 == 0:      # fp16x3 engine for layers 1..3 (_enc_x3_layers)
+            if self._enc_on_engine():      # fp16x3 engine for layers 1..3 (StepPlan.enc_x3)
                 ws['eplanes'] = A.empty(2 * B * F * ws['Tl'][0], dtype=torch.float16, device=dev)   # planes of one layer's operand
                 ws['ewp'] = A.empty(5, 2 * 5 * F * F, dtype=torch.float16, device=dev)
                 ws['enc_amax'] = torch.zeros(12, dtype=torch.int32, device=dev)
@@ -563,7 +577,7 @@ class VQVAE:
         Tin = ws['Tl'][0]
         # the long strided layers on the fp16x3 engine (space-to-depth planes): exact power-of-two scales from a
         # max-abs pass over this step's tensors; a non-finite value raises the step's range flag (-> fp32 repeat)
-        ex3 = ws['enc_x3'] = self._enc_x3_layers(ws)
+        ex3 = ws['enc_x3'] = self._plan(ws, ws is self._ws.get((B, T, True))).enc_x3      # (a training workspace: also under encode())
         if ex3:
             ea, es, flag = ws['enc_amax'], ws['enc_scale'], self.x3_flag
             K.f16x3_amax(P['enc_w'], ea[0:1], flag=flag)
@@ -576,7 +590,7 @@ class VQVAE:
             if i in ex3:
                 K.f16x3_amax(ws['X'][i - 1], ea[i:i + 1], flag=flag)
                 K.f16x3_update_scales(ea[i:i + 1], es[i:i + 1], target_exp=13, flag=flag)
-                epl = ws['esp'][i] if (save and 'esp' in ws) else ws['eplanes']
+                epl = ws['esp'][i] if (save and self.wg_planes) else ws['eplanes']
                 K.f16x3_split_activations(ws['X'][i - 1], epl, B, F, Tin, scale_dev=es[i:i + 1], mode=K.X3_S2D)
                 K.f16x3_strided_conv(xp=epl, wp=ws['ewp'][i - 1], out=ws['X'][i], save_r=ws['r'][i] if save else None,
                                      B=B, T=Tout, Cin=F, M=F, ks=5, pad_left=pl, bias=P['enc_b'][i], bn_scale=sc[i * F:(i + 1) * F],
@@ -598,17 +612,6 @@ class VQVAE:
                     scale=sc[6 * F:], shift=sh[6 * F:], B=B, T_in=Tz, T_out=Tz, M=D, C0=F, taps=[0])
         self._quantise(spk, ws)
 
-    def _enc_x3_layers(self, ws):
-        """Encoder layers (1..5) whose conv and input gradient run on the fp16x3 engine this step: the guarded engine is active,
-        channel blocks of 128 (the 256-column tiles over the flat (batch, time) rows may be partial: layers 4 and 5 have 1664 and
-        832 columns at B = 8).  Slots of ws['enc_scale'] / ws['enc_amax']: 0 the kernels, i = 1..5 the input of layer i (X[i-1]),
-        5 + i the gradient of layer i's conv output."""
-        if not (self.x3_guard and self._x3_active and not self.bf16 and self.enc == '64' and self.F % 256 == 0
-                and os.environ.get('VQW_ENC_X3', '1') != '0' and 'ewtp' in ws):      # (training workspaces only: the step's
-            return ()                                                                   #  range flag is read by train_step)
-        B, Tl = ws['B'], ws['Tl']
-        return tuple(i for i in (1, 2, 3, 4, 5) if B * Tl[i] >= 256 and Tl[i - 1] == 2 * Tl[i])
-
     def _wslab(self, ws):
         """Slab of the engine's weight-gradient kernels: the partial 256x256 tiles of ONE launch.  The launcher cuts K so that
         tiles x K splits <= the device's CU count (vqw_device_cus), hence one 256x256 fp32 tile per CU."""
@@ -621,7 +624,7 @@ class VQVAE:
     def _sconv_split(self, ws):
         """Scratch of the strided convs' split-K launches (encoder layers 3-5: 24..78 tiles of 240 K steps on 256 CUs): partial tiles
         of one launch (at most two rounds of 128-row blocks) and the tiles' ticket counters, which every launch leaves at zero."""
-        if os.environ.get('VQW_SCONV_SPLIT', '1') == '0':
+        if not self.sw.sconv_split:
             return {}
         if 'sslab' not in ws:
             cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
@@ -720,58 +723,82 @@ class VQVAE:
         finally:
             self._jitter_step = None
 
-    def _decode_train(self, x, ws, save=True):
-        """wavenet.py:24-100 -> ws['logits'] [B][Q][T], ws['labels']."""
-        self._decode_layers(ws, self._decode_prologue(x, ws, save))
-
-    def _decode_prologue(self, x, ws, save=True):
-        """Everything of the decoder's forward pass that does not depend on the encoder: inputs / labels, the preprocess conv
-        (wavenet.py:33-44), this step's guard scales and weight planes, the skip start (wavenet.py:53-54).  Returns the
-        plan of the step (which engine carries what, the guard slots) for _decode_layers."""
-        P, R, S, Q, L, B, T, Tz = self.P, self.R, self.S, self.Q, self.L, ws['B'], ws['T'], ws['Tz']
-        self._decode_input(x, ws)
-        net = ws['net']
+    def _step_plan(self, B, T, Tz, save, active):
+        """The StepPlan of one pass over a (B, T) problem with Tz condition frames: a pure function of the model's constants, self.sw and its arguments
+        (no tensors, no workspace, no launches).  save: a training pass on a training workspace (False: the score workspace); active: self._x3_active."""
+        sw, R, S, L = self.sw, self.R, self.S, self.L
         # fp16x3 needs whole 256-step tiles inside a batch row, 128-channel blocks and one condition frame per 32 steps;
         # |w| < 255 and |net| < 65504 (fp16 range of the leading planes) are assumed, not checked
         f16x3 = self.gate_f16x3 and T % 256 == 0 and R % 128 == 0 and (T // Tz) % 32 == 0
         f16x3_skip = f16x3 and self.skip_f16x3 and R % 256 == 0 and S % 256 == 0
         f16x3_out = f16x3 and self.out_f16x3 and R % 256 == 0 and S % 256 == 0    # the 1x1 skip + residual conv too; it hands the next layer its planes
-        if self.x3_all and not (f16x3_skip and self._x3_active):   # guarded / bf16 engine: all of it or none of it
-            if self._x3_active and (B, T) not in self._x3_warned:
-                self._x3_warned.add((B, T))
-                why = ('length %d is not a multiple of 256' % T if T % 256 else
-                       'residual / skip widths %d / %d are not multiples of 256' % (R, S) if (R % 256 or S % 256) else
-                       '%d samples per condition frame is not a multiple of 32' % (T // Tz))
-                print('[vqwave] batch %d x length %d runs on the fp32-MFMA engine (about half the speed of the %s engine): %s'
-                      % (B, T, 'bf16' if self.bf16 else 'fp16x3', why), file=sys.stderr, flush=True)
+        off = self.x3_all and not (f16x3_skip and active)   # guarded / bf16 engine: all of it or none of it
+        why = None if not (off and active) else ('length %d is not a multiple of 256' % T if T % 256 else
+                                                 'residual / skip widths %d / %d are not multiples of 256' % (R, S) if (R % 256 or S % 256) else
+                                                 '%d samples per condition frame is not a multiple of 32' % (T // Tz))
+        if off:
             f16x3 = f16x3_skip = f16x3_out = False
         # the skip contraction over all layers reads L*R/8 chunks of the gated planes through 32-bit offsets: at most 2 GiB
         # per plane and launch, so a large batch cuts it into groups of layers (batch 16 x 6656: 2 groups; one up to B*T = 139 k)
-        ngrp = max(1, int(os.environ.get('VQW_SKIP_GROUPS', '1')))          # (the variable forces groups at small shapes: tests)
+        ngrp = sw.skip_groups                               # (VQW_SKIP_GROUPS forces groups at small shapes: tests)
         while f16x3_skip and (L % ngrp or 2 * (L // ngrp) * R * B * T >= (1 << 31)):
             ngrp += 1
-        ws['skip_groups'] = ngrp if f16x3_skip else 0
-        Lg = L // ngrp
-        ws['x3_used'] = bool(f16x3_skip and self.x3_all)
-        md = self.x3_mode_fwd
+        full = f16x3_skip and self.x3_all                   # x3_used
         gd = self.x3_guard and f16x3_skip
-        sc = (lambda name, i=0: self.x3_scale[self.SL[name] + i:self.SL[name] + i + 1]) if gd else (lambda name, i=0: None)
-        am = (lambda name, i=0: self.x3_amax[self.SL[name] + i:self.SL[name] + i + 1]) if gd else (lambda name, i=0: None)
-        flag = self.x3_flag if gd else None
-        WS = 1.0 if gd else 256.0          # guarded: the weight scale lives on the device (exact max-abs of this step's weights)
-        head_x3 = ws['head_x3'] = bool((gd or (self.bf16 and f16x3_skip)) and self.head_x3 and 'hp' in ws and T % 32 == 0)
+        head_x3 = full and self.head_x3 and self._head_on_engine() and T % 32 == 0
         # layer l's input planes: kept per layer for the weight gradients where the skip contraction runs on the engine (then
         # every layer hands its successor planes), else one buffer (slot L: the planes of net[L], which nothing reads)
-        keep_xp = bool('xp_all' in ws and f16x3_skip)
-        ws['xp_kept'] = keep_xp
-        xpl = (lambda l: ws['xp_all'][l]) if keep_xp else (lambda l: ws['xp'])    # noqa: E731
+        keep_xp = save and self._keeps_layer_planes() and f16x3_skip
         # the guarded engine's gate backward forms tanh = gated / sigmoid itself: tanh is not stored (54 MB less per layer and gate
         # conv, 166 -> 157 us); VQW_SAVE_TANH=1 stores it
-        drop_th = ws['th_dropped'] = bool((gd or (self.bf16 and f16x3_skip)) and self.gbwd_f16x3 and os.environ.get('VQW_SAVE_TANH', '0') != '1')
-        # ... and then nothing reads the fp32 gated output either (gate backward and the 1x1 kernels' weight gradients take the
-        # gated planes): the gate conv does not write it (54 MB less per layer)
-        drop_g = ws['gated_dropped'] = bool(gd and keep_xp and save and drop_th and os.environ.get('VQW_WGRAD_BATCH', '1') != '0'
-                                            and os.environ.get('VQW_SAVE_GATED', '0') != '1')
+        drop_th = full and self.gbwd_f16x3 and not sw.save_tanh
+        # Gate backward and the gate convs' input gradient on the plane engine.  Guarded engine: the gradient planes carry
+        # device-side power-of-two scales (slots G and DP[l]); development ladder (VQW_GATE_F16X3=4,5): a fixed lift by 2^20
+        # (d(loss)/d(logits) is bounded by 1 / (B T); |dpre| < 0.06 assumed there, not checked).
+        dgrad_x3 = self.dgrad_f16x3 and T % 256 == 0 and R % 256 == 0 and (full or not self.x3_all)
+        gbwd_x3 = dgrad_x3 and self.gbwd_f16x3 and S % 256 == 0
+        wg_x3 = full and gbwd_x3 and T % 32 == 0 and sw.wgrad_x3
+        batched = wg_x3 and sw.wgrad_batch                  # several layers' weight gradients per launch (backward)
+        pp = batched and keep_xp                            # ... their p operands from the kept input planes and the gated planes
+        # ... and then nothing reads the fp32 gated output (gate backward and the 1x1 kernels' weight gradients take the gated
+        # planes): the gate conv does not write it (54 MB less per layer)
+        drop_g = gd and pp and drop_th and not sw.save_gated
+        # encoder layers (1..5) whose conv and input gradient run on the fp16x3 engine (training workspaces only: train_step reads the
+        # step's range flag): channel blocks of 128; the 256-column tiles over the flat (batch, time) rows may be partial (layers 4, 5: 1664,
+        # 832 columns at B = 8).  Slots of ws['enc_scale'] / ws['enc_amax']: 0 the kernels, i the input of layer i, 5 + i d(its conv output)
+        enc, Tl = self._enc_on_engine(), [T // (2 ** (i + 1)) for i in range(6)]
+        enc_x3 = tuple(i for i in (1, 2, 3, 4, 5) if B * Tl[i] >= 256 and Tl[i - 1] == 2 * Tl[i]) if (enc and active and save and sw.enc_x3) else ()
+        return StepPlan(      # (WS, GS: 1.0 where the scales live on the device; enc_wg3: head_x3 or wg_x3 = this step's backward makes the slab)
+            save=save, f16x3=f16x3, f16x3_out=f16x3_out, f16x3_skip=f16x3_skip, x3_used=full, gd=gd, calib=self.x3_guard and not active,
+            ngrp=ngrp, WS=1.0 if gd else 256.0, GS=1.0 if gd else float(2 ** 20), GSh=1.0 if self.x3_guard else float(2 ** 20),
+            head_x3=head_x3, keep_xp=keep_xp, drop_th=drop_th, drop_g=drop_g, dgrad_x3=dgrad_x3, gbwd_x3=gbwd_x3, wg_x3=wg_x3,
+            batched=batched, qp=batched and sw.wgrad_qp, pp=pp, gate_batch=sw.wg_gate_batch, res_batch=sw.wg_res_batch, enc_x3=enc_x3,
+            enc_wg3=(head_x3 or wg_x3) and enc and sw.enc_wgrad_x3, why=why)
+
+    def _plan(self, ws, save):          # _step_plan of a pass over ws, computed once per (save, _x3_active)
+        plans, key = ws.setdefault('_plans', {}), (save, self._x3_active)
+        if key not in plans:
+            plans[key] = self._step_plan(ws['B'], ws['T'], ws['Tz'], save, self._x3_active)
+        return plans[key]
+
+    def _slots(self, buf, on):
+        """The accessor of the guard slots of buf = x3_scale or x3_amax: sc('X', l), am('G') give the 1-element view of slot (name, i); None where the guards are off."""
+        return (lambda name, i=0: buf[self.SL[name] + i:self.SL[name] + i + 1]) if on else (lambda name, i=0: None)
+
+    def _decode_prologue(self, x, ws, save=True):
+        """Everything of the decoder's forward pass that does not depend on the encoder: inputs / labels, the preprocess conv
+        (wavenet.py:33-44), this step's guard scales and weight planes, the skip start (wavenet.py:53-54).  Leaves the plan of
+        the step as ws['plan'] (for _decode_layers and the backward pass) and returns it."""
+        P, R, S, Q, L, B, T = self.P, self.R, self.S, self.Q, self.L, ws['B'], ws['T']
+        plan = ws['plan'] = self._plan(ws, save)
+        if plan.why and (B, T) not in self._x3_warned:
+            self._x3_warned.add((B, T))
+            print('[vqwave] batch %d x length %d runs on the fp32-MFMA engine (about half the speed of the %s engine): %s'
+                  % (B, T, 'bf16' if self.bf16 else 'fp16x3', plan.why), file=sys.stderr, flush=True)
+        self._decode_input(x, ws)
+        net, gd, WS, ngrp, md = ws['net'], plan.gd, plan.WS, plan.ngrp, self.x3_mode_fwd
+        ws['skip_groups'], ws['x3_used'] = ngrp if plan.f16x3_skip else 0, plan.x3_used
+        sc, am, flag = self._slots(self.x3_scale, gd), self._slots(self.x3_amax, gd), self.x3_flag if gd else None
         if gd:
             K.f16x3_amax(P['gated_w'], am('WG'), flag=flag)
             K.f16x3_amax(P['out_w'], am('WO'), flag=flag)
@@ -779,7 +806,7 @@ class VQVAE:
             # weights and the first layer's input: exact scales (amax < 2^14 after scaling); the collectors restart
             K.f16x3_update_scales(self.x3_amax[:2], self.x3_scale[:2], target_exp=14, flag=flag)
             K.f16x3_update_scales(am('X', 0), sc('X', 0), target_exp=13, flag=flag)
-        if head_x3:      # the three kernels around the stack share one scale (bf16 planes need none)
+        if plan.head_x3:      # the three kernels around the stack share one scale (bf16 planes need none)
             if gd:
                 for name in ('skip0_w', 'post1_w', 'post2_w'):
                     K.f16x3_amax(P[name], am('WH'), flag=flag)
@@ -787,22 +814,21 @@ class VQVAE:
             K.f16x3_pack_weights(P['skip0_w'], ws['wskip0'], R, S, S, 1.0, scale_dev=sc('WH'), mode=md)
             K.f16x3_pack_weights(P['post1_w'], ws['wpost1'], S, S, S, 1.0, scale_dev=sc('WH'), mode=md)
             K.f16x3_pack_weights(P['post2_w'], ws['wpost2'], S, Q, Q, 1.0, scale_dev=sc('WH'), mode=md)
-            # wavenet.py:53-54 on the first layer's input planes
-            K.f16x3_split_activations(net[0], xpl(0), B, R, T, scale_dev=sc('X', 0), flag=flag, mode=md)
-            K.f16x3_out_conv(xp=xpl(0), Cin=R, wp=ws['wskip0'], bias=P['skip0_b'], net_out=ws['skip'], B=B, T=T, R=S, S=0,
+            # wavenet.py:53-54 on the first layer's input planes (ws['xp']: also xp_all[0])
+            K.f16x3_split_activations(net[0], ws['xp'], B, R, T, scale_dev=sc('X', 0), flag=flag, mode=md)
+            K.f16x3_out_conv(xp=ws['xp'], Cin=R, wp=ws['wskip0'], bias=P['skip0_b'], net_out=ws['skip'], B=B, T=T, R=S, S=0,
                              w_scale_inv=1.0, x_scale=sc('X', 0), w_scale=sc('WH'), mode=md)
         else:
             K.conv_gemm(x0=net[0], w=P['skip0_w'], bias=P['skip0_b'], out0=ws['skip'], B=B, T_in=T, T_out=T, M=S,
                         C0=R, taps=[0])                                                   # wavenet.py:53-54
-        if f16x3:      # this step's weights of all layers as fp16 planes, one launch per kind
+        if plan.f16x3:      # this step's weights of all layers as fp16 planes, one launch per kind
             K.f16x3_pack_gate_weights(P['gated_w'], ws['wp_all'], self.ks, R, 2 * R, WS, count=L, scale_dev=sc('WG'), mode=md)
-            if f16x3_skip:     # [L*R][S] skip kernels of all layers as one K = L*R operand (per layer group); the residual kernels per layer
-                K.f16x3_pack_weights(P['out_w'], ws['wskip'], Lg * R, S, S + R, WS, count=ngrp, scale_dev=sc('WO'), mode=md)
+            if plan.f16x3_skip:     # [L*R][S] skip kernels of all layers as one K = L*R operand (per layer group); the residual kernels per layer
+                K.f16x3_pack_weights(P['out_w'], ws['wskip'], L // ngrp * R, S, S + R, WS, count=ngrp, scale_dev=sc('WO'), mode=md)
                 K.f16x3_pack_weights(P['out_w'].view(-1)[S:], ws['wres'], R, R, S + R, WS, count=L, scale_dev=sc('WO'), mode=md)
-            elif f16x3_out:
+            elif plan.f16x3_out:
                 K.f16x3_pack_weights(P['out_w'], ws['wop_all'], R, S + R, S + R, WS, count=L, mode=md)
-        return dict(f16x3=f16x3, f16x3_skip=f16x3_skip, f16x3_out=f16x3_out, ngrp=ngrp, Lg=Lg, md=md, gd=gd, sc=sc, am=am, flag=flag, WS=WS,
-                    head_x3=head_x3, xpl=xpl, drop_th=drop_th, drop_g=drop_g, save=save)
+        return plan
 
     def _decode_input(self, x, ws):
         """The input stage: labels and net[0] = the preprocess conv of the shifted input (hook)."""
@@ -813,9 +839,11 @@ class VQVAE:
     def _decode_layers(self, ws, plan):
         """The condition projections, the residual stack and the convs behind it (wavenet.py:58-100; wavenet_ops.py:93-138)."""
         P, R, S, Q, L, B, T, Tz = self.P, self.R, self.S, self.Q, self.L, ws['B'], ws['T'], ws['Tz']
-        f16x3, f16x3_skip, f16x3_out, ngrp, Lg, md, gd = (plan[k] for k in ('f16x3', 'f16x3_skip', 'f16x3_out', 'ngrp', 'Lg', 'md', 'gd'))
-        sc, am, flag, WS, head_x3, xpl, drop_th, drop_g, save = (plan[k] for k in ('sc', 'am', 'flag', 'WS', 'head_x3', 'xpl', 'drop_th',
-                                                                                  'drop_g', 'save'))
+        f16x3, f16x3_skip, f16x3_out, ngrp, WS, head_x3, drop_th, drop_g, save = (
+            plan.f16x3, plan.f16x3_skip, plan.f16x3_out, plan.ngrp, plan.WS, plan.head_x3, plan.drop_th, plan.drop_g, plan.save)
+        Lg, md, flag = L // ngrp, self.x3_mode_fwd, self.x3_flag if plan.gd else None
+        sc, am = self._slots(self.x3_scale, plan.gd), self._slots(self.x3_amax, plan.gd)
+        xpl = (lambda l: ws['xp_all'][l]) if plan.keep_xp else (lambda l: ws['xp'])    # noqa: E731
         net = ws['net']
         if self.cond_proj:                                                                # all add_condition 1x1s
             K.cond_proj_fwd(ws['cond'], P['cond_w'], ws['condenc'], B=B, Cc=self.Cc, Mall=self.Mall, Tz=Tz)
@@ -1096,42 +1124,44 @@ class VQVAE:
         dlog, h1, skip = ws['logits'], ws['h1'], ws['skip']
         cbs = self.Mall * Tz
         dce = ws['dcondenc']
-        head_x3 = bool(ws.get('head_x3')) and bool(ws.get('x3_used')) and (self.x3_guard or self.bf16)
-        GSh = 1.0 if self.x3_guard else float(2 ** 20)      # the gradient planes' lift where no device scale carries it (bf16 engine)
+        plan, md = ws['plan'], self.x3_mode_bwd      # what the forward pass decided: nothing is derived again here
+        head_x3, dgrad_x3, gbwd_x3, wg_x3, batched, qp, pp, gd, calib, GS, GSh, WS, th_dropped, g_dropped = (
+            plan.head_x3, plan.dgrad_x3, plan.gbwd_x3, plan.wg_x3, plan.batched, plan.qp, plan.pp, plan.gd, plan.calib, plan.GS, plan.GSh, plan.WS, plan.drop_th, plan.drop_g)
+        sc, flag = self._slots(self.x3_scale, gd), self.x3_flag if gd else None
+        am = self._slots(self.x3_amax, gd or calib)      # (calib: the fp32 repeat of a step measures what the planes would have held)
+        if wg_x3 or head_x3:
+            self._wslab(ws)
         if head_x3:
-            # the convs around the stack on the fp16x3 engine (forward: _decode_train): d logits as planes with a fixed scale
+            # the convs around the stack on the fp16x3 engine (forward: _decode_layers): d logits as planes with a fixed scale
             # (|d logits| <= 1 / (B T)), each input gradient hands the next one its planes, the weight gradients split their fp32
             # operands in registers (p = relu of the forward tensor), bias and condition sums ride along
-            hsc = (lambda name: self.x3_scale[self.SL[name]:self.SL[name] + 1]) if self.x3_guard else (lambda name: None)      # noqa: E731
-            ham = (lambda name: self.x3_amax[self.SL[name]:self.SL[name] + 1]) if self.x3_guard else (lambda name: None)       # noqa: E731
-            mdh, dl, hflag = self.x3_mode_bwd, ws['dl_scale'], (self.x3_flag if self.x3_guard else None)
-            self._wslab(ws)
-            K.f16x3_pack_weights_t(P['post2_w'], ws['wpost2t'], Q, S, Q, Q, 0, 1.0, scale_dev=hsc('WH'), mode=mdh)
-            K.f16x3_pack_weights_t(P['post1_w'], ws['wpost1t'], S, S, S, S, 0, 1.0, scale_dev=hsc('WH'), mode=mdh)
-            K.f16x3_pack_weights_t(P['skip0_w'], ws['wskip0t'], S, R, S, S, 0, 1.0, scale_dev=hsc('WH'), mode=mdh)
+            dl = ws['dl_scale']
+            K.f16x3_pack_weights_t(P['post2_w'], ws['wpost2t'], Q, S, Q, Q, 0, 1.0, scale_dev=sc('WH'), mode=md)
+            K.f16x3_pack_weights_t(P['post1_w'], ws['wpost1t'], S, S, S, S, 0, 1.0, scale_dev=sc('WH'), mode=md)
+            K.f16x3_pack_weights_t(P['skip0_w'], ws['wskip0t'], S, R, S, S, 0, 1.0, scale_dev=sc('WH'), mode=md)
             dce.zero_()
             # ---- postprocess2 (wavenet.py:93-96)
-            K.f16x3_split_activations(dlog, ws['hp2'], B, Q, T, scale_dev=dl, mode=mdh)
+            K.f16x3_split_activations(dlog, ws['hp2'], B, Q, T, scale_dev=dl, mode=md)
             K.f16x3_wgrad(p=h1, p_relu=True, q0=dlog, dw=G['post2_w'], slab=ws['wslab'], B=B, T=T, Cp=S, Q0=Q, taps=[0],
-                          p_scale=hsc('H1'), q0_scale=dl, q_total=G['post2_b'], mode=mdh)
+                          p_scale=sc('H1'), q0_scale=dl, q_total=G['post2_b'], mode=md)
             K.f16x3_out_conv(epi=2, xp=ws['hp2'], Cin=Q, wp=ws['wpost2t'], net_out=h1, aux0=h1, net_out_planes=ws['hp'], B=B, T=T,
-                             R=S, S=0, w_scale_inv=1.0, x_scale=dl, w_scale=hsc('WH'), out_scale=hsc('DH'), out_amax=ham('DH'),
-                             flag=hflag, mode=self.x3_mode_head)   # h1 := d h1 (pre-relu)
+                             R=S, S=0, w_scale_inv=1.0, x_scale=dl, w_scale=sc('WH'), out_scale=sc('DH'), out_amax=am('DH'),
+                             flag=flag, mode=self.x3_mode_head)   # h1 := d h1 (pre-relu)
             # ---- postprocess1 (wavenet.py:79-88)
             K.f16x3_wgrad(p=skip, p_relu=True, q0=h1, dw=G['post1_w'], slab=ws['wslab'], B=B, T=T, Cp=S, Q0=S, taps=[0],
-                          p_scale=hsc('SK'), q0_scale=hsc('DH'), q_total=G['post1_b'], q_seg=dce.view(-1)[L * 2 * R * Tz:], seg_T=Tz,
-                          seg_bstride=cbs, mode=mdh)
+                          p_scale=sc('SK'), q0_scale=sc('DH'), q_total=G['post1_b'], q_seg=dce.view(-1)[L * 2 * R * Tz:], seg_T=Tz,
+                          seg_bstride=cbs, mode=md)
             K.f16x3_out_conv(epi=2, xp=ws['hp'], Cin=S, wp=ws['wpost1t'], net_out=skip, aux0=skip, net_out_planes=ws['gr'],
-                             planes_kc0=0, planes_KC=(S + R) // 8, plane_scale=GSh, B=B, T=T, R=S, S=0, w_scale_inv=1.0, x_scale=hsc('DH'),
-                             w_scale=hsc('WH'), out_scale=hsc('G'), out_amax=ham('G'), flag=hflag, mode=self.x3_mode_head)   # skip := d skip, and its planes
+                             planes_kc0=0, planes_KC=(S + R) // 8, plane_scale=GSh, B=B, T=T, R=S, S=0, w_scale_inv=1.0, x_scale=sc('DH'),
+                             w_scale=sc('WH'), out_scale=sc('G'), out_amax=am('G'), flag=flag, mode=self.x3_mode_head)   # skip := d skip, and its planes
         else:
             # ---- postprocess2 (wavenet.py:93-96)
             K.wgrad_gemm(p=h1, p_relu=True, q0=dlog, dw=G['post2_w'], B=B, T_q=T, T_p=T, Cp=S, Q0=Q, taps=[0])
             K.rowsum(dlog, total=G['post2_b'])
             K.conv_gemm(x0=dlog, w=self._tt('post2_w'), out0=h1, aux0=h1, B=B, T_in=T, T_out=T, M=S, C0=Q, taps=[0],
                         epilogue=K.EPI_MASK)                       # h1 := d h1 (pre-relu)
-            if self.x3_guard and not self._x3_active:              # fp32 repeat of a step: what the planes would have held
-                K.f16x3_amax(h1, self.x3_amax[self.SL['DH']:self.SL['DH'] + 1])
+            if calib:
+                K.f16x3_amax(h1, am('DH'))
             # ---- postprocess1 (wavenet.py:79-88)
             K.wgrad_gemm(p=skip, p_relu=True, q0=h1, dw=G['post1_w'], B=B, T_q=T, T_p=T, Cp=S, Q0=S, taps=[0])
             seg_p1 = A.empty(B, S, Tz, device=self.dev)
@@ -1150,28 +1180,6 @@ class VQVAE:
         main = torch.cuda.current_stream()
         side = self._side_stream() if self.overlap_wgrad else main
         dnet_ring, dpre_ring = ws['dnet_ring'], ws['dpre_ring']
-        # Gate backward and the gate convs' input gradient on the plane engine.  Guarded engine: the gradient planes carry
-        # device-side power-of-two scales (slots G and DP[l]); development ladder (VQW_GATE_F16X3=4,5): a fixed lift by 2^20
-        # (d(loss)/d(logits) is bounded by 1 / (B T); |dpre| < 0.06 assumed there, not checked).
-        dgrad_x3 = self.dgrad_f16x3 and T % 256 == 0 and R % 256 == 0
-        gbwd_x3 = dgrad_x3 and self.gbwd_f16x3 and S % 256 == 0
-        full = bool(ws.get('x3_used'))
-        gd = full and self.x3_guard
-        md = self.x3_mode_bwd
-        if self.x3_all and not full:
-            dgrad_x3 = gbwd_x3 = False
-        calib = self.x3_guard and not self._x3_active     # fp32 repeat of a step: measure what the planes would have held
-        sc = (lambda name, i=0: self.x3_scale[self.SL[name] + i:self.SL[name] + i + 1]) if gd else (lambda name, i=0: None)
-        am = (lambda name, i=0: self.x3_amax[self.SL[name] + i:self.SL[name] + i + 1]) if (gd or calib) else (lambda name, i=0: None)
-        flag = self.x3_flag if gd else None
-        GS = 1.0 if gd else float(2 ** 20)      # guarded: the gradient scales live on the device
-        WS = 1.0 if gd else 256.0
-        wg_x3 = full and gbwd_x3 and T % 32 == 0 and os.environ.get('VQW_WGRAD_X3', '1') != '0'
-        th_dropped = bool(ws.get('th_dropped'))
-        if th_dropped and not gbwd_x3:
-            raise RuntimeError('the forward pass did not store tanh but gate backward is not on the fp16x3 engine')
-        if wg_x3:
-            self._wslab(ws)
         if dgrad_x3:
             K.f16x3_pack_weights_t(P['gated_w'], ws['wdg'], ks * 2 * R, R, 2 * R, 2 * R, R * 2 * R, WS, count=L, scale_dev=sc('WG'), mode=md)
         if gbwd_x3:
@@ -1194,16 +1202,9 @@ class VQVAE:
         # A launch writes tiles x splits <= CUs partial 256x256 tiles to the slab whatever its batch size: per layer the slab
         # traffic (2 x 61 MB per single launch, 7.3 GB per step) falls with the batch size, dskip is read once per XCD instead
         # of once per layer, and 68 reductions become ~10.
-        batched = bool(wg_x3) and os.environ.get('VQW_WGRAD_BATCH', '1') != '0'
-        # ... and dpre is kept as the operand PLANES gate backward writes for the input gradient anyway: the gate kernels' weight
+        # ... and (qp) dpre is kept as the operand PLANES gate backward writes for the input gradient anyway: the gate kernels' weight
         # gradient reads its q operand from them (transposed LDS reads, vqw_f16x3_wgrad q_planes) and gate backward no longer
-        # writes fp32 dpre at all (109 of its 312 MB per layer)
-        qp = batched and os.environ.get('VQW_WGRAD_QP', '1') != '0'
-        # ... and so do p = the layer's input planes (kept per layer by the forward pass) and p = the gated planes of all layers
-        pp = batched and bool(ws.get('xp_kept'))
-        g_dropped = bool(ws.get('gated_dropped'))
-        if g_dropped and not (pp and gbwd_x3):
-            raise RuntimeError('the forward pass did not store the fp32 gated output but the backward pass needs it')
+        # writes fp32 dpre at all (109 of its 312 MB per layer); (pp) p = the layer's input planes and the gated planes likewise
         gated_p = (lambda i: dict(p_planes=ws['gp'], p_planes_kc0=i * (R // 8), p_planes_KC=L * (R // 8))) if pp else \
             (lambda i: dict(p=ws['gated'][i]))
         if batched and 'dnet_all' not in ws:
@@ -1215,8 +1216,6 @@ class VQVAE:
             else:
                 ws['dpre_all'] = [A.empty(B, 2 * R, T, device=self.dev) for _ in range(L)]
             ws['_poison'] += ws['dp_all' if qp else 'dpre_all']
-        gate_batch = max(1, min(K.WGRAD_MAX_BATCH, int(os.environ.get('VQW_WG_GATE_BATCH', '6'))))      # 36 tiles x 7 K splits = 252 blocks (tools/wg_batch_sweep.sh)
-        res_batch = max(1, min(K.WGRAD_MAX_BATCH, int(os.environ.get('VQW_WG_RES_BATCH', '29'))))
         pend_gate, pend_res = {False: [], True: []}, []
 
         def on_side(launch):           # weight gradients: nothing downstream waits for them
@@ -1299,11 +1298,11 @@ class VQVAE:
             if batched:
                 odd = any(((ks - 1 - j) * d) % 4 for j in range(ks))
                 pend_gate[odd].append(l)
-                if len(pend_gate[odd]) >= gate_batch:
+                if len(pend_gate[odd]) >= plan.gate_batch:      # 6: 36 tiles x 7 K splits = 252 blocks (tools/wg_batch_sweep.sh)
                     flush_gate(odd)
                 if not top:                  # layer l + 1 wrote dnet[l + 1] in the iteration before this one
                     pend_res.append(l)
-                    if len(pend_res) >= res_batch:
+                    if len(pend_res) >= plan.res_batch:
                         flush_res()
                 dnet = dnet_next
                 continue
@@ -1415,9 +1414,7 @@ class VQVAE:
         # layers 1..5 on the fp16x3 engine: the input gradient where the forward conv ran there (ws['enc_x3']), the weight
         # gradient (operands split in registers, bias sums riding along) whenever the decoder's ran there this step.  Scales:
         # exact powers of two from max-abs passes over THIS step's tensors (slots: _enc_x3_layers)
-        ex3 = ws.get('enc_x3', ())
-        wg3 = ('wslab' in ws and bool(ws.get('x3_used')) and self.x3_guard and not self.bf16 and F % 256 == 0
-               and os.environ.get('VQW_ENC_WGRAD_X3', '1') != '0')
+        ex3, wg3 = ws['plan'].enc_x3, ws['plan'].enc_wg3
         ea, es, flag = ws.get('enc_amax'), ws.get('enc_scale'), self.x3_flag
         if ex3:
             K.f16x3_pack_weights_t(P['enc_w'], ws['ewtp'], 5 * F, F, F, F, F * F, 1.0, count=5, scale_dev=es[0:1], mode=0)
@@ -1442,7 +1439,7 @@ class VQVAE:
                 ready.record(main)
             # both operands as planes where the forward conv ran on the engine (its space-to-depth input planes were kept):
             # tap j, e = j - pad_left, is parity block e & 1 at row offset e >> 1
-            w_planes = on_w and on_c and 'esp' in ws
+            w_planes = on_w and on_c and self.wg_planes
             if w_planes:     # (the split the input gradient needs anyway, into this layer's own buffer, BEFORE the weight gradient)
                 K.f16x3_split_activations(dX, ws['edp'][i], B, F, Ti, scale_dev=es[5 + i:6 + i], mode=0)
                 if side is not main:
@@ -1615,11 +1612,11 @@ class VQVAE:
                 self._x3_active = False
                 try:
                     self.x3_amax.zero_()
-                    ws = self._forward_step(x, spk, gs0)
+                    ws, am = self._forward_step(x, spk, gs0), self._slots(self.x3_amax, True)
                     for l in range(1, self.L):       # what the layer-input planes would have held (net[L] feeds nothing)
-                        K.f16x3_amax(ws['net'][l], self.x3_amax[self.SL['X'] + l:self.SL['X'] + l + 1])
-                    K.f16x3_amax(ws['skip'], self.x3_amax[self.SL['SK']:self.SL['SK'] + 1])
-                    K.f16x3_amax(ws['h1'], self.x3_amax[self.SL['H1']:self.SL['H1'] + 1])
+                        K.f16x3_amax(ws['net'][l], am('X', l))
+                    K.f16x3_amax(ws['skip'], am('SK'))
+                    K.f16x3_amax(ws['h1'], am('H1'))
                     if on_forward is not None:
                         on_forward(ws)
                     self.backward(x, spk, ws)
@@ -1642,8 +1639,8 @@ class VQVAE:
         EMA shadow or plane scale), x3_void is
         copied to pinned host memory, and the host looks at the copy of step k only after it has enqueued step k + 1.  If step k
         was flagged, it and step k + 1 (enqueued behind it, voided by the sticky guard) have changed nothing: the guard is
-        cleared, the step counter rewound, step k is repeated on the fp32 engine and step k + 1 is run again -- parameters after
-        every step are bit-identical to the immediate mode (tests/test_model_gpu.py::test_deferred_guard_matches_immediate).
+        cleared, the step counter rewound, step k is repeated on the fp32 engine and step k + 1 is run again -- the same steps are repeated as in the immediate mode
+        and the state agrees with it as closely as two runs of that mode do (tests/test_model_gpu.py::test_deferred_guard_matches_immediate: tolerances).
         Callers keep x / spk unchanged until the step is resolved (finish_steps(), or the next-but-one train_step) and call
         finish_steps() before reading what a step left behind (losses, gradients, parameters; state_dict() / encode() do)."""
         t_host = time.perf_counter()
