@@ -592,7 +592,11 @@ typedef struct vqw_f16x3_out_desc {
     int32_t mode;          /* VQW_X3_* bits                                                                          */
     /* epi 2 -- the 1x1 convs around the stack (wavenet.py:53-54, 80-96) and their input gradients; S = 0, R rows, fp16x3 mode:
      *   net_out = mask * (net_in + W x + bias + cond[b][m][t / (T / cond_T)]),  mask = (aux0 > 0) or 1 (aux0 NULL); net_in, bias,
-     *   cond optional; net_out may alias net_in and aux0; net_out_planes get net_out, or relu(net_out) with flags bit 0        */
+     *   cond optional; net_out may alias net_in and aux0; net_out_planes get net_out, or relu(net_out) with flags bit 0.
+     *   Aliasing means THE SAME tensor (equal base address), for epi 0 too (net_out = net_in, skip in place): the epilogues
+     *   request the operands of a later group of elements before an earlier group is stored; every element is read and
+     *   written by the same lane within one group and groups touch disjoint elements, so in-place calls give the bits of
+     *   out-of-place calls.  Buffers that overlap at an offset are not supported (they never were: blocks run in any order). */
     const float* cond;
     int64_t cond_bstride;
     int32_t cond_T;

@@ -20,6 +20,8 @@
 // kernel: the fp32 operands themselves, split in registers (wgrad_f16x3_kernel).
 #include <string.h>
 
+#include <type_traits>
+
 #include "vqw_common.h"
 
 namespace {
@@ -538,6 +540,68 @@ __device__ __forceinline__ void f16x3_mainloop(f32x16 (&acc)[MR][2], char* smem,
     }
 }
 
+// Epilogue request depth.  An epilogue works through NG groups -- four channels x two column tiles per lane -- and each
+// group reads operands from memory (old value, bias, condition, mask, saved activations) before it stores.  Outputs may alias
+// inputs by contract, so the compiler keeps every load behind the stores written before it; loads and stores share vmcnt and
+// retire in issue order, so a wave that loads, computes and stores one group at a time has one group of requests in flight and
+// pays a memory round trip plus a store acknowledge per group.  Here the operands of group g + DEPTH are requested BEFORE group g is
+// computed and stored: the wait for group g + 1 then leaves the stores of g and the loads of g + 2 outstanding.
+// Aliasing stays legal: every element is read and written by the same lane in the same group, and groups touch disjoint
+// elements, so a load hoisted over the stores of earlier groups never reads an element one of those stores writes.
+// The prefetch buffers are named values rotated by hand -- never an array indexed by the group -- and the loop unrolls fully.
+template <int NG, int DEPTH, typename Ops, typename Req, typename Fin>
+__device__ __forceinline__ void x3_epilogue_pipeline(Req&& request, Fin&& finish) {
+    static_assert(NG % 2 == 0 && DEPTH >= 0 && DEPTH <= 2, "two named buffers");
+    Ops p0, p1;
+    request(0, p0);
+    if constexpr (DEPTH == 0) {      // (no prefetch: a group is requested, computed and stored before the next one)
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            if (g > 0) request(g, p0);
+            finish(g, p0);
+        }
+    } else if constexpr (DEPTH == 2) {
+        request(1, p1);
+#pragma unroll
+        for (int g = 0; g < NG; g += 2) {
+            { const Ops c = p0; if (g + 2 < NG) request(g + 2, p0); finish(g, c); }
+                { const Ops c = p1; if (g + 3 < NG) request(g + 3, p1); finish(g + 1, c); }
+            }
+    } else {
+#pragma unroll
+        for (int g = 0; g < NG; g += 2) {
+            request(g + 1, p1);
+            finish(g, p0);
+                if (g + 2 < NG) request(g + 2, p0);
+            finish(g + 1, p1);
+            }
+    }
+}
+// An optional operand that is absent reads a valid dummy address and is then taken as +0: as a bit mask, not as a select on the
+// block-uniform "is it there" condition -- the optimiser turns such a select into a branch around the load, and the merge behind
+// the branch waits for the load right where it was issued (vmcnt(0) after every single load of a prefetched group).
+__device__ __forceinline__ unsigned x3_present(bool present) {
+    unsigned m = __builtin_amdgcn_readfirstlane(present ? 0xffffffffu : 0u);
+    asm volatile("" : "+s"(m));      // (opaque: not to be recognised as a select again)
+    return m;
+}
+__device__ __forceinline__ float x3_masked(float v, unsigned m) { return __uint_as_float(__float_as_uint(v) & m); }
+__device__ __forceinline__ int x3_masked(int i, unsigned m) { return (int)((unsigned)i & m); }      // (the index of an absent operand: 0)
+// The max-abs / finiteness folds of a group are pinned where they are written: left alone, the optimiser sinks them into the
+// conditional guard_report at the end of the kernel and keeps every value of the whole epilogue alive until then (spills).
+__device__ __forceinline__ void x3_pin_guard(float& gmax, bool& gbad) {
+    int gb_i = (int)gbad;
+    asm volatile("" : "+v"(gmax), "+v"(gb_i));
+    gbad = gb_i != 0;
+}
+#ifndef VQW_X3_EPI_DEPTH
+#define VQW_X3_EPI_DEPTH 2
+#endif
+#ifndef VQW_X3_GATE_EPI_DEPTH
+#define VQW_X3_GATE_EPI_DEPTH 0      // the gate conv's 24 operand registers per group: depth 1 and 2 spill (40-240 bytes of scratch per lane)
+#endif
+constexpr int EPI_DEPTH = VQW_X3_EPI_DEPTH;
+
 // Four consecutive channels (rows 4 lhi .. 4 lhi + 3 of chunk kc) of one (batch, time) row as the lane's 8-byte
 // half of the 16-byte plane entries: the 64 lanes of a wave cover 32 rows x 16 bytes = 512 contiguous bytes per plane.
 template <bool BF>
@@ -579,30 +643,45 @@ __global__ __launch_bounds__(256, MR == 8 ? 1 : 2) void gate_f16x3_kernel(const 
     // ---- epilogue: + bias + upsampled condition (add_condition, wavenet_ops.py:93-101), tanh(filter) * sigmoid(gate).
     // With one block per CU nothing overlaps it, so it is kept lean: one 64-bit row offset per four channels, 32-bit
     // offsets inside, v_rcp_f32 instead of IEEE divisions (1 ulp; the quotients feed tanh/sigmoid values in [-1, 1]).
+    // Groups go through x3_epilogue_pipeline like the other epilogues', but at depth 0 (VQW_X3_GATE_EPI_DEPTH): its operands
+    // are L2 hits and prefetching them costs more registers than the kernel has.
     const bool hb = d.bias != nullptr, hc = d.cond != nullptr;
     const float* bp = hb ? d.bias : reinterpret_cast<const float*>(d.wp);      // absent operands read a valid dummy address
     const float* cb = hc ? d.cond + (size_t)b * d.cond_bstride : reinterpret_cast<const float*>(d.wp);
     const int tcol = t0 + 64 * wv + l31;
     const int tz0 = (t0 + 64 * wv) / a.ratio, tz1 = (t0 + 64 * wv + 32) / a.ratio;   // 32 | ratio: one frame per tile row
-    const bool s0 = d.save0 != nullptr, s1 = d.save1 != nullptr;
     const float winv = inv_scales(d.w_scale_inv, d.x_scale, d.w_scale);
-#pragma unroll
-    for (int i = 0; i < MR / 2; ++i)
-#pragma unroll
-        for (int v4 = 0; v4 < 4; ++v4) {
+    const unsigned mb = x3_present(hb), mc = x3_present(hc);
+    struct Ops { float bf[4], bg[4], f0[4], f1[4], g0[4], g1[4]; };
+    // STEP: the outputs the training step asks for (sigmoid + gated planes) are known at compile time -- no branch around any
+    // store; every other combination takes the same body with its block-uniform conditions tested at run time
+    auto epilogue = [&](auto step_c) {
+        constexpr bool STEP = decltype(step_c)::value;
+        const bool s0 = STEP ? false : d.save0 != nullptr, s1 = STEP ? true : d.save1 != nullptr;
+        const bool w0 = STEP ? false : d.out0 != nullptr, wp_ = STEP ? true : d.out_planes != nullptr;
+        auto request = [&](int g, Ops& o) {
+            const int i = g >> 2, v4 = g & 3;
             const int c0 = HH * mt + 32 * i + 8 * v4 + 4 * lhi;          // first of this lane's four channels
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                o.bf[e] = bp[x3_masked(c0 + e, mb)]; o.bg[e] = bp[x3_masked(R + c0 + e, mb)];
+                const int cf = (c0 + e) * d.cond_T, cg = (R + c0 + e) * d.cond_T;
+                o.f0[e] = cb[x3_masked(cf + tz0, mc)]; o.f1[e] = cb[x3_masked(cf + tz1, mc)];
+                o.g0[e] = cb[x3_masked(cg + tz0, mc)]; o.g1[e] = cb[x3_masked(cg + tz1, mc)];
+            }
+        };
+        auto finish = [&](int g, const Ops& o) {
+            const int i = g >> 2, v4 = g & 3;
+            const int c0 = HH * mt + 32 * i + 8 * v4 + 4 * lhi;
             float addf[4][2], addg[4][2];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float bfv = bp[hb ? c0 + e : 0], bgv = bp[hb ? R + c0 + e : 0];
-                const int cf = (c0 + e) * d.cond_T, cg = (R + c0 + e) * d.cond_T;
-                const float f0 = cb[hc ? cf + tz0 : 0], f1 = cb[hc ? cf + tz1 : 0];
-                const float g0 = cb[hc ? cg + tz0 : 0], g1 = cb[hc ? cg + tz1 : 0];
-                addf[e][0] = (hb ? bfv : 0.0f) + (hc ? f0 : 0.0f); addf[e][1] = (hb ? bfv : 0.0f) + (hc ? f1 : 0.0f);
-                addg[e][0] = (hb ? bgv : 0.0f) + (hc ? g0 : 0.0f); addg[e][1] = (hb ? bgv : 0.0f) + (hc ? g1 : 0.0f);
+                const float bfv = o.bf[e], bgv = o.bg[e], f0 = o.f0[e], f1 = o.f1[e], g0 = o.g0[e], g1 = o.g1[e];
+                addf[e][0] = x3_masked(bfv, mb) + x3_masked(f0, mc); addf[e][1] = x3_masked(bfv, mb) + x3_masked(f1, mc);
+                addg[e][0] = x3_masked(bgv, mb) + x3_masked(g0, mc); addg[e][1] = x3_masked(bgv, mb) + x3_masked(g1, mc);
             }
             const size_t off = ((size_t)b * R + c0) * T + tcol;
-            float* po = (d.out0 ? d.out0 : d.save1) + off;
+            float* po = (w0 ? d.out0 : d.save1) + off;
             float* p0 = s0 ? d.save0 + off : po;
             float* p1 = s1 ? d.save1 + off : po;
             float gq[2][4];
@@ -614,19 +693,26 @@ __global__ __launch_bounds__(256, MR == 8 ? 1 : 2) void gate_f16x3_kernel(const 
                     const float xg = acc[i + MR / 2][j][v4 * 4 + e] * winv + addg[e][j];
                     const float th = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * xf) + 1.0f);
                     const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-xg));
-                    const int o = e * T + 32 * j;
+                    const int o_ = e * T + 32 * j;
                     gq[j][e] = th * sg;
-                    if (s0) p0[o] = th;
-                    if (s1) p1[o] = sg;
-                    if (d.out0) po[o] = gq[j][e];        // (optional where every reader takes the planes: 54 MB less per layer)
+                    // (the fp32 product itself goes into the planes, also where no fp32 copy of it is stored: unpinned, a body that
+                    // only writes planes rounds th * sg to fp16 in one step -- v_fma_mixlo_f16 -- and the plane bits change)
+                    if constexpr (STEP) asm volatile("" : "+v"(gq[j][e]));
+                    if (s0) p0[o_] = th;
+                    if (s1) p1[o_] = sg;
+                    if (w0) po[o_] = gq[j][e];        // (optional where every reader takes the planes: 54 MB less per layer)
                 }
-            if (d.out_planes) {
+            if (wp_) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
                     store_plane_quad<BF>(d.out_planes, d.out_planes_KC > 0 ? d.out_planes_KC : R / 8, a.NB, d.out_planes_kc0 + (HH / 8) * mt + 4 * i + v4,
                                      n0 + 64 * wv + 32 * j + l31, lhi, gq[j]);
             }
-        }
+        };
+        x3_epilogue_pipeline<MR * 2, VQW_X3_GATE_EPI_DEPTH, Ops>(request, finish);
+    };
+    if (!d.out0 && !d.save0 && d.save1 && d.out_planes) epilogue(std::true_type{});
+    else epilogue(std::false_type{});
 }
 
 // The layer's 1x1 skip + residual conv (wavenet_ops.py:132-136, wavenet.py:72-73) on the gated planes:
@@ -657,24 +743,48 @@ __global__ __launch_bounds__(256, MR == 8 ? 1 : 2) void out_f16x3_kernel(const O
     const int tcol = t0 + 64 * wv + l31;
     const float winv = inv_scales(d.w_scale_inv, d.x_scale, d.w_scale);
     const float ps = (d.plane_scale > 0.0f ? d.plane_scale : 1.0f) * dev_scale(d.out_scale);
-    float gmax = 0.0f;
-    bool gbad = false;
+    const bool hin = is_skip || d.net_in != nullptr;
+    const unsigned mb = x3_present(hb), min_ = x3_present(hin);
+    // (chosen once, not per group: a block reads and writes either skip rows or residual rows)
+    const float* in_base = is_skip ? d.skip : (d.net_in ? d.net_in : d.net_out);
+    float* out_base = is_skip ? d.skip : d.net_out;
+    const int nrows = is_skip ? S : R, mrow0 = is_skip ? 0 : S;
+    // net_out may be net_in (and skip is updated in place): the old values of group g + 2 are requested before group g is stored,
+    // which is legal because a lane reads and writes the same elements within one group and groups are disjoint (x3_epilogue_pipeline)
+    struct Ops { float bq[4], old[2][4]; };
+    // PL: this block writes planes (and reports to the range guard) -- block-uniform, decided once in front of the epilogue
+    auto epilogue = [&](auto pl_c) {
+        constexpr bool PL = decltype(pl_c)::value;
+        float gmax = 0.0f;
+        bool gbad = false;
+        auto offset = [&](int g, int& m0) {
+            const int i = g >> 2, v4 = g & 3;
+            m0 = mt * HB + 32 * i + 8 * v4 + 4 * lhi;      // first of this lane's four rows
+            return ((size_t)b * nrows + (m0 - mrow0)) * T + tcol;
+        };
+        auto request = [&](int g, Ops& o) {
+            int m0;
+            const size_t off = offset(g, m0);
+            const float* pin = in_base + off;
 #pragma unroll
-    for (int i = 0; i < MR; ++i)
+            for (int e = 0; e < 4; ++e) {
+                o.bq[e] = bp[x3_masked(m0 + e, mb)];
 #pragma unroll
-        for (int v4 = 0; v4 < 4; ++v4) {
-            const int m0 = mt * HB + 32 * i + 8 * v4 + 4 * lhi;      // first of this lane's four rows
-            const size_t off = is_skip ? ((size_t)b * S + m0) * T + tcol : ((size_t)b * R + (m0 - S)) * T + tcol;
-            const bool hin = is_skip || d.net_in != nullptr;
-            const float* pin = is_skip ? d.skip + off : (d.net_in ? d.net_in + off : d.net_out + off);
-            float* pout = is_skip ? d.skip + off : d.net_out + off;
+                for (int j = 0; j < 2; ++j) o.old[j][e] = pin[e * T + 32 * j];
+            }
+        };
+        auto finish = [&](int g, const Ops& o) {
+            const int i = g >> 2, v4 = g & 3;
+            int m0;
+            const size_t off = offset(g, m0);
+            float* pout = out_base + off;
             float bq[4], old[2][4], nq[2][4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float bv = bp[hb ? m0 + e : 0];
-                bq[e] = hb ? bv : 0.0f;
+                const float bv = o.bq[e];
+                bq[e] = x3_masked(bv, mb);
 #pragma unroll
-                for (int j = 0; j < 2; ++j) { const float ov = pin[e * T + 32 * j]; old[j][e] = hin ? ov : 0.0f; }
+                for (int j = 0; j < 2; ++j) { const float ov = o.old[j][e]; old[j][e] = x3_masked(ov, min_); }
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -683,7 +793,7 @@ __global__ __launch_bounds__(256, MR == 8 ? 1 : 2) void out_f16x3_kernel(const O
                     nq[j][e] = old[j][e] + (acc[i][j][v4 * 4 + e] * winv + bq[e]);
                     pout[e * T + 32 * j] = nq[j][e];
                 }
-            if (!is_skip && d.net_out_planes) {
+            if constexpr (PL) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
 #pragma unroll
@@ -691,9 +801,14 @@ __global__ __launch_bounds__(256, MR == 8 ? 1 : 2) void out_f16x3_kernel(const O
                     store_plane_quad<BF>(d.net_out_planes, d.planes_KC > 0 ? d.planes_KC : R / 8, a.NB, d.planes_kc0 + (m0 - S) / 8,
                                      n0 + 64 * wv + 32 * j + l31, lhi, nq[j], ps);
                 }
+                x3_pin_guard(gmax, gbad);
             }
-        }
-    if (!is_skip && d.net_out_planes) guard_report(gmax, gbad, ps, d.out_amax, d.flag);
+        };
+        x3_epilogue_pipeline<MR * 4, EPI_DEPTH, Ops>(request, finish);
+        if constexpr (PL) guard_report(gmax, gbad, ps, d.out_amax, d.flag);
+    };
+    if (!is_skip && d.net_out_planes) epilogue(std::true_type{});
+    else epilogue(std::false_type{});
 }
 
 // The 1x1 convs around the residual stack (wavenet.py:53-54, 72, 80-96) and their input gradients, epi = 2:
@@ -729,30 +844,47 @@ __global__ __launch_bounds__(256, MR == 8 ? 1 : 2) void head_f16x3_kernel(const 
     const float winv = inv_scales(d.w_scale_inv, d.x_scale, d.w_scale);
     const float ps = (d.plane_scale > 0.0f ? d.plane_scale : 1.0f) * dev_scale(d.out_scale);
     const int PKC = d.planes_KC > 0 ? d.planes_KC : M / 8;
-    float gmax = 0.0f;
-    bool gbad = false;
-#pragma unroll
-    for (int i = 0; i < MR; ++i)
-#pragma unroll
-        for (int v4 = 0; v4 < 4; ++v4) {
+    const unsigned mb = x3_present(hb), mc = x3_present(hc), min_ = x3_present(hin), mnm = x3_present(!hm);
+    const float* in_base = hin ? d.net_in : d.net_out;        // absent operands read net_out's own (valid) addresses
+    const float* mask_base = hm ? d.aux0 : d.net_out;
+    // net_out may be net_in and / or aux0: a lane reads its elements of group g + 2 before group g is stored, and groups are
+    // disjoint (x3_epilogue_pipeline)
+    struct Ops { float bv[4], c0[4], c1[4], old[2][4], mv[2][4]; };
+    auto epilogue = [&](auto pl_c) {      // PL: planes (and the range guard) are written
+        constexpr bool PL = decltype(pl_c)::value;
+        float gmax = 0.0f;
+        bool gbad = false;
+        auto request = [&](int g, Ops& o) {
+            const int i = g >> 2, v4 = g & 3;
             const int m0 = mt * HB + 32 * i + 8 * v4 + 4 * lhi;      // first of this lane's four rows
             const size_t off = ((size_t)b * M + m0) * T + tcol;
-            const float* pin = hin ? d.net_in + off : d.net_out + off;
-            const float* pm = hm ? d.aux0 + off : d.net_out + off;
+            const float* pin = in_base + off;
+            const float* pm = mask_base + off;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                o.bv[e] = bp[x3_masked(m0 + e, mb)];
+                const int cr = (m0 + e) * d.cond_T;
+                o.c0[e] = cb[x3_masked(cr + tz[0], mc)]; o.c1[e] = cb[x3_masked(cr + tz[1], mc)];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) { o.old[j][e] = pin[e * T + 32 * j]; o.mv[j][e] = pm[e * T + 32 * j]; }
+            }
+        };
+        auto finish = [&](int g, const Ops& o) {
+            const int i = g >> 2, v4 = g & 3;
+            const int m0 = mt * HB + 32 * i + 8 * v4 + 4 * lhi;
+            const size_t off = ((size_t)b * M + m0) * T + tcol;
             float* pout = d.net_out + off;
             float add[4][2], old[2][4], mk[2][4], nq[2][4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float bv = bp[hb ? m0 + e : 0];
-                const int cr = (m0 + e) * d.cond_T;
-                const float c0 = cb[hc ? cr + tz[0] : 0], c1 = cb[hc ? cr + tz[1] : 0];
-                add[e][0] = (hb ? bv : 0.0f) + (hc ? c0 : 0.0f);
-                add[e][1] = (hb ? bv : 0.0f) + (hc ? c1 : 0.0f);
+                const float bv = o.bv[e], c0 = o.c0[e], c1 = o.c1[e];
+                add[e][0] = x3_masked(bv, mb) + x3_masked(c0, mc);
+                add[e][1] = x3_masked(bv, mb) + x3_masked(c1, mc);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    const float ov = pin[e * T + 32 * j], mv = pm[e * T + 32 * j];
-                    old[j][e] = hin ? ov : 0.0f;
-                    mk[j][e] = (!hm || mv > 0.0f) ? 1.0f : 0.0f;
+                    const float ov = o.old[j][e], mv = o.mv[j][e];
+                    old[j][e] = x3_masked(ov, min_);
+                    mk[j][e] = x3_masked(1.0f, (mv > 0.0f ? 0xffffffffu : 0u) | mnm);
                 }
             }
 #pragma unroll
@@ -762,20 +894,29 @@ __global__ __launch_bounds__(256, MR == 8 ? 1 : 2) void head_f16x3_kernel(const 
                     nq[j][e] = mk[j][e] * (old[j][e] + (acc[i][j][v4 * 4 + e] * winv + add[e][j]));
                     pout[e * T + 32 * j] = nq[j][e];
                 }
-            if (d.net_out_planes) {
+            if constexpr (PL) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
+                        // (the stored fp32 value itself goes into the planes: unpinned, the body without relu contracts the product
+                        // above into the fp16 conversions and the plane bits change)
+                        asm volatile("" : "+v"(nq[j][e]));
                         gbad |= !(fabsf(nq[j][e]) <= 3.0e38f);
                         if (relu_planes) nq[j][e] = fmaxf(nq[j][e], 0.0f);
                         gmax = fmaxf(gmax, fabsf(nq[j][e]));
                     }
                     store_plane_quad<BF>(d.net_out_planes, PKC, a.NB, d.planes_kc0 + m0 / 8, n0 + 64 * wv + 32 * j + l31, lhi, nq[j], ps);
                 }
+                x3_pin_guard(gmax, gbad);
             }
-        }
-    if (d.net_out_planes) guard_report(gmax, gbad, ps, d.out_amax, d.flag);
+        };
+        // depth 1: a group has 28 operand registers (the 128-row bf16 instantiation has none to spare: it keeps the plain order)
+        x3_epilogue_pipeline<MR * 4, (MR == 4 && BF) ? 0 : 1, Ops>(request, finish);
+        if constexpr (PL) guard_report(gmax, gbad, ps, d.out_amax, d.flag);
+    };
+    if (d.net_out_planes) epilogue(std::true_type{});
+    else epilogue(std::false_type{});
 }
 
 // Gate backward (the transpose of gated_cnn's tanh * sigmoid, wavenet_ops.py:112-113, behind the transposed 1x1 convs):
@@ -803,50 +944,76 @@ __global__ __launch_bounds__(256, MR == 8 ? 1 : 2) void gate_bwd_f16x3_kernel(co
     const int tcol = t0 + 64 * wv + l31;
     const float ps = (d.plane_scale > 0.0f ? d.plane_scale : 1.0f) * dev_scale(d.out_scale);
     const float winv = inv_scales(d.w_scale_inv, d.x_scale, d.w_scale);
-    float gmax = 0.0f;
-    bool gbad = false;
     const int PKC = d.planes_KC > 0 ? d.planes_KC : 2 * R / 8;
-#pragma unroll
-    for (int i = 0; i < MR; ++i)
-#pragma unroll
-        for (int v4 = 0; v4 < 4; ++v4) {
+    const int AKC = d.aux0_KC > 0 ? d.aux0_KC : R / 8;
+    // The saved activations of group g + 2 are requested before group g is stored (x3_epilogue_pipeline); aux0 as planes: this
+    // lane's four channels of one (batch, time) row = 8 bytes of the row's plane entry (store_plane_quad's layout), kept as
+    // loaded and decoded when the group is computed.
+    struct Ops { float th[2][4], sg[2][4]; uint2 h1[2], h2[2]; };
+    // STEP: what the training step asks for -- planes only, no fp32 dpre -- known at compile time: no branch around any store.
+    // Every other combination takes the same body with its block-uniform conditions tested at run time.
+    auto epilogue = [&](auto step_c) {
+        constexpr bool STEP = decltype(step_c)::value;
+        const bool w32 = STEP ? false : d.net_out != nullptr, wpl = STEP ? true : d.net_out_planes != nullptr;
+        float gmax = 0.0f;
+        bool gbad = false;
+        auto request = [&](int g, Ops& o) {
+            const int i = g >> 2, v4 = g & 3;
             const int c0 = mt * HB + 32 * i + 8 * v4 + 4 * lhi;      // first of this lane's four gated channels
             const size_t offa = ((size_t)b * R + c0) * T + tcol;      // saved tanh / sigmoid [B][R][T]
-            const size_t offo = ((size_t)b * 2 * R + c0) * T + tcol;  // dpre [B][2R][T]: filter rows, then gate rows
-            const float* pt = d.aux0 + offa;
             const float* pg = d.aux1 + offa;
+            if constexpr (FG == 2) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const char* pe = reinterpret_cast<const char*>(d.aux0) + ((size_t)(d.aux0_kc0 + c0 / 8) * a.NB + n0 + 64 * wv + 32 * j + l31) * 16 + lhi * 8;
+                    o.h1[j] = *reinterpret_cast<const uint2*>(pe);
+                    if constexpr (!BF) o.h2[j] = *reinterpret_cast<const uint2*>(pe + (size_t)AKC * a.NB * 16);
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) o.sg[j][e] = pg[e * T + 32 * j];
+            } else {
+                const float* pt = d.aux0 + offa;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) { o.th[j][e] = pt[e * T + 32 * j]; o.sg[j][e] = pg[e * T + 32 * j]; }
+            }
+        };
+        auto finish = [&](int g, const Ops& o) {
+            const int i = g >> 2, v4 = g & 3;
+            const int c0 = mt * HB + 32 * i + 8 * v4 + 4 * lhi;
+            const size_t offo = ((size_t)b * 2 * R + c0) * T + tcol;  // dpre [B][2R][T]: filter rows, then gate rows
             float* pf = d.net_out + offo;
             float* pq = pf + (size_t)R * T;
             float th[2][4], sg[2][4], qf[2][4], qg[2][4];
             if constexpr (FG == 2) {
-                // this lane's four channels of one (batch, time) row = 8 bytes of the row's plane entry (store_plane_quad's layout)
-                const int AKC = d.aux0_KC > 0 ? d.aux0_KC : R / 8;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    const char* pe = reinterpret_cast<const char*>(d.aux0) + ((size_t)(d.aux0_kc0 + c0 / 8) * a.NB + n0 + 64 * wv + 32 * j + l31) * 16 + lhi * 8;
-                    const uint2 h1 = *reinterpret_cast<const uint2*>(pe);
+                    const uint2 h1 = o.h1[j];
                     // (no local arrays here: indexed ones kept the 256-row instantiation from unrolling and put the accumulators in scratch)
                     if constexpr (BF) {
                         th[j][0] = __uint_as_float(h1.x << 16); th[j][1] = __uint_as_float(h1.x & 0xffff0000u);
                         th[j][2] = __uint_as_float(h1.y << 16); th[j][3] = __uint_as_float(h1.y & 0xffff0000u);
                     } else {
-                        const uint2 h2 = *reinterpret_cast<const uint2*>(pe + (size_t)AKC * a.NB * 16);
+                        const uint2 h2 = o.h2[j];
                         auto lo16 = [](unsigned w) { return (float)__builtin_bit_cast(_Float16, (u16)(w & 0xffffu)); };
                         auto hi16 = [](unsigned w) { return (float)__builtin_bit_cast(_Float16, (u16)(w >> 16)); };
                         th[j][0] = lo16(h1.x) + lo16(h2.x); th[j][1] = hi16(h1.x) + hi16(h2.x);
                         th[j][2] = lo16(h1.y) + lo16(h2.y); th[j][3] = hi16(h1.y) + hi16(h2.y);
                     }
                 }
+            } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) sg[j][e] = pg[e * T + 32 * j];
-            } else {
+                    for (int j = 0; j < 2; ++j) th[j][e] = o.th[j][e];
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) { th[j][e] = pt[e * T + 32 * j]; sg[j][e] = pg[e * T + 32 * j]; }
-            }
+                for (int j = 0; j < 2; ++j) sg[j][e] = o.sg[j][e];
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -865,13 +1032,16 @@ __global__ __launch_bounds__(256, MR == 8 ? 1 : 2) void gate_bwd_f16x3_kernel(co
                         qf[j][e] = dg * sg[j][e] * (1.0f - th[j][e] * th[j][e]);
                         qg[j][e] = dg * th[j][e] * sg[j][e] * (1.0f - sg[j][e]);
                     }
+                    // (the fp32 values themselves go into the planes, also where no fp32 dpre is stored: unpinned, the planes-only body
+                    // contracts these products into the fp16 conversions and the plane bits change)
+                    if constexpr (STEP) asm volatile("" : "+v"(qf[j][e]), "+v"(qg[j][e]));
                     // (a NaN / inf in dg or in the saved activations shows in qf / qg: the check below sees it)
-                    if (d.net_out) {       // fp32 dpre only where somebody reads it (the batched weight gradients read the planes)
+                    if (w32) {       // fp32 dpre only where somebody reads it (the batched weight gradients read the planes)
                         pf[e * T + 32 * j] = qf[j][e];
                         pq[e * T + 32 * j] = qg[j][e];
                     }
                 }
-            if (d.net_out_planes) {
+            if (wpl) {
                 // The max-abs / finiteness folds sit HERE, next to the plane stores and under the same condition, and are pinned by
                 // an empty asm: written in the arithmetic loop above, the optimiser sank them into the conditional guard_report at the
                 // end of the kernel and kept every qf / qg of the whole epilogue alive until then -- 150 (128-row blocks) to 290
@@ -893,8 +1063,15 @@ __global__ __launch_bounds__(256, MR == 8 ? 1 : 2) void gate_bwd_f16x3_kernel(co
                 asm volatile("" : "+v"(gmax), "+v"(gb_i));
                 gbad = gb_i != 0;
             }
-        }
-    if (d.net_out_planes) guard_report(gmax, gbad, ps, d.out_amax, d.flag);
+        };
+        x3_epilogue_pipeline<MR * 4, EPI_DEPTH, Ops>(request, finish);
+        if (wpl) guard_report(gmax, gbad, ps, d.out_amax, d.flag);
+    };
+    // (the compile-time body where the training step runs: aux0 as planes.  Not FG 0 / 1 and not the 256-row fp16 instantiation, whose
+    // planes-only bodies need more scratch than the run-time body -- 870 and 8 bytes per lane)
+    constexpr bool HAS_STEP = FG == 2 && (MR == 4 || BF);
+    if (HAS_STEP && !d.net_out && d.net_out_planes) epilogue(std::integral_constant<bool, HAS_STEP>{});
+    else epilogue(std::false_type{});
 }
 
 
