@@ -53,10 +53,10 @@ def random_params(prior, seed):
 
 # ------------------------------------------------------------------ CPU restatement
 def ref_logits(codes, spk, P, cfg):
-    """codes int64 [B,T], spk int64 [B] -> logits [B,T,k]."""
+    """codes int64 [B,T], spk int64 [B] -> logits [B,T,k], in the parameters' dtype (float64 copies: tests/gen_ref.py)."""
     k = cfg['quantization_channels']
     B, T = codes.shape
-    x = R.shift_right(Fn.one_hot(codes, k).float())
+    x = R.shift_right(Fn.one_hot(codes, k).to(P['prior/preprocess/kernel'].dtype))
     net = R.conv1d_v2(x, P['prior/preprocess/kernel'], P['prior/preprocess/bias'])
     skip = R.conv1d_v2(net, P['prior/skip/kernel'], P['prior/skip/bias'])
     cond = P['prior/speaker_embedding'][spk].unsqueeze(1).repeat(1, T // 64, 1)          # [B, Tz, Cs]
