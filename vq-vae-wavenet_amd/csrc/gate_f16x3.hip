@@ -311,6 +311,22 @@ __global__ __launch_bounds__(256) void pack_w_t_tile_kernel(const float* __restr
     }
 }
 
+// LDS-DMA of the conv main loop: 16 bytes per lane from raw buffer `rsrc` (as vqw_make_rsrc builds it) at byte offset `voff` into
+// the 1 KiB of LDS at the wave-uniform byte address `lds_dst` (lane i lands at + 16 i; an out-of-range lane gets zeros).  As inline
+// assembly and not through vqw_buf_load_lds16: the compiler orders every LDS read behind every LDS-DMA it knows of -- an
+// `s_waitcnt vmcnt(0)` in front of the first ds_read that follows a request, which would empty the ring in every K step.  Hidden
+// from it the requests are ordered by f16x3_mainloop's own counted waits and barriers.  M0 (the destination) is the compiler's
+// register: written and restored inside the statement.
+__device__ __forceinline__ void x3_dma16(u32x4 rsrc, unsigned lds_dst, int voff) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "s"(lds_dst), "v"(voff), "s"(rsrc) : "memory");
+}
+__device__ __forceinline__ u32x4 x3_rsrc_words(const void* p, unsigned bytes) {
+    const size_t a = reinterpret_cast<size_t>(p);
+    return u32x4{(unsigned)a, (unsigned)(a >> 32) & 0xffffu, bytes, 0x00020000u};      // stride 0, raw: offsets are checked against `bytes`
+}
+
 struct GateArgs {
     vqw_f16x3_gate_desc d;
     int NB;        // B * T rows of the activation planes
@@ -339,7 +355,7 @@ struct OutArgs {
 #define VQW_X3_PAT_MEM 1      // issue pattern of the conv main loop: LDS / global-memory instructions per MFMA ...
 #define VQW_X3_PAT_ALU 2      // ... and address computations per MFMA (tools/x3_bench.py: 1/2 measured best)
 #endif
-constexpr int NSTG = 4, STG_BYTES = 32 * 1024, PIECES = 8;   // per wave and stage: 4 weight + 4 activation pieces of 1 KiB
+constexpr int NSTG = 4;      // LDS stages of the weight-gradient kernel
 
 // Geometry of one block's contraction: 256 weight rows from row m_row0 of planes with M rows, K = ks taps x Cin
 // input channels, 256 activation rows from row n0 (time t0 of its batch row) of planes with NB rows.
@@ -358,12 +374,12 @@ struct LoopGeom {
     int sb, sn;      // TAB: this block's K steps [sb, sb + sn) of the ks * Cin / 16 (split-K of the short encoder layers); sn even
 };
 
-// acc[i][j] += W[m_row0 + 32 i .., :] X[:, n0 + 64 wv + 32 j ..]: MR x 2 accumulator tiles per wave, operands through
-// VGPRs into an LDS ring, one barrier per K step of 16.
+// acc[i][j] += W[m_row0 + 32 i .., :] X[:, n0 + 64 wv + 32 j ..]: MR x 2 accumulator tiles per wave, operands by LDS-DMA
+// into an LDS ring, one barrier per K step of 16.
 //   MR = 8: block = 256 rows x 256 columns, 16 accumulator tiles (256 AGPRs) per wave, one block per CU, 4 LDS stages of
-//           32 KiB, two stages of requests in flight.
+//           32 KiB, three stages of requests in flight.
 //   MR = 4: block = 128 rows x 256 columns, 8 accumulator tiles per wave, 256 registers per wave => TWO blocks per CU
-//           (3 stages of 24 KiB each): while one block is in its HBM-bound epilogue (all blocks of a one-block-per-CU
+//           (3 stages of 24 KiB each, two stages of requests in flight): while one block is in its HBM-bound epilogue (all blocks of a one-block-per-CU
 //           grid reach it together: gate backward spent 64 % of its time there) the other block's MFMAs run; each weight
 //           panel is read by twice as many blocks (all of the loop's data movement is 16 % of the MR = 8 kernel).
 // Two blocks that share a CU start together and would reach their epilogues together; the blocks of every second
@@ -379,20 +395,24 @@ template <int MR> struct X3Shape {
     static constexpr int NSTAGE = MR == 8 ? 4 : 3;
     static constexpr int STAGE_BYTES = (MR * 2 + 16) * 1024;     // MR*2 weight pieces + 16 activation pieces of 1 KiB
     static constexpr int LDS_BYTES = NSTAGE * STAGE_BYTES;
-    static constexpr int DEPTH = MR == 8 ? 2 : 1;                 // stages of requests in flight
+    static constexpr int DEPTH = MR == 8 ? 2 : 1;                 // stages of requests left in flight across a step's barrier
 };
 template <bool BF, int MR, bool TAB = false, int DEPTH = X3Shape<MR>::DEPTH>
-__device__ __forceinline__ void f16x3_mainloop(f32x16 (&acc)[MR][2], char* smem, const LoopGeom& g, int wv, int lane) {
+__device__ __forceinline__ void f16x3_mainloop(f32x16 (&acc)[MR][2], char* smem, const LoopGeom& g, int wv_, int lane_) {
+    // The loop's own copies of the wave and lane index.  The callers' are live from the top of the kernel to the end of the epilogue;
+    // used in here as well they get a register of the loop's choosing, which the epilogues -- 256 + 256 registers, every one taken --
+    // then spill (8 bytes of scratch in the 256-row head conv, 4 more in the bf16 gate conv).
+    int wv = wv_, lane = lane_;
+    asm volatile("" : "+v"(wv), "+v"(lane));
     constexpr int NP = BF ? 1 : 2;        // planes per operand
     constexpr int NA = MR * NP / 4, NBP = 2 * NP;      // weight / activation pieces a wave moves per step
     if (MR == 4) x3_stagger(VQW_X3_STAGGER);
-    constexpr int NSTG_ = DEPTH + 2, STGB = X3Shape<MR>::STAGE_BYTES, BOFF = MR * 2 * 1024;      // (DEPTH: stages of requests in flight)
+    constexpr int NSTG_ = DEPTH + 2, STGB = X3Shape<MR>::STAGE_BYTES, BOFF = MR * 2 * 1024;      // (a stage is requested DEPTH + 1 steps before it is read)
     const int l31 = lane & 31, lhi = lane >> 5;
     const int KCA = (TAB ? g.wks : g.ks) * g.Cin / 8, KCB = g.Cin / 8, spt = g.Cin / 16;   // spt: K steps per tap
     const int nsteps = TAB ? g.sn : g.ks * spt;
-    // (NP planes: the requests past the last K step must fall outside the resource -- and read as zero -- in bf16 mode too, where the
-    // weight planes end after ONE plane)
-    const __amdgpu_buffer_rsrc_t ra = vqw_make_rsrc(g.wp, (unsigned)((size_t)NP * KCA * g.M * 16));
+    // Weight resource `ra` (below): NP planes -- the requests past the last K step must fall outside the resource, and read as zero,
+    // in bf16 mode too, where the weight planes end after ONE plane.
     // One buffer resource per activation plane, based at the contraction's first chunk: 32-bit offsets then only span the
     // chunks this contraction reads (checked by the callers: Cin / 8 * NB * 16 < 2 GiB), not the planes tensor -- the gated planes
     // of all layers side by side are 3.3 GB at batch 16 and neither their size nor the distance between the two planes may
@@ -400,26 +420,31 @@ __device__ __forceinline__ void f16x3_mainloop(f32x16 (&acc)[MR][2], char* smem,
     const size_t plane_bytes = (size_t)g.xKC * g.NB * 16, span = (size_t)(g.xKC - g.xkc0) * g.NB * 16;
     const char* xbase = reinterpret_cast<const char*>(g.xp) + (size_t)g.xkc0 * g.NB * 16;
     const unsigned xspan = span < 0x7fffffffu ? (unsigned)span : 0x7fffffffu;
-    const __amdgpu_buffer_rsrc_t rb0 = vqw_make_rsrc(xbase, xspan);
-    const __amdgpu_buffer_rsrc_t rb1 = vqw_make_rsrc(xbase + (NP > 1 ? plane_bytes : 0), xspan);
     // Stage image: MR*2 weight pieces (row tile i, plane p at (i * 2 + p) KiB), then 16 activation pieces.  lane = (k half, row)
     // as the MFMA wants it.
-    int voffA[NA], pieceA[NA], voffB[NBP], trow[NBP], pieceB[NBP];
+    int voffA[NA], voffB[NBP], trow[NBP];
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
         const int q = wv * NA + i, tile = q / NP, p = q % NP;
-        pieceA[i] = tile * 2 + p;
         voffA[i] = ((p * KCA + lhi) * g.M + g.m_row0 + tile * 32 + l31) * 16;
     }
 #pragma unroll
     for (int i = 0; i < NBP; ++i) {
-        const int q = wv * NBP + i, tile = q / NP, p = q % NP;
-        pieceB[i] = tile * 2 + p;
+        const int tile = (wv * NBP + i) / NP;
         voffB[i] = (lhi * g.NB + g.n0 + tile * 32 + l31) * 16;      // (plane p = i % NP: its own resource)
         trow[i] = TAB ? (g.n0 + tile * 32 + l31) % g.T : g.t0 + tile * 32 + l31;      // time of this lane's activation row
     }
-    f32x4 rgA[NA + NBP], rgB[NA + NBP];
-    auto rissue = [&](int s_, f32x4 (&rg)[NA + NBP]) {
+    // Stage s: global -> LDS by LDS-DMA (x3_dma16: no VGPRs, no ds_write).  A 1-KiB piece is the lane-linear image one such
+    // instruction writes (wave-uniform base + 16 * lane); a lane whose row lies before / behind its batch row (causal, batch-boundary
+    // and stride-2 padding) or past the end of the planes requests an out-of-range offset and gets zeros in its 16 bytes of LDS,
+    // as it would in a VGPR.  Piece q of the wave's P = NA + NBP: weights first.
+    constexpr int P = NA + NBP;
+    const u32x4 ra = x3_rsrc_words(g.wp, (unsigned)((size_t)NP * KCA * g.M * 16));
+    const u32x4 rb0 = x3_rsrc_words(xbase, xspan), rb1 = x3_rsrc_words(xbase + (NP > 1 ? plane_bytes : 0), xspan);
+    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+    const int wvu = __builtin_amdgcn_readfirstlane(wv);
+    struct StageReq { int woff, xoff, shift; unsigned dst; };
+    auto stage_req = [&](int s_) {
         const int s = TAB ? s_ + g.sb : s_;
 #if VQW_X3_TAP_MINOR
         // K order: channel chunk outermost, taps innermost -- the taps of one chunk read the same activation lines a few rows apart,
@@ -432,21 +457,20 @@ __device__ __forceinline__ void f16x3_mainloop(f32x16 (&acc)[MR][2], char* smem,
         const int e_ = TAB ? j - g.toff : 0;
         const int shift = TAB ? g.tsgn * (e_ >> 1) : (g.ks - 1 - j) * g.dilation * (g.dir < 0 ? -1 : 1);   // rows before / behind the batch row read as zero
         const int kcx = TAB ? kc + (g.ts2d ? (e_ & 1) * KCB : 0) : kc;
-#pragma unroll
-        for (int i = 0; i < NA; ++i) rg[i] = vqw_buf_load4(ra, voffA[i] + (j * KCB + kc) * g.M * 16, 0);
-#pragma unroll
-        for (int i = 0; i < NBP; ++i) {
-            const int tr = trow[i] - shift;
-            const int vb = (tr >= 0 && tr < g.T) ? voffB[i] + (kcx * g.NB - shift) * 16 : (int)0x80000000;   // out of range -> 0
-            rg[NA + i] = vqw_buf_load4((i % NP) ? rb1 : rb0, vb, 0);      // (wv * NBP is even: plane = i % NP at compile time)
-        }
+        return StageReq{(j * KCB + kc) * g.M * 16, (kcx * g.NB - shift) * 16, shift, lds0 + (unsigned)((s_ % NSTG_) * STGB)};
     };
-    auto rcommit = [&](int s, const f32x4 (&rg)[NA + NBP]) {
-        char* dst = smem + (s % NSTG_) * STGB + lane * 16;
-#pragma unroll
-        for (int i = 0; i < NA; ++i) *reinterpret_cast<f32x4*>(dst + pieceA[i] * 1024) = rg[i];
-#pragma unroll
-        for (int i = 0; i < NBP; ++i) *reinterpret_cast<f32x4*>(dst + BOFF + pieceB[i] * 1024) = rg[NA + i];
+    auto dma_piece = [&](const StageReq& r, int q) {
+#ifndef VQW_ABL_NODMA
+        if (q < NA) {
+            const int w = wvu * NA + q;
+            x3_dma16(ra, r.dst + (unsigned)((w / NP * 2 + w % NP) * 1024), voffA[q] + r.woff);
+        } else {
+            const int i = q - NA, w = wvu * NBP + i, tr = trow[i] - r.shift;
+            const int vb = (tr >= 0 && tr < g.T) ? voffB[i] + r.xoff : (int)0x80000000;   // out of range -> 0
+            // (wv * NBP is even: plane = i % NP at compile time)
+            x3_dma16((i % NP) ? rb1 : rb0, r.dst + (unsigned)(BOFF + (w / NP * 2 + w % NP) * 1024), vb);
+        }
+#endif
     };
     // Fragments: ONE set of A fragments (MR row tiles x NP planes) that is refilled row tile by row tile -- right behind the
     // MFMAs of a row tile its fragments of the NEXT stage are fetched from LDS, a whole step before they are used -- and two
@@ -490,34 +514,40 @@ __device__ __forceinline__ void f16x3_mainloop(f32x16 (&acc)[MR][2], char* smem,
         }
     };
 
-    rissue(0, rgA); rcommit(0, rgA);
-    rissue(1, rgA); rcommit(1, rgA);
-    rissue(2, rgA);
-    if (DEPTH == 2) rissue(3, rgB);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    // P requests per wave and stage.  All NSTG_ = DEPTH + 2 slots of the ring are requested up front; the counted wait before a
+    // stage is read leaves the wave's newer stages in flight (NSTG_ - 1 here, DEPTH in the loop), the raw barrier behind it
+    // covers the other waves' pieces.  The compiler does not count these requests (x3_dma16): every wait for them is written here.
+    auto wait_barrier = [&](auto n_c) {
+        constexpr int N = decltype(n_c)::value;
+        static_assert(N < 64, "vmcnt is a 6-bit counter");
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(N) : "memory");
+    };
+#pragma unroll
+    for (int s = 0; s < NSTG_; ++s) {
+        const StageReq r = stage_req(s);
+#pragma unroll
+        for (int q = 0; q < P; ++q) dma_piece(r, q);
+    }
+    wait_barrier(std::integral_constant<int, (NSTG_ - 1) * P>{});
 #pragma unroll
     for (int i = 0; i < MR; ++i) read_a(i, 0);
     read_b(fb, 0);
-    // One step s (one barrier): stage s + 1 is complete in LDS behind the barrier and the slot of stage s is free (its
-    // fragments are in registers); the MFMAs of stage s run row-tile pair by row-tile pair with the LDS reads of stage s + 1
-    // behind them; stage s + 2 (requested DEPTH steps ago) goes to LDS and stage s + 2 + DEPTH is requested.  nsteps is even
-    // (Cin % 32 == 0 is checked by the callers).
-    auto step = [&](const uint4 (&bc)[2][NP], uint4 (&bn)[2][NP], int s, f32x4 (&rg)[NA + NBP]) {
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    // One step s (one barrier).  The wait retires this wave's pieces of stage s + 1 (the DEPTH stages requested after it stay in
+    // flight) and the fragment reads of stage s it issued in step s - 1; behind the barrier stage s + 1 is therefore complete in
+    // LDS and the slot of stage s is free (every wave's fragments of it are in registers): stage s + NSTG_ is requested into that
+    // slot -- DEPTH + 1 steps before it is read -- and the MFMAs of stage s run row-tile pair by row-tile pair with the LDS reads
+    // of stage s + 1 behind them.  nsteps is even (Cin % 32 == 0 is checked by the callers).
+    auto step = [&](const uint4 (&bc)[2][NP], uint4 (&bn)[2][NP], int s) {
+        wait_barrier(std::integral_constant<int, DEPTH * P>{});
         const int sn = s + 1 < nsteps ? s + 1 : s;          // (the last step re-reads its own stage: no branch in the body)
-        // No conditionals in the body (they would cut it into scheduling regions): past the last stages the commit rewrites
-        // stale registers into an LDS stage nobody reads again and the requests run past the end of the weight planes,
-        // where raw buffer loads return zero.
-        // (VQW_ABL_*: timing ablations, wrong results, never shipped -- which of the three data paths bounds the loop)
+        // No conditionals in the body (they would cut it into scheduling regions): the requests past the last stage land in
+        // slots nobody reads again (the last step's own re-read is never used), from wherever their addresses point -- past the
+        // end of the weight planes raw buffer loads return zero.
+        // (VQW_ABL_*: timing ablations, wrong results, never shipped -- which of the data paths bounds the loop)
 #ifndef VQW_ABL_NOLDSREAD
         read_b(bn, sn);
 #endif
-#ifndef VQW_ABL_NOCOMMIT
-        rcommit(s + 2, rg);
-#endif
-#ifndef VQW_ABL_NOGLOBAL
-        rissue(s + 2 + DEPTH, rg);
-#endif
+        const StageReq r = stage_req(s + NSTG_);
 #pragma unroll
         for (int i = 0; i < MR; i += 2) {
             mfma_rows(i, bc);
@@ -525,6 +555,10 @@ __device__ __forceinline__ void f16x3_mainloop(f32x16 (&acc)[MR][2], char* smem,
             read_a(i, sn);
             read_a(i + 1, sn);
 #endif
+            // the wave's P requests in MR / 2 even parts, one behind the fragment reads of each row-tile pair: inline asm keeps its
+            // place among the LDS reads, which the issue pattern below spreads over the MFMAs
+#pragma unroll
+            for (int q = P * (i / 2) / (MR / 2); q < P * (i / 2 + 1) / (MR / 2); ++q) dma_piece(r, q);
         }
         // issue order: one MFMA, then one LDS / global-memory instruction and a few address computations in its shadow
 #pragma unroll
@@ -535,9 +569,12 @@ __device__ __forceinline__ void f16x3_mainloop(f32x16 (&acc)[MR][2], char* smem,
         }
     };
     for (int s = 0; s < nsteps; s += 2) {
-        step(fb, fbn, s, rgA);
-        step(fbn, fb, s + 1, DEPTH == 2 ? rgB : rgA);
+        step(fb, fbn, s);
+        step(fbn, fb, s + 1);
     }
+    // the requests past the last stage: nothing of the loop may be in flight when the epilogue starts counting its own loads (or
+    // when an input gradient's second run refills the ring)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // Epilogue request depth.  An epilogue works through NG groups -- four channels x two column tiles per lane -- and each
