@@ -229,6 +229,38 @@ int vqw_speaker_tile_bwd(const float* dcond, int64_t dcond_bstride, int row0,
                          vqw_stream_t s);
 
 /* ------------------------------------------------------------------------------------
+ * The codebook by moving averages, with dead-code restart (sonnet's VectorQuantizerEMA, which the reference
+ * vendors in Magenta/sonnet.py, without its zero-debias).
+ * z_e [B][D][Tz], idx int64 [B][Tz] as vqw_vq_nearest_fwd leaves them; frames are numbered f = b*Tz + t, Nf = B*Tz.
+ *
+ * vqw_vq_cluster_stats -- the statistics of one pass:
+ *   cnt[k]    int32 [K]    = #{f : idx[f] == k}
+ *   sum[k][d] fp32 [K][D]  = sum of z_e[b][d][t] over those frames, added IN ASCENDING f, each add rounded to fp32,
+ *                            starting from +0.0f (a code nobody chose: +0.0f)
+ *   cand[k][d] fp32 [K][D] = z_e of frame pick[k] (pick int32 [K] on the device; a pick outside [0, Nf) is CLAMPED into it:
+ *                            the host cannot look at a device value without a sync).  pick and cand may both be NULL.
+ * Every element of the outputs is written on every call (no zero-fill beforehand), nothing is atomic: bitwise
+ * reproducible.  An index outside [0, K) belongs to no code.  Any K, D, B*Tz >= 1 (B*Tz, K*D <= 2^30).  No output may
+ * overlap an input or another output.
+ *
+ * vqw_vq_codebook_ema_step -- the update, in place on emb [K][D], n [K], m [K][D]; g = fp32(decay), h = fp32(1 - decay),
+ * every operation rounded to fp32 on its own (no contraction):
+ *   n'[k]    = g*n[k] + h*float(cnt[k])
+ *   m'[k][d] = g*m[k][d] + h*sum[k][d]
+ *   if tau > 0 and n'[k] < tau:   n'[k] = 1;  m'[k][:] = cand[k][:];  emb[k][:] = cand[k][:]      (dead: restart)
+ *   else if cnt[k] > 0:           emb[k][d] = m'[k][d] / n'[k]
+ *   else:                         emb[k][:] is not written                                       (n, m still decay)
+ *   info[0] = codes restarted, info[1] = codes with cnt > 0 in this call.
+ * info is int32 [8]: [2..7] belong to the kernel (the blocks' running counts and a ticket; integer atomics), must be zero
+ * before the first call and are left zero by every call.  cand may be NULL when tau == 0.  skip (device int32, may be
+ * NULL): non-zero when the kernel runs = NOTHING is written, not emb, n, m nor info.  0 < g, h < 1, 0 <= tau < 1.  No
+ * output may overlap an input or another output.                                                                      */
+int vqw_vq_cluster_stats(const float* z_e, const int64_t* idx, const int32_t* pick, int32_t* cnt, float* sum, float* cand,
+                         int B, int D, int Tz, int K, vqw_stream_t s);
+int vqw_vq_codebook_ema_step(float* emb, float* n, float* m, const int32_t* cnt, const float* sum, const float* cand,
+                             float g, float h, float tau, int32_t* info, const int32_t* skip, int K, int D, vqw_stream_t s);
+
+/* ------------------------------------------------------------------------------------
  * Time-jitter regularisation of the latents (arXiv 1901.08810; the reference's unused
  * Decoder/decoder_ops.py:5-28, but per utterance: rows are independent).
  * zq [B][D][Tz] at batch stride zq_bstride, u fp32 [B][Tz] in [0, 1); lo = fp32(p / 2), hi = fp32(1 - p / 2):

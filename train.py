@@ -22,6 +22,12 @@ that step's line of summaries.jsonl.  The list is in the format of the `<name>_t
 neighbour of the same utterance (arXiv 1901.08810; overrides `time_jitter` of the parameters file, 0 = off).  Adds
 `[jitter ...]` to the console line and `jitter_moved` (the share of frames that moved in that step) to summaries.jsonl, on
 logged steps.
+
+`-codebook_ema G`: the VQ codebook is trained as the moving average (decay G, e.g. 0.99) of the encoder outputs assigned to each
+code (sonnet's VectorQuantizerEMA) instead of by Adam on the codebook loss; `-codebook_restart T` (needs `-codebook_ema`): a
+code whose moving count falls below T (e.g. 0.05) is restarted on an encoder output of the batch.  They override `codebook_ema`
+/ `codebook_restart` of the parameters file (0 = off).  Adds `[codebook used U/K restarted R]` to the console line and
+`codebook_used`, `codebook_restarted` to summaries.jsonl, on logged steps.
 """
 import importlib
 import json
@@ -67,11 +73,21 @@ def main():
     parser.add_argument('-grad_norm', action='store_true', dest='grad_norm', help='log gradient norms without clipping')
     parser.add_argument('-time_jitter', default=None, type=float, dest='time_jitter', metavar='float',
                         help='probability in [0, 1] that a latent frame the decoder reads is its neighbour (0 = off)')
+    parser.add_argument('-codebook_ema', default=None, type=float, dest='codebook_ema', metavar='float',
+                        help='decay in (0, 1) of the codebook\'s moving averages (0 = off: Adam trains the codebook)')
+    parser.add_argument('-codebook_restart', default=None, type=float, dest='codebook_restart', metavar='float',
+                        help='restart a code whose moving count falls below this threshold in (0, 1) (0 = never; needs -codebook_ema)')
     args = parser.parse_args()
     if args.clip_norm is not None and not args.clip_norm > 0:
         parser.error('-clip_norm must be > 0 (got %r)' % args.clip_norm)
     if args.time_jitter is not None and not 0.0 <= args.time_jitter <= 1.0:
         parser.error('-time_jitter must be a probability in [0, 1] (got %r)' % args.time_jitter)
+    if args.codebook_ema is not None and not 0.0 <= args.codebook_ema < 1.0:
+        parser.error('-codebook_ema must be 0 (off) or a decay in (0, 1) (got %r)' % args.codebook_ema)
+    if args.codebook_restart is not None and not 0.0 <= args.codebook_restart < 1.0:
+        parser.error('-codebook_restart must be 0 (never) or a threshold in (0, 1) (got %r)' % args.codebook_restart)
+    if args.codebook_restart and args.codebook_ema == 0.0:
+        parser.error('-codebook_restart needs -codebook_ema (got -codebook_ema 0)')
     if args.eval_interval < 0 or args.eval_batches < 1:
         parser.error('-eval_interval must be >= 0 and -eval_batches >= 1')
     if args.eval_interval > 0 and args.eval_list is None:
@@ -117,6 +133,9 @@ def main():
         raise NotImplementedError('encoder %s not implemented' % parameters['encoder'])
     if args.time_jitter is not None:
         parameters['time_jitter'] = args.time_jitter
+    for key in ('codebook_ema', 'codebook_restart'):
+        if getattr(args, key) is not None:
+            parameters[key] = getattr(args, key)
     model = pkg.model.VQVAE(parameters, wavenet_parameters, dataset.num_speakers, device=dev, seed=0)
     if args.restore_path is not None:
         if args.restore_path.endswith(('.safetensors', '.npz')):      # TF variable names (checkpoint.py)
@@ -158,6 +177,9 @@ def main():
             extra = {}
             if model.time_jitter > 0:             # from the step's source frames; read here, on logged steps only
                 extra['jitter_moved'] = model.jitter_moved(ws)
+            if model.codebook_ema > 0:            # counts the update kernel left on the device; read here, on logged steps only
+                info = model.codebook_info()
+                extra.update(codebook_used=info['used'], codebook_restarted=info['restarted'])
             if eval_now:
                 extra['eval'] = pkg.scoring.score_batches(model, eval_set, dev, weights='ema').report(
                     'sample', latent_dim=model.D if model.use_vq else 0)
@@ -170,6 +192,8 @@ def main():
                 msg += ' [gnorm %.4f]' % gn['global']
             if 'jitter_moved' in extra:
                 msg += ' [jitter %.3f]' % extra['jitter_moved']
+            if 'codebook_used' in extra:
+                msg += ' [codebook used %d/%d restarted %d]' % (extra['codebook_used'], model.Kc, extra['codebook_restarted'])
             if eval_now:
                 msg += ' [eval bits %.5f]' % extra['eval']['bits_per_sample']
             print(progress + msg + display_time(t, (args.num_steps - step) * t), end='', flush=True)

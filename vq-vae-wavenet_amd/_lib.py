@@ -137,6 +137,8 @@ SIGNATURES = {
     'vqw_transpose': (_i, [_fp, _fp, _i, _i, _i, _fp]),
     'vqw_vq_nearest_fwd': (_i, [_fp, _fp, _fp, _fp, _fp, _i64, _fp, _i, _i, _i, _i, _fp]),
     'vqw_vq_nearest_bwd': (_i, [_fp, _fp, _fp, _fp, _i64, _fp, _fp, _f, _f, _i, _i, _i, _i, _fp]),
+    'vqw_vq_cluster_stats': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp]),
+    'vqw_vq_codebook_ema_step': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _f, _f, _f, _fp, _fp, _i, _i, _fp]),
     'vqw_speaker_tile_fwd': (_i, [_fp, _fp, _fp, _i64, _i, _i, _i, _i, _i, _fp]),
     'vqw_speaker_tile_bwd': (_i, [_fp, _i64, _i, _fp, _fp, _i, _i, _i, _i, _fp]),
     'vqw_time_jitter_fwd': (_i, [_fp, _i64, _fp, _f, _f, _fp, _i64, _fp, _i, _i, _i, _fp]),

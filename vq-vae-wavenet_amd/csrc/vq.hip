@@ -136,6 +136,111 @@ __global__ void speaker_tile_bwd_kernel(const float* __restrict__ dcond, long dc
     unsafeAtomicAdd(dtable + row * Cs + j, s);
 }
 
+// ---- codebook by moving averages --------------------------------------------------------------------
+// Cluster statistics of one pass: one wave per code k.  The wave's 64 lanes load 64 consecutive idx (frames f = b*Tz + t in
+// ascending order), a ballot finds the frames of code k, the set bits are walked from the lowest up and the lanes stride
+// over d: sum[k][d] is a chain of fp32 adds in ascending f from +0.0f -- a fixed order, nothing atomic, every element of
+// cnt / sum / cand written by exactly one lane (zeros for an unused code).  More than 64 channels: the frames are scanned
+// once per 64 channels (the running sums stay in one register per lane).  cand[k] = the frame pick[k], clamped to [0, Nf).
+constexpr int CB_WAVES = 4;
+
+__global__ __launch_bounds__(64 * CB_WAVES) void vq_cluster_stats_kernel(
+    const float* __restrict__ z_e, const int64_t* __restrict__ idx, const int32_t* __restrict__ pick, int32_t* __restrict__ cnt,
+    float* __restrict__ sum, float* __restrict__ cand, int Nf, int D, int Tz, int K) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * CB_WAVES + (threadIdx.x >> 6);
+    if (k >= K) return;                                   // (whole waves leave; the kernel has no barrier)
+    const size_t bstride = (size_t)D * Tz;
+    for (int d0 = 0; d0 < D; d0 += 64) {
+        const int d = d0 + lane;
+        const bool on = d < D;
+        const float* zd = z_e + (size_t)(on ? d : 0) * Tz;
+        float acc = 0.0f;
+        int n = 0;
+        for (int f0 = 0; f0 < Nf; f0 += 64) {
+            const int f = f0 + lane;
+            unsigned long long hit = __ballot(f < Nf && idx[f < Nf ? f : 0] == (int64_t)k);
+            n += __popcll(hit);
+            while (hit) {
+                const int fk = f0 + __builtin_ctzll(hit);
+                hit &= hit - 1;
+                const int b = fk / Tz, t = fk - b * Tz;
+                if (on) acc = acc + zd[(size_t)b * bstride + t];
+            }
+        }
+        if (on) sum[(size_t)k * D + d] = acc;
+        if (d0 == 0 && lane == 0) cnt[k] = n;
+    }
+    if (cand) {
+        int p = pick[k];
+        p = p < 0 ? 0 : (p >= Nf ? Nf - 1 : p);
+        const int b = p / Tz, t = p - b * Tz;
+        for (int d = lane; d < D; d += 64) cand[(size_t)k * D + d] = z_e[(size_t)b * bstride + (size_t)d * Tz + t];
+    }
+}
+
+// The codebook's update, one wave per code (the per-code scalars once per wave, the lanes over d).  Every operation is
+// rounded to fp32 on its own.  info[0..1] = codes restarted / codes with cnt > 0 of THIS call: the blocks add their counts
+// into info[4..5] (integer atomics) and the last block to finish (ticket info[6]) moves them to info[0..1] and leaves
+// info[4..6] at zero for the next call.  *skip != 0: the kernel returns before it reads or writes anything else.
+__global__ __launch_bounds__(64 * CB_WAVES) void vq_codebook_ema_kernel(
+    float* __restrict__ emb, float* __restrict__ n_, float* __restrict__ m_, const int32_t* __restrict__ cnt,
+    const float* __restrict__ sum, const float* __restrict__ cand, float g, float h, float tau, int32_t* __restrict__ info,
+    const int32_t* __restrict__ skip, int K, int D) {
+    // plain operators under contract(off): each is one IEEE fp32 operation (what __fmul_rn / __fadd_rn / __fdiv_rn name); the
+    // intrinsics are inlined WITH the translation unit's contraction and g*m + h*sum came out as v_mul + v_fmac
+#pragma clang fp contract(off)
+    if (skip && *skip != 0) return;
+    __shared__ int tally[2];
+    if (threadIdx.x < 2) tally[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * CB_WAVES + (threadIdx.x >> 6);
+    if (k < K) {
+        const int c = cnt[k];
+        const float gn = g * n_[k], hc = h * (float)c;
+        const float n1 = gn + hc;
+        const bool dead = tau > 0.0f && n1 < tau;
+        const size_t row = (size_t)k * D;
+        for (int d = lane; d < D; d += 64) {
+            const float gm = g * m_[row + d], hs = h * sum[row + d];
+            const float m1 = gm + hs;
+            if (dead) {
+                const float z = cand[row + d];
+                m_[row + d] = z;
+                emb[row + d] = z;
+            } else {
+                m_[row + d] = m1;
+                if (c > 0) emb[row + d] = m1 / n1;
+            }
+        }
+        if (lane == 0) {          // (every lane has read n_[k] above: one wave, program order)
+            n_[k] = dead ? 1.0f : n1;
+            if (dead) atomicAdd(&tally[0], 1);
+            if (c > 0) atomicAdd(&tally[1], 1);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (tally[0]) atomicAdd(info + 4, tally[0]);
+        if (tally[1]) atomicAdd(info + 5, tally[1]);
+        __threadfence();
+        if (atomicAdd(info + 6, 1) == (int)gridDim.x - 1) {
+            __threadfence();
+            info[0] = atomicExch(info + 4, 0);
+            info[1] = atomicExch(info + 5, 0);
+            atomicExch(info + 6, 0);
+        }
+    }
+}
+
+// [a, a + na) and [b, b + nb) bytes share a byte
+bool cb_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && x < y + nb && y < x + na;
+}
+
 }  // namespace
 
 extern "C" int vqw_vq_nearest_fwd(const float* z_e, const float* emb, int64_t* idx, float* e_k, float* zq,
@@ -175,6 +280,54 @@ extern "C" int vqw_vq_nearest_bwd(const float* z_e, const float* e_k, const int6
     hipLaunchKernelGGL(vq_nearest_bwd_kernel, dim3(g), dim3(256), 0, (hipStream_t)s, z_e, e_k, idx, dzq,
                        (long)dzq_bstride, dz_e, demb, cscale, escale, B, D, Tz);
     VQW_LAUNCH_CHECK("vqw_vq_nearest_bwd");
+    return 0;
+}
+
+extern "C" int vqw_vq_cluster_stats(const float* z_e, const int64_t* idx, const int32_t* pick, int32_t* cnt, float* sum,
+                                    float* cand, int B, int D, int Tz, int K, vqw_stream_t s) {
+    VQW_CHECK(z_e && idx && cnt && sum, "vqw_vq_cluster_stats: null pointer");
+    VQW_CHECK((pick == nullptr) == (cand == nullptr), "vqw_vq_cluster_stats: null pointer (pick and cand go together)");
+    VQW_CHECK(B > 0 && D > 0 && Tz > 0 && K > 0, "vqw_vq_cluster_stats: B=%d, D=%d, Tz=%d, K=%d must be positive", B, D, Tz, K);
+    VQW_CHECK((int64_t)B * Tz <= (1 << 30) && (int64_t)K * D <= (1 << 30), "vqw_vq_cluster_stats: B*Tz and K*D must be <= 2^30");
+    const size_t nz = (size_t)B * D * Tz * 4, ni = (size_t)B * Tz * 8, nk = (size_t)K * 4, nkd = (size_t)K * D * 4;
+    const void* in[3] = {z_e, idx, pick};
+    const size_t in_n[3] = {nz, ni, nk};
+    const void* out[3] = {cnt, sum, cand};
+    const size_t out_n[3] = {nk, nkd, nkd};
+    for (int o = 0; o < 3; ++o) {
+        for (int i = 0; i < 3; ++i)
+            VQW_CHECK(!cb_overlap(out[o], out_n[o], in[i], in_n[i]), "vqw_vq_cluster_stats: an output must not alias an input");
+        for (int p = o + 1; p < 3; ++p)
+            VQW_CHECK(!cb_overlap(out[o], out_n[o], out[p], out_n[p]), "vqw_vq_cluster_stats: the outputs must not alias each other");
+    }
+    hipLaunchKernelGGL(vq_cluster_stats_kernel, dim3(vqw_cdiv(K, CB_WAVES)), dim3(64 * CB_WAVES), 0, (hipStream_t)s, z_e, idx,
+                       pick, cnt, sum, cand, B * Tz, D, Tz, K);
+    VQW_LAUNCH_CHECK("vqw_vq_cluster_stats");
+    return 0;
+}
+
+extern "C" int vqw_vq_codebook_ema_step(float* emb, float* n, float* m, const int32_t* cnt, const float* sum, const float* cand,
+                                        float g, float h, float tau, int32_t* info, const int32_t* skip, int K, int D,
+                                        vqw_stream_t s) {
+    VQW_CHECK(emb && n && m && cnt && sum && info, "vqw_vq_codebook_ema_step: null pointer");
+    VQW_CHECK(K > 0 && D > 0 && (int64_t)K * D <= (1 << 30), "vqw_vq_codebook_ema_step: K=%d, D=%d must be positive, K*D <= 2^30", K, D);
+    VQW_CHECK(g > 0.0f && g < 1.0f && h > 0.0f && h < 1.0f, "vqw_vq_codebook_ema_step: g=%g and h=%g must lie in (0, 1)", g, h);
+    VQW_CHECK(tau >= 0.0f && tau < 1.0f, "vqw_vq_codebook_ema_step: tau=%g must lie in [0, 1)", tau);
+    VQW_CHECK(cand || tau == 0.0f, "vqw_vq_codebook_ema_step: null pointer (tau > 0 needs cand)");
+    const size_t nk = (size_t)K * 4, nkd = (size_t)K * D * 4;
+    const void* out[4] = {emb, n, m, info};
+    const size_t out_n[4] = {nkd, nk, nkd, 8 * 4};
+    const void* in[4] = {cnt, sum, cand, skip};
+    const size_t in_n[4] = {nk, nkd, nkd, 4};
+    for (int o = 0; o < 4; ++o) {
+        for (int i = 0; i < 4; ++i)
+            VQW_CHECK(!cb_overlap(out[o], out_n[o], in[i], in_n[i]), "vqw_vq_codebook_ema_step: an output must not alias an input");
+        for (int p = o + 1; p < 4; ++p)
+            VQW_CHECK(!cb_overlap(out[o], out_n[o], out[p], out_n[p]), "vqw_vq_codebook_ema_step: the outputs must not alias each other");
+    }
+    hipLaunchKernelGGL(vq_codebook_ema_kernel, dim3(vqw_cdiv(K, CB_WAVES)), dim3(64 * CB_WAVES), 0, (hipStream_t)s, emb, n, m,
+                       cnt, sum, cand, g, h, tau, info, skip, K, D);
+    VQW_LAUNCH_CHECK("vqw_vq_codebook_ema_step");
     return 0;
 }
 

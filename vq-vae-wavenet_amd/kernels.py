@@ -581,6 +581,65 @@ def vq_nearest_bwd(z_e, e_k, idx, *, dzq, dzq_bstride, dz_e, demb, cscale, escal
                                        L.ptr(demb), float(cscale), float(escale), B, D, Tz, K, L.stream()))
 
 
+def codebook_ema_constants(decay, restart=0.0):
+    """(g, h, tau) of vqw_vq_codebook_ema_step for the configuration keys codebook_ema = decay and codebook_restart = restart:
+    g = fp32(decay), h = fp32(1 - decay) (the subtraction in float64, rounded once), tau = fp32(restart).  decay 0 is "off"
+    ((0.0, 1.0, 0.0); it allows no restart); otherwise 0 < decay < 1 and 0 <= restart < 1 must still hold in fp32."""
+    decay, restart = float(decay), float(restart)
+    g, h, tau = C.c_float(decay).value, C.c_float(1.0 - decay).value, C.c_float(restart).value
+    if not 0.0 <= restart < 1.0 or not 0.0 <= tau < 1.0:
+        raise ValueError('codebook_restart must be 0 (never) or a threshold in (0, 1) (got %r)' % restart)
+    if decay == 0.0:
+        if restart != 0.0:
+            raise ValueError('codebook_restart needs codebook_ema (got codebook_restart %r with codebook_ema 0)' % restart)
+        return 0.0, 1.0, 0.0
+    if not (0.0 < decay < 1.0 and 0.0 < g < 1.0 and 0.0 < h < 1.0):
+        raise ValueError('codebook_ema must be 0 (off) or a decay in (0, 1), also as fp32 (got %r)' % decay)
+    return g, h, tau
+
+
+def vq_cluster_stats(z_e, idx, *, cnt, sum, pick=None, cand=None, K):
+    """vqw_vq_cluster_stats: cnt int32 [K], sum [K][D] and (with pick int32 [K]) cand [K][D] of z_e [B][D][Tz], idx int64 [B][Tz]."""
+    B, D, Tz = z_e.shape
+    L.require_cuda(z_e, idx, pick, cnt, sum, cand)
+    if (pick is None) != (cand is None):
+        raise ValueError('pick and cand go together')
+    _need(z_e, B * D * Tz, 'z_e')
+    if idx.dtype != torch.int64 or idx.numel() < B * Tz:
+        raise ValueError('idx must be int64 [B][Tz]')
+    _need_i32(cnt, K, 'cnt')
+    _need(sum, K * D, 'sum')
+    if pick is not None:
+        _need_i32(pick, K, 'pick')
+        _need(cand, K * D, 'cand')
+    L.check(L.lib().vqw_vq_cluster_stats(L.ptr(z_e), L.ptr(idx), L.ptr(pick), L.ptr(cnt), L.ptr(sum), L.ptr(cand), B, D, Tz, K,
+                                         L.stream()))
+
+
+def vq_codebook_ema_step(emb, n, m, *, cnt, sum, cand=None, decay, restart=0.0, info, skip=None):
+    """vqw_vq_codebook_ema_step on emb [K][D], n [K], m [K][D] in place; info int32 [8] ([0] restarted, [1] codes with
+    cnt > 0; the rest is the kernel's, zero before the first call); skip: device int32, non-zero = nothing is written."""
+    K, D = emb.shape
+    L.require_cuda(emb, n, m, cnt, sum, cand, info, skip)
+    g, h, tau = codebook_ema_constants(decay, restart)
+    if g == 0.0:
+        raise ValueError('vq_codebook_ema_step: codebook_ema is 0 (off)')
+    if tau > 0.0 and cand is None:
+        raise ValueError('vq_codebook_ema_step: a restart threshold needs cand')
+    _need(emb, K * D, 'emb')
+    _need(n, K, 'n')
+    _need(m, K * D, 'm')
+    _need_i32(cnt, K, 'cnt')
+    _need(sum, K * D, 'sum')
+    if cand is not None:
+        _need(cand, K * D, 'cand')
+    _need_i32(info, 8, 'info')
+    if skip is not None:
+        _need_i32(skip, 1, 'skip')
+    L.check(L.lib().vqw_vq_codebook_ema_step(L.ptr(emb), L.ptr(n), L.ptr(m), L.ptr(cnt), L.ptr(sum), L.ptr(cand), g, h, tau,
+                                             L.ptr(info), L.ptr(skip), K, D, L.stream()))
+
+
 def jitter_thresholds(p):
     """(lo, hi) of vqw_time_jitter_fwd for a jitter probability p in [0, 1]: fp32(p / 2) and fp32(1 - p / 2), each computed
     in float64 and rounded once.  A frame moves left where u < lo, right where u >= hi."""

@@ -70,6 +70,17 @@ def prefill_window(t_end, ks, dilations, pre_k, ratio):
     return W, s0, end
 
 
+def mix_seed(*words):
+    """splitmix64 over integer words: the seed of a device generator that is a pure function of them (jitter_uniforms, codebook_uniforms)."""
+    seed = 0
+    for v in words:
+        seed = (seed ^ (int(v) & 0xFFFFFFFFFFFFFFFF)) + 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF
+        seed = (seed ^ (seed >> 30)) * 0xBF58476D1CE4E5B9 & 0xFFFFFFFFFFFFFFFF
+        seed = (seed ^ (seed >> 27)) * 0x94D049BB133111EB & 0xFFFFFFFFFFFFFFFF
+        seed ^= seed >> 31
+    return seed >> 1
+
+
 def same_pads(n, k, s):
     """TF 'SAME' padding (left, right) -- SURVEY.md Appendix A-4."""
     out = -(-n // s)
@@ -92,7 +103,14 @@ class VQVAE:
     _time_jitter = 0.0     # probability that a latent frame the decoder reads is its neighbour's (time_jitter; 0 = off)
     jitter_seed = 0        # seed of the jitter draws (jitter_uniforms); not part of state_dict
     _jitter_gen = None     # the device generator of jitter_uniforms
-    _jitter_step = None    # the step whose forward pass is running inside train_step; None: no jitter (forward(), evaluate, ...)
+    _jitter_step = None    # the step whose forward pass is running inside train_step; None: no jitter, no cluster statistics (forward(), evaluate, ...)
+    _codebook_ema = 0.0    # decay of the codebook's moving averages (codebook_ema; 0 = off: Adam trains the codebook)
+    _codebook_restart = 0.0    # a code whose moving count falls below this is restarted on an encoder output (codebook_restart; 0 = never)
+    codebook_seed = 0      # seed of the restart picks (codebook_uniforms); not part of state_dict
+    _codebook_gen = None   # the device generator of codebook_uniforms
+    vq_ema_n = None        # fp32 [K]: moving count per code, and
+    vq_ema_m = None        # fp32 [K][D]: moving sum of the encoder outputs assigned to it (made at the first such step / by load_state_dict)
+    _cb_info = None        # int32 [8]: vqw_vq_codebook_ema_step's info
 
     def __init__(self, model_cfg, wavenet_cfg, num_speakers, device='cuda', seed=0):
         self.m, self.w = model_cfg, wavenet_cfg
@@ -195,6 +213,8 @@ class VQVAE:
         self.beta = float(model_cfg['beta'])
         self.use_vq = bool(model_cfg.get('use_vq', True))     # false: z_q = e_k = z_e, reconstruction loss only (model.py:139-141)
         self.time_jitter = model_cfg.get('time_jitter', 0.0)  # train_step only: latent frames the decoder reads move
+        # the codebook as moving averages of the encoder outputs instead of an Adam-trained variable
+        self._set_codebook(model_cfg.get('codebook_ema', 0.0), model_cfg.get('codebook_restart', 0.0))
         # speaker_embedding = 0: the one-hot speaker vector itself is the global condition (model.py:19-27 leaves self.h
         # as [B, 1, num_speakers]); its width is padded to a multiple of 16 channels for the conv engine (the extra
         # condition rows are always zero, their kernel rows never receive a gradient)
@@ -655,6 +675,10 @@ class VQVAE:
         zq, zq_bs = (self._jitter_buffers(ws)['zq'], D * Tz) if jit else (ws['cond'], self.Cc * Tz)
         if self.use_vq:
             K.vq_nearest_fwd(ws['z_e'], P['embedding'], idx=ws['idx'], e_k=ws['e_k'], zq=zq, zq_bstride=zq_bs, mind=ws['mind'])
+            if self._codebook_ema > 0.0:      # (a train_step's passes only) the cluster statistics the codebook's update reads
+                ws['cb_stats'] = self._jitter_step is not None
+                if ws['cb_stats']:
+                    self._cluster_stats(ws, self._jitter_step)
         else:                       # z_q = e_k = z_e (model.py:139-141): a copy, no quantisation losses
             (zq if jit else zq[:, :D]).copy_(ws['z_e'])
             ws['idx'].zero_()
@@ -698,13 +722,7 @@ class VQVAE:
         if self._jitter_gen is None:
             self._jitter_gen = torch.Generator(device=self.dev)
         rank = self.grad_sync.rank if self.grad_sync is not None else 0
-        seed = 0
-        for v in (self.jitter_seed, step, rank):      # splitmix64 over the three words
-            seed = (seed ^ (int(v) & 0xFFFFFFFFFFFFFFFF)) + 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF
-            seed = (seed ^ (seed >> 30)) * 0xBF58476D1CE4E5B9 & 0xFFFFFFFFFFFFFFFF
-            seed = (seed ^ (seed >> 27)) * 0x94D049BB133111EB & 0xFFFFFFFFFFFFFFFF
-            seed ^= seed >> 31
-        self._jitter_gen.manual_seed(seed >> 1)
+        self._jitter_gen.manual_seed(mix_seed(self.jitter_seed, step, rank))
         return torch.rand(B, Tz, generator=self._jitter_gen, device=self.dev)
 
     def jitter_moved(self, ws):
@@ -715,8 +733,122 @@ class VQVAE:
         src = ws['jitter_src']
         return float((src != torch.arange(ws['Tz'], dtype=torch.int32, device=self.dev)).float().mean())
 
+    # ------------------------------------------------------------------ codebook by moving averages
+    @property
+    def codebook_ema(self):
+        """Decay of the codebook's moving averages (sonnet's VectorQuantizerEMA).  0: off, the codebook is an Adam-trained
+        variable and the step is what it was without this attribute.  0 < decay < 1: train_step moves the codebook to the moving
+        average of the encoder outputs assigned to each code, it gets no gradient and `loss` has no codebook term."""
+        return self._codebook_ema
+
+    @codebook_ema.setter
+    def codebook_ema(self, value):
+        self._set_codebook(value, self._codebook_restart)
+
+    @property
+    def codebook_restart(self):
+        """Threshold below which a code's moving count makes it dead: it is restarted on an encoder output of the batch.
+        0: never.  Needs codebook_ema."""
+        return self._codebook_restart
+
+    @codebook_restart.setter
+    def codebook_restart(self, value):
+        self._set_codebook(self._codebook_ema, value)
+
+    def _set_codebook(self, decay, restart):
+        K.codebook_ema_constants(decay, restart)      # (refuses what is no decay / no threshold)
+        if (float(decay) != 0.0 or float(restart) != 0.0) and not self.use_vq:
+            raise ValueError('codebook_ema / codebook_restart need a codebook (use_vq is false)')
+        self._codebook_ema, self._codebook_restart = float(decay), float(restart)
+
+    def _world(self):
+        """(world, rank) of the exchange of the cluster statistics: (1, 0) unless a data-parallel grad_sync is active."""
+        gs = self.grad_sync
+        return (gs.world, gs.rank) if gs is not None and gs.active else (1, 0)
+
+    def _codebook_buffers(self, ws):
+        """The statistics of a pass, made at the first such step: cnt int32 [K] and ONE fp32 buffer sum [K][D] | cand [K][D] |
+        float(cnt) [K] (what the data-parallel ranks exchange in one all-reduce)."""
+        if 'cb_pack' not in ws:
+            Kc, D, dev = self.Kc, self.D, self.dev
+            if ws['B'] * ws['Tz'] * self._world()[0] > 2 ** 24:
+                raise ValueError('codebook_ema: more than 2^24 frames per step (the ranks exchange the counts as fp32, exact up to there)')
+            with A.record(ws['_poison']):
+                ws['cb_pack'] = A.empty(Kc * (2 * D + 1), device=dev)
+                ws['cb_u'] = A.empty(Kc, device=dev)
+            ws['cb_sum'], ws['cb_cand'] = ws['cb_pack'][:Kc * D].view(Kc, D), ws['cb_pack'][Kc * D:2 * Kc * D].view(Kc, D)
+            ws['cb_cntf'] = ws['cb_pack'][2 * Kc * D:]
+            ws['cb_cnt'] = torch.zeros(Kc, dtype=torch.int32, device=dev)
+            ws['cb_pick'] = torch.zeros(Kc, dtype=torch.int32, device=dev)
+        return ws
+
+    def _cluster_stats(self, ws, step):
+        """cnt / sum of the un-jittered z_e, idx of this pass and, with restarts on, cand = the frame pick[k] = min(int(u[k] * Nf), Nf - 1)
+        (an fp32 product; the kernel clamps) for u = codebook_uniforms(K, step)."""
+        self._codebook_buffers(ws)
+        pick = cand = None
+        if self._codebook_restart > 0.0:
+            pick, cand = ws['cb_pick'], ws['cb_cand']
+            torch.mul(self.codebook_uniforms(self.Kc, step), float(ws['B'] * ws['Tz']), out=ws['cb_u'])
+            pick.copy_(ws['cb_u'])                    # (fp32 -> int32: truncation)
+        K.vq_cluster_stats(ws['z_e'], ws['idx'], cnt=ws['cb_cnt'], sum=ws['cb_sum'], pick=pick, cand=cand, K=self.Kc)
+
+    def codebook_uniforms(self, Kc, step):
+        """The uniforms [K] (fp32 in [0, 1), on the device) behind step `step`'s restart picks: a pure function of
+        (codebook_seed, step) -- a device generator of its own, seeded again at every call as jitter_uniforms seeds its one, so
+        the global torch RNG is never touched and the attempt, its fp32 repeat and a deferred step run again draw the same
+        picks.  No host sync.  Every data-parallel rank draws the same values (and picks among its own frames)."""
+        if self._codebook_gen is None:
+            self._codebook_gen = torch.Generator(device=self.dev)
+        self._codebook_gen.manual_seed(mix_seed(self.codebook_seed, step, 0x636F6465626F6F6B))      # (the last word keeps the stream apart from the jitter's)
+        return torch.rand(Kc, generator=self._codebook_gen, device=self.dev)
+
+    def _codebook_state(self, reset=False):
+        """vq_ema_n = 1, vq_ema_m = the embedding, made at the first moving-average step (reset: made again from the current
+        embedding).  The embedding's Adam slots are zeroed with it: from here on its gradient is zero, and Adam leaves a variable
+        with zero gradient and zero slots bit for bit (a checkpoint trained the old way arrives with slots that would go on moving it)."""
+        if self.vq_ema_n is None or reset:
+            o, shp = self.seg_off['embedding']
+            self.vq_ema_n = torch.ones(self.Kc, device=self.dev)
+            self.vq_ema_m = self.P['embedding'].detach().clone()
+            self._cb_info = torch.zeros(8, dtype=torch.int32, device=self.dev)
+            self.adam_m[o:o + math.prod(shp)].zero_()
+            self.adam_v[o:o + math.prod(shp)].zero_()
+
+    def _codebook_step(self, ws, skip=None):
+        """The codebook's update from the statistics of the pass that is kept, enqueued right before apply_gradients (skip: as
+        there).  Data parallel: the ranks first sum sum | cand | float(cnt) in one all-reduce on this stream; cand[k] comes from
+        rank k % world alone (the others contribute zeros), so every rank applies the same restart."""
+        if not (self._codebook_ema > 0.0 and ws.get('cb_stats')):
+            return
+        self._codebook_state()
+        restart = self._codebook_restart
+        if self.grad_sync is not None and self.grad_sync.active:
+            ws['cb_cntf'].copy_(ws['cb_cnt'])
+            if restart > 0.0:
+                if ws.get('cb_world') != self._world():      # codes whose restart candidate another rank supplies
+                    ws['cb_world'] = world, rank = self._world()
+                    ws['cb_other'] = (torch.arange(self.Kc, device=self.dev) % world != rank).view(self.Kc, 1)
+                ws['cb_cand'].masked_fill_(ws['cb_other'], 0.0)
+            else:
+                ws['cb_cand'].zero_()
+            self.grad_sync.all_reduce_sum(ws['cb_pack'])
+            ws['cb_cnt'].copy_(ws['cb_cntf'])
+        K.vq_codebook_ema_step(self.P['embedding'], self.vq_ema_n, self.vq_ema_m, cnt=ws['cb_cnt'], sum=ws['cb_sum'],
+                               cand=ws['cb_cand'] if restart > 0.0 else None, decay=self._codebook_ema, restart=restart,
+                               info=self._cb_info, skip=skip)
+
+    def codebook_info(self):
+        """{'used': codes that won a frame, 'restarted': codes restarted} in the last applied moving-average step (zeros before
+        the first).  Synchronises."""
+        self.finish_steps()
+        used = restarted = 0
+        if self._cb_info is not None:
+            restarted, used = self._cb_info[:2].tolist()
+        return {'used': used, 'restarted': restarted}
+
     def _forward_step(self, x, spk, step):
-        """forward() as a pass of training step `step`: the only passes that jitter the latents."""
+        """forward() as a pass of training step `step`: the only passes that jitter the latents and compute the codebook's cluster statistics."""
         self._jitter_step = step
         try:
             return self.forward(x, spk)
@@ -1055,6 +1187,8 @@ class VQVAE:
         recon = v[0] / (ws['B'] * ws['T'])
         vq = v[1] / (ws['B'] * ws['Tz'] * self.D) if self.use_vq else 0.0   # model.py:100
         commit = self.beta * vq                             # model.py:103 (same forward value)
+        if self._codebook_ema > 0.0:                        # the codebook term is not optimised (sonnet's VectorQuantizerEMA)
+            return recon + commit, recon, vq, commit
         return recon + vq + commit, recon, vq, commit
 
     def summaries(self, ws, bins=30):
@@ -1392,7 +1526,8 @@ class VQVAE:
             K.time_jitter_bwd(ws['dcond'], ws['jitter_src'], dzq, D=D, dout_bstride=self.Cc * Tz)
         if self.use_vq:
             K.vq_nearest_bwd(ws['z_e'], ws['e_k'], ws['idx'], dzq=dzq, dzq_bstride=dzq_bs, dz_e=ws['dz'],
-                             demb=G['embedding'], cscale=2.0 * self.beta / nd, escale=2.0 / nd, K=self.Kc)
+                             demb=None if self._codebook_ema > 0.0 else G['embedding'],      # (moving averages: no codebook-loss gradient)
+                             cscale=2.0 * self.beta / nd, escale=2.0 / nd, K=self.Kc)
         elif not ws.get('jittered'):
             ws['dz'].copy_(ws['dcond'][:, :D])
         if self.enc != '64':
@@ -1628,6 +1763,7 @@ class VQVAE:
             # next step's scales of the planes written inside the kernels (max-abs * scale in [2^12, 2^13): 8x headroom)
             n0 = self.SL['G']
             K.f16x3_update_scales(self.x3_amax[n0:], self.x3_scale[n0:], target_exp=13)
+        self._codebook_step(ws)
         self.apply_gradients(1.0 / world)
         return ws
 
@@ -1653,6 +1789,7 @@ class VQVAE:
             self._in_step = False
         world = self.grad_sync.finish() if self.grad_sync is not None else 1
         if not (ws.get('x3_used') or ws.get('enc_x3')):       # nothing on the guarded engine in this workspace
+            self._codebook_step(ws)
             self.apply_gradients(1.0 / world)
             return ws
         if self.grad_sync is not None and self.grad_sync.active:
@@ -1661,6 +1798,7 @@ class VQVAE:
         n0 = self.SL['G']
         K.f16x3_update_scales(self.x3_amax[n0:], self.x3_scale[n0:], target_exp=13, skip=self.x3_void)
         gs0 = self.global_step
+        self._codebook_step(ws, skip=self.x3_void)
         self.apply_gradients(1.0 / world, skip=self.x3_void)
         if self._void_host is None:
             self._void_host = torch.zeros(4, dtype=torch.int32).pin_memory()
@@ -1803,9 +1941,13 @@ class VQVAE:
         self.finish_steps()
         # x3_scale: the guarded engine's power-of-two plane scales (measured by the last step, used by the next): with them a
         # resumed run continues exactly as the uninterrupted one would (without them its first step runs on the start-up scales)
-        return {'flat': self.flat, 'ema': self.ema, 'adam_m': self.adam_m, 'adam_v': self.adam_v,
-                'bn_mean': self.bn_mean, 'bn_var': self.bn_var, 'x3_scale': self.x3_scale,
-                'global_step': torch.tensor(self.global_step, dtype=torch.int64)}
+        sd = {'flat': self.flat, 'ema': self.ema, 'adam_m': self.adam_m, 'adam_v': self.adam_v,
+              'bn_mean': self.bn_mean, 'bn_var': self.bn_var, 'x3_scale': self.x3_scale,
+              'global_step': torch.tensor(self.global_step, dtype=torch.int64)}
+        if self._codebook_ema > 0.0:      # the codebook's moving averages (before the first such step: n = 1, m = the embedding)
+            self._codebook_state()
+            sd.update(vq_ema_n=self.vq_ema_n, vq_ema_m=self.vq_ema_m)
+        return sd
 
     def load_state_dict(self, sd):
         self.finish_steps()
@@ -1814,3 +1956,11 @@ class VQVAE:
         if 'x3_scale' in sd and tuple(sd['x3_scale'].shape) == tuple(self.x3_scale.shape):      # (absent in round-2 files)
             self.x3_scale.copy_(sd['x3_scale'].to(self.dev))
         self.global_step = int(sd['global_step'])
+        if self._codebook_ema > 0.0:
+            # a state saved without the moving averages (trained the old way): n = 1, m = the loaded embedding, its Adam slots zeroed
+            if 'vq_ema_n' in sd and 'vq_ema_m' in sd:
+                self.vq_ema_n = sd['vq_ema_n'].to(self.dev, torch.float32).clone().reshape(self.Kc)
+                self.vq_ema_m = sd['vq_ema_m'].to(self.dev, torch.float32).clone().reshape(self.Kc, self.D)
+                self._cb_info = torch.zeros(8, dtype=torch.int32, device=self.dev)
+            else:
+                self._codebook_state(reset=True)

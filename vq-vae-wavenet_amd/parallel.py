@@ -53,3 +53,10 @@ class GradAllReduce:
         if self.active:
             dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
         return t
+
+    def all_reduce_sum(self, t):
+        """In-place SUM over the ranks on the caller's stream (the codebook's cluster statistics, DESIGN 3.11: every rank must
+        apply the same update).  Active under the same condition as all_reduce_max."""
+        if self.active:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return t
