@@ -1,4 +1,4 @@
-"""The bf16 engine's contractions (VQW_X3_BF16: the BF = true instantiations of csrc/gate_f16x3.hip) against a bf16-rounded
+"""The bf16 engine's contractions (VQW_X3_BF16: the BF = true instantiations of csrc/f16x3_*.hip) against a bf16-rounded
 float64 reference.
 
 A bf16 x bf16 product is exact in fp32, so with operands rounded to bf16 (round to nearest even, x3_ref.bf16_round) a kernel differs

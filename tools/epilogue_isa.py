@@ -2,8 +2,9 @@
 
     python tools/epilogue_isa.py [--asm FILE.s] [--keep FILE.s] > profiles/epilogue_isa_<tag>.txt
 
-Compiles vq-vae-wavenet_amd/csrc/gate_f16x3.hip to gfx950 assembly with build.py's FLAGS (two to three minutes; --asm reads an
-assembly file made earlier instead) and prints, for every *_f16x3_kernel instantiation, the vector-memory instructions
+Compiles the sources of the fp16x3 engine that hold *_f16x3_kernel instantiations (vq-vae-wavenet_amd/csrc/f16x3_*.hip, SRCS) to
+gfx950 assembly with build.py's FLAGS, side by side (under a minute), into ONE listing (--keep keeps it; --asm reads a listing made
+earlier instead) and prints, for every *_f16x3_kernel instantiation, the vector-memory instructions
 behind its last v_mfma in text order:
 
     L  a load (global / buffer / flat)         S  a 4-byte store         P  a wider store (plane entries)
@@ -24,6 +25,7 @@ block-uniform branch they follow one another (the FIFO is emptied at s_endpgm an
 Only loads, stores and wait counts are looked at."""
 import argparse
 import importlib.util
+from concurrent.futures import ThreadPoolExecutor
 import os
 import re
 import subprocess
@@ -31,15 +33,18 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'vq-vae-wavenet_amd', 'csrc', 'gate_f16x3.hip')
+SRCS = [os.path.join(ROOT, 'vq-vae-wavenet_amd', 'csrc', 'f16x3_%s.hip' % n) for n in ('conv', 'gate_bwd', 'sconv', 'wgrad')]
 
 
 def compile_asm(out):
     spec = importlib.util.spec_from_file_location('vqw_build', os.path.join(ROOT, 'vq-vae-wavenet_amd', 'build.py'))
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
-    cmd = [b._hipcc()] + b.FLAGS + ['--cuda-device-only', '-S', SRC, '-o', out]
-    subprocess.run(cmd, check=True)
+    cmd = [b._hipcc()] + b.FLAGS + ['--cuda-device-only', '-S', '-o', '-']
+    with ThreadPoolExecutor(len(SRCS)) as ex:
+        parts = list(ex.map(lambda s: subprocess.run(cmd + [s], check=True, capture_output=True, text=True).stdout, SRCS))
+    with open(out, 'w') as f:
+        f.write(''.join(parts))
 
 
 def demangle(names):
@@ -151,7 +156,7 @@ def main():
         path = a.keep
         if not path:
             tmp = tempfile.mkdtemp()
-            path = os.path.join(tmp, 'gate_f16x3.s')
+            path = os.path.join(tmp, 'f16x3.s')
         compile_asm(path)
     kernels, name, body = {}, None, []
     meta = {}
