@@ -23,6 +23,12 @@ speaker; the wav holds them verbatim, then `length - N` generated samples.  `-pr
 prefills the prior with the utterance's first N codes (encode_codes), samples `-frames` more, and decodes all N + frames codes
 with the audio generator prefilled with the utterance's first N x 64 samples (which the wav holds verbatim); the codes file
 holds all N + frames codes.  With `-seed`, uniforms are drawn for the generated samples / codes only.
+
+`-teacher_forced` with `-audio` and `-speakers`: no autoregression.  The decoder is given the TRUE past of the utterance and
+every sample is decided from its logits in one pass (VQVAE.reconstruct), by `-mode` with `-seed / -temperature / -top_k /
+-top_p`: what the decoder predicts when nothing it predicted is fed back.  The utterance is trimmed to a multiple of the
+encoder's ratio, zero-padded to a multiple of lcm(256, ratio) as evaluate.py pads, reconstructed with its true length and
+trimmed back; `<dir>/<step>_<speaker>_teacher.wav` is written for every speaker.  Not with `-prior` or a prompt.
 """
 import importlib
 import json
@@ -60,7 +66,13 @@ def main():
                         help='with -audio: continue the first N samples of the utterance instead of generating from nothing')
     parser.add_argument('-prompt_frames', default=0, type=int,
                         help='with -prior and -audio: continue the first N codes (N x 64 samples) of the utterance')
+    parser.add_argument('-teacher_forced', action='store_true',
+                        help='with -audio: the decoder\'s one-pass reconstruction given the true past (<step>_<speaker>_teacher.wav)')
     args = parser.parse_args()
+    if args.teacher_forced and (args.prior_path is not None or args.prompt_samples or args.prompt_frames):
+        parser.error('-teacher_forced reconstructs -audio in one pass: not with -prior, -prompt_samples or -prompt_frames')
+    if args.teacher_forced and args.audio_path is None:
+        parser.error('-teacher_forced needs -audio (the utterance whose true past the decoder is given)')
     if args.prior_path is None and args.audio_path is None:
         parser.error('-audio is required (or -prior to sample codes from a latent prior)')
     if args.prompt_samples < 0 or args.prompt_frames < 0:
@@ -89,6 +101,8 @@ def main():
     from scipy.io import wavfile
     if args.prior_path is not None:
         return generate_from_prior(args, pkg, gs, rank, world, dev, parser)
+    if args.teacher_forced:
+        return teacher_forced(args, pkg, gs, rank, world, dev, parser)
     wav = read_wav(args.audio_path)
     length = len(wav)
     n_prompt = args.prompt_samples
@@ -136,7 +150,7 @@ def main():
             print('wrote', save_path + '/%d_%s.wav' % (gs, s))
 
 
-def read_wav(path):
+def read_wav(path, multiple=512):
     """The utterance as float32 at 16 kHz, trimmed to a multiple of 512 samples (generate.py:39, 512 = largest dilation)."""
     from scipy.io import wavfile
     sr, wav = wavfile.read(path)
@@ -148,7 +162,7 @@ def read_wav(path):
         from scipy.signal import resample_poly
         g = gcd(sr, 16000)
         wav = resample_poly(wav, 16000 // g, sr // g).astype(np.float32)
-    return wav[:len(wav) // 512 * 512]
+    return wav[:len(wav) // multiple * multiple]
 
 
 def speaker_ids(args, pkg):
@@ -180,6 +194,42 @@ def load_vqvae(args, pkg, parameters, wavenet_parameters, num_speakers, dev):
         model.load_state_dict(torch.load(args.restore_path, map_location='cpu', weights_only=True))
         model.use_ema_weights()                # generate.py:88-90
     return model
+
+
+def teacher_forced(args, pkg, gs, rank, world, dev, parser):
+    """The decoder's teacher-forced reconstruction of the utterance for every speaker: one pass, no generator."""
+    from math import gcd
+    from scipy.io import wavfile
+    num_speakers, ids = speaker_ids(args, pkg)
+    parameters, wavenet_parameters = pkg.model.load_configs(args.parameter_path)
+    ratio = 320 if parameters.get('encoder', '64') == '2019' else 64
+    wav = read_wav(args.audio_path, multiple=ratio)
+    length = len(wav)
+    if length == 0:
+        parser.error('-audio: the utterance is shorter than one latent frame (%d samples)' % ratio)
+    model = load_vqvae(args, pkg, parameters, wavenet_parameters, num_speakers, dev)     # the EMA weights are the live ones now
+    save_path = args.restore_path.split('/weights')[0]
+    lcm = 256 * ratio // gcd(256, ratio)
+    padded = -(-length // lcm) * lcm
+    mine = list(range(rank, len(ids), world))
+    uniforms = None
+    if args.mode == 'sample' and mine:     # one row of uniforms per requested speaker, whatever the sharding
+        g = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
+        uniforms = torch.zeros(len(mine), padded)
+        uniforms[:, :length] = torch.rand(len(ids), length, generator=g)[mine]
+    for b0 in range(0, len(mine), 8):
+        rows = mine[b0:b0 + 8]
+        x = torch.zeros(len(rows), padded)
+        x[:, :length] = torch.from_numpy(wav)
+        spk = torch.tensor([ids[i] for i in rows], dtype=torch.int64, device=dev)
+        audio, _ = model.reconstruct(x.to(dev), spk, lengths=[length] * len(rows), weights='live', mode=args.mode,
+                                     uniforms=None if uniforms is None else uniforms[b0:b0 + len(rows)].contiguous().to(dev),
+                                     temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
+        audio = audio[:, :length].cpu().numpy()
+        for j, i in enumerate(rows):
+            s = 'no_speaker' if args.speakers[i] == 'None' else args.speakers[i]
+            wavfile.write(save_path + '/%d_%s_teacher.wav' % (gs, s), 16000, audio[j])
+            print('wrote', save_path + '/%d_%s_teacher.wav' % (gs, s))
 
 
 def generate_from_prior(args, pkg, gs, rank, world, dev, parser):

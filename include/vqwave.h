@@ -467,6 +467,25 @@ int vqw_ar_decode_run_group_sampled_async(vqw_ar_decoder* const* hs, int n, cons
                                           int ratio, int n_steps, int mode, const float* const* uniforms,
                                           const vqw_ar_sampling* const* sampling, float* const* audio,
                                           int32_t* const* indices, float* const* probs_last, vqw_stream_t s);
+/* Teacher-forced sampling: one class for EVERY position of logits [B][Q][T] (the layout vqw_softmax_score reads) in one
+ * pass.  For a position (b, t) with t_begin[b] <= t < t_end[b] (device int32 [B]; either may be NULL: 0 / T):
+ *   mode 0 (greedy): idx = the LOWEST index among the maxima of z = logits[b][:][t] -- the "hit" of vqw_softmax_score and
+ *                    the generators' greedy decision; probs = softmax(z);
+ *   mode 1 (sample): steps 1-4 above with row b's settings (`rows`: a HOST array of B entries, NULL = every row at its
+ *                    defaults) and u = uniforms[b][t] (fp32 [B][T] in [0, 1]); probs = the q drawn from.
+ * Outside the range idx = -1, audio = 0, probs = 0.  idx int32 [B][T]; audio fp32 [B][T] or NULL: the mu-law decode of
+ * idx (Q must be 256), bit-equal to vqw_mu_law_decode_f32; probs fp32 [B][T][Q] or NULL (one position's distribution is
+ * one contiguous row).  Non-finite logits are not special-cased; idx is clamped to [0, Q).
+ * Mode 1 runs the generators' tempered / truncated sampling code for every position, default rows included (with top_k
+ * and top_p off that code skips both truncations).  A truncated row therefore runs exactly the device code the
+ * generators run; NO bit-equality with the generators' DEFAULT path is promised: that path keeps a serial cdf in another
+ * summation order.  Every sum has one fixed order, there are no atomics, a row's output depends on that row's inputs
+ * only, and the bits are the same on every launch.
+ * Errors (before any launch): null logits / idx; B, T < 1; Q < 1, Q > 1024 or Q % 4 != 0; mode not 0 or 1; mode 1
+ * without uniforms; non-default `rows` with mode 0, or invalid ones; audio with Q != 256.                            */
+int vqw_softmax_sample(const float* logits, const float* uniforms, const vqw_ar_sampling* rows,
+                       const int32_t* t_begin, const int32_t* t_end, int mode, int32_t* idx, float* audio,
+                       float* probs, int B, int Q, int T, vqw_stream_t s);
 /* Prefill: leave the handle in the state it would have after vqw_ar_decode_reset and t_end steps teacher-forced on a
  * prompt (the input of step t is the prompt's value at t - 1, not a sampled one); the next run continues at step t_end
  * (sample i of it uses encoding[:, :, (t_end + i) / ratio]).  Sequence: vqw_ar_decode_reset, then

@@ -14,6 +14,11 @@ enough, so the curve is comparable from step to step), adds `[eval bits ...]` to
 that step's line of summaries.jsonl.  The list is in the format of the `<name>_train.txt` lists, read under `-data_root` as
 `-eval_dataset` (default: `-dataset`; VCTK when that is synthetic).
 
+`-audio_interval N [-audio_count 2] [-audio_dir DIR]` (needs `-eval_list`): every N steps rank 0 reconstructs the first
+`-audio_count` rows of the first held-out batch with the EMA weights (VQVAE.reconstruct: teacher forced, mode sample, seed 0,
+default settings) and writes `DIR/<step>_<k>_teacher.wav` (float32, 16 kHz; DIR defaults to `audio/` next to `-save`), once
+per run also `DIR/<k>_original.wav`; the console line of that step gains `[audio <count>]`.  0 (the default) = never.
+
 `-clip_norm C`: gradients are clipped to the global norm C (tf.clip_by_global_norm; norm and scale stay on the device).
 `-grad_norm`: the norms are measured and logged, nothing is clipped.  Either adds `[gnorm ...]` to the console line and
 `grad_norm`, `grad_clip_scale` and a per-variable `grad_norms` object to summaries.jsonl, on logged steps.
@@ -69,6 +74,10 @@ def main():
     parser.add_argument('-eval_batches', default=4, type=int, dest='eval_batches', metavar='int', help='held-out batches per evaluation')
     parser.add_argument('-eval_dataset', default=None, dest='eval_dataset', metavar='DATASET', help='dataset the list belongs to (default: -dataset)')
     parser.add_argument('-data_root', default='data/', dest='data_root', metavar='string', help='where the held-out wavs and *_speakers.txt are')
+    parser.add_argument('-audio_interval', default=0, type=int, dest='audio_interval', metavar='int',
+                        help='write teacher-forced reconstructions of held-out rows every N steps (0 = never; needs -eval_list)')
+    parser.add_argument('-audio_count', default=2, type=int, dest='audio_count', metavar='int', help='held-out rows reconstructed each time')
+    parser.add_argument('-audio_dir', default=None, dest='audio_dir', metavar='string', help='where the wavs go (default: audio/ next to -save)')
     parser.add_argument('-clip_norm', default=None, type=float, dest='clip_norm', metavar='float', help='clip gradients to this global norm (> 0)')
     parser.add_argument('-grad_norm', action='store_true', dest='grad_norm', help='log gradient norms without clipping')
     parser.add_argument('-time_jitter', default=None, type=float, dest='time_jitter', metavar='float',
@@ -90,6 +99,10 @@ def main():
         parser.error('-codebook_restart needs -codebook_ema (got -codebook_ema 0)')
     if args.eval_interval < 0 or args.eval_batches < 1:
         parser.error('-eval_interval must be >= 0 and -eval_batches >= 1')
+    if args.audio_interval < 0 or args.audio_count < 1:
+        parser.error('-audio_interval must be >= 0 and -audio_count >= 1')
+    if args.audio_interval > 0 and args.eval_list is None:
+        parser.error('-audio_interval needs -eval_list (the held-out rows it reconstructs)')
     if args.eval_interval > 0 and args.eval_list is None:
         parser.error('-eval_interval needs -eval_list')
     if args.eval_list is not None:
@@ -165,6 +178,15 @@ def main():
         if not crops:
             raise ValueError('-eval_list: no file of %s has %d samples' % (args.eval_list, args.max_len))
         eval_set = list(D.fixed_batches(crops, args.batch_size))
+    audio_dir = None
+    if eval_set is not None and args.audio_interval > 0:
+        audio_dir = args.audio_dir or os.path.join(save_dir, 'audio')
+        os.makedirs(audio_dir, exist_ok=True)
+        _, ax, aspk, _ = eval_set[0]
+        ax, aspk = ax[:args.audio_count].contiguous(), aspk[:args.audio_count].contiguous()
+        from scipy.io import wavfile
+        for k in range(ax.shape[0]):
+            wavfile.write(os.path.join(audio_dir, '%d_original.wav' % k), 16000, ax[k].cpu().numpy())
 
     for step in range(1, 1 + args.num_steps):
         t = time.time()
@@ -172,7 +194,8 @@ def main():
         ws = model.train_step(x, spk)
         gs = model.global_step
         eval_now = eval_set is not None and gs % args.eval_interval == 0
-        if rank == 0 and (gs % args.interval == 0 or step == args.num_steps or eval_now):
+        audio_now = audio_dir is not None and gs % args.audio_interval == 0
+        if rank == 0 and (gs % args.interval == 0 or step == args.num_steps or eval_now or audio_now):
             loss, rl, vq, commit = model.losses(ws)          # synchronises: only every `interval` steps
             extra = {}
             if model.time_jitter > 0:             # from the step's source frames; read here, on logged steps only
@@ -183,6 +206,10 @@ def main():
             if eval_now:
                 extra['eval'] = pkg.scoring.score_batches(model, eval_set, dev, weights='ema').report(
                     'sample', latent_dim=model.D if model.use_vq else 0)
+            if audio_now:
+                rec, _ = model.reconstruct(ax.to(dev), aspk.to(dev), weights='ema', mode='sample', seed=0)
+                for k, row in enumerate(rec.cpu().numpy()):
+                    wavfile.write(os.path.join(audio_dir, '%d_%d_teacher.wav' % (gs, k)), 16000, row)
             t = time.time() - t
             progress = '\r[step %d] %.2f' % (gs, step / args.num_steps * 100) + '%'
             msg = ' [recons %.5f] [vq %.5f] [lr %.5f]' % (rl, vq, model.lr_at(gs - 1))
@@ -196,6 +223,8 @@ def main():
                 msg += ' [codebook used %d/%d restarted %d]' % (extra['codebook_used'], model.Kc, extra['codebook_restarted'])
             if eval_now:
                 msg += ' [eval bits %.5f]' % extra['eval']['bits_per_sample']
+            if audio_now:
+                msg += ' [audio %d]' % ax.shape[0]
             print(progress + msg + display_time(t, (args.num_steps - step) * t), end='', flush=True)
             # the reference writes its merged summaries to a TensorBoard event file here (train.py:104-109); without
             # TensorFlow the same tags go to <save_dir>/summaries.jsonl, one line per logged step

@@ -767,6 +767,43 @@ def softmax_score(logits, labels, *, t_begin=None, t_end=None, nll=None, entropy
     return row_sums, row_counts
 
 
+def softmax_sample(logits, *, mode='sample', uniforms=None, temperature=1.0, top_k=0, top_p=1.0, t_begin=None, t_end=None,
+                   idx=None, audio=None, probs=None):
+    """vqw_softmax_sample: one class for every position of logits fp32 [B][Q][T] over t_begin[b] <= t < t_end[b] (device
+    int32 [B]; None: the whole row).  mode 'greedy': the lowest index among the maxima; 'sample': the generators' tempered /
+    truncated sampling with uniforms fp32 [B][T] in [0, 1] and temperature / top_k / top_p (scalars or one value per row,
+    generator.sampling_settings).  Returns idx int32 [B][T] (-1 outside the range).  audio: optional fp32 [B][T] output, the
+    mu-law decode of idx (Q = 256; 0 outside); probs: optional fp32 [B][T][Q] output, the distribution drawn from (softmax
+    in greedy mode; 0 outside)."""
+    from .generator import sampling_settings
+    if mode not in ('sample', 'greedy'):
+        raise ValueError("softmax_sample: mode must be 'sample' or 'greedy' (got %r)" % (mode,))
+    if logits.dim() != 3:
+        raise ValueError('logits must be float32 [B][Q][T]')
+    B, Q, T = logits.shape
+    settings = sampling_settings(B, mode, temperature, top_k, top_p)
+    if idx is None:
+        idx = torch.empty(B, T, dtype=torch.int32, device=logits.device)
+    L.require_cuda(logits, uniforms, t_begin, t_end, idx, audio, probs)
+    if logits.dtype != torch.float32:
+        raise ValueError('logits must be float32 [B][Q][T]')
+    if mode == 'sample':
+        _need(uniforms, B * T, 'uniforms')
+    _need_i32(t_begin, B, 't_begin')
+    _need_i32(t_end, B, 't_end')
+    _need_i32(idx, B * T, 'idx')
+    if audio is not None:
+        _need(audio, B * T, 'audio')
+    if probs is not None:
+        _need(probs, B * T * Q, 'probs')
+    rows = None
+    if settings is not None:
+        rows = (L.ArSampling * B)(*[L.ArSampling(t, k, p) for t, k, p in settings])
+    L.check(L.lib().vqw_softmax_sample(L.ptr(logits), L.ptr(uniforms) if mode == 'sample' else None, rows, L.ptr(t_begin), L.ptr(t_end),
+                                       1 if mode == 'sample' else 0, L.ptr(idx), L.ptr(audio), L.ptr(probs), B, Q, T, L.stream()))
+    return idx
+
+
 def code_histogram(idx, counts, flag, *, f_end=None):
     """vqw_code_histogram: counts[c] += occurrences of c in idx int64 [B][Tz] over frames f < f_end[b] (device int32 [B];
     None: all).  flag (device int32) is set non-zero by an index outside [0, len(counts)), which is counted nowhere."""

@@ -103,6 +103,7 @@ class VQVAE:
     _time_jitter = 0.0     # probability that a latent frame the decoder reads is its neighbour's (time_jitter; 0 = off)
     jitter_seed = 0        # seed of the jitter draws (jitter_uniforms); not part of state_dict
     _jitter_gen = None     # the device generator of jitter_uniforms
+    _recon_gen = None      # the device generator of reconstruct's uniforms
     _jitter_step = None    # the step whose forward pass is running inside train_step; None: no jitter, no cluster statistics (forward(), evaluate, ...)
     _codebook_ema = 0.0    # decay of the codebook's moving averages (codebook_ema; 0 = off: Adam trains the codebook)
     _codebook_restart = 0.0    # a code whose moving count falls below this is restarted on an encoder output (codebook_restart; 0 = never)
@@ -1110,20 +1111,38 @@ class VQVAE:
         scales, max-abs collectors, range flag and the sticky void flag are bit-identical to what they were: an evaluation
         between two training steps leaves the second step what it would have been.  Synchronises."""
         from . import scoring
+
+        def finish(ws, t_end, f_end):
+            sums, counts = K.softmax_score(ws['logits'], ws['labels'], t_end=t_end, nll=ws['nll'] if per_position else None,
+                                           entropy=ws['entropy'] if per_position else None)
+            out = scoring.Score(nll_sum=sums[:, 0].cpu(), entropy_sum=sums[:, 1].cpu(), count=counts[:, 0].cpu().long(),
+                                hits=counts[:, 1].cpu().long())
+            if per_position:
+                out.nll, out.entropy = ws['nll'].clone(), ws['entropy'].clone()
+            if self.use_vq:
+                self._score_codes(ws, f_end, out)
+            return out
+        return self._teacher_forced('evaluate', x, spk, lengths, weights, finish)
+
+    def _teacher_forced(self, who, x, spk, lengths, weights, finish):
+        """What evaluate and reconstruct share: the argument checks (errors named after `who`), the teacher-forced pass on the
+        score workspace with the EMA or the live weights, forward_checked's handling of the range flag, and the restoration of
+        every piece of training state, also when something raises.  finish(ws, t_end, f_end) turns the pass's logits into the
+        caller's result while the chosen weights are still in place (t_end / f_end: device int32 [B], None without lengths)."""
         if weights not in ('ema', 'live'):
-            raise ValueError("evaluate: weights must be 'ema' or 'live' (got %r)" % (weights,))
+            raise ValueError("%s: weights must be 'ema' or 'live' (got %r)" % (who, weights))
         if x.dim() != 2 or spk.numel() != x.shape[0]:
-            raise ValueError('evaluate: x [B][T] and B speaker ids expected (got %s, %d ids)' % (tuple(x.shape), spk.numel()))
+            raise ValueError('%s: x [B][T] and B speaker ids expected (got %s, %d ids)' % (who, tuple(x.shape), spk.numel()))
         B, T = x.shape
         unit = self._length_unit()
         lens = None
         if lengths is not None:
             lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
             if len(lens) != B:
-                raise ValueError('evaluate: %d lengths for a batch of %d' % (len(lens), B))
+                raise ValueError('%s: %d lengths for a batch of %d' % (who, len(lens), B))
             bad = [v for v in lens if v <= 0 or v > T or v % unit]
             if bad:
-                raise ValueError('evaluate: lengths must be positive multiples of %d and at most T = %d (got %s)' % (unit, T, bad[:5]))
+                raise ValueError('%s: lengths must be positive multiples of %d and at most T = %d (got %s)' % (who, unit, T, bad[:5]))
         self.finish_steps()
         ws = self._workspace(B, T, 'score')
         t_end = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=self.dev)
@@ -1141,21 +1160,56 @@ class VQVAE:
                     self._score_pass(x, spk, ws)
                 finally:
                     self._x3_active = True
-            sums, counts = K.softmax_score(ws['logits'], ws['labels'], t_end=t_end, nll=ws['nll'] if per_position else None,
-                                           entropy=ws['entropy'] if per_position else None)
-            out = scoring.Score(nll_sum=sums[:, 0].cpu(), entropy_sum=sums[:, 1].cpu(), count=counts[:, 0].cpu().long(),
-                                hits=counts[:, 1].cpu().long())
-            if per_position:
-                out.nll, out.entropy = ws['nll'].clone(), ws['entropy'].clone()
-            if self.use_vq:
-                self._score_codes(ws, f_end, out)
-            return out
+            return finish(ws, t_end, f_end)
         finally:
             if live is not None:
                 self.flat.copy_(live)
             for t, saved in guard:
                 t.copy_(saved)
             self._tt_done = set()          # (transposed kernels cached from the parameters: made again on next use)
+
+    def reconstruct(self, x, spk, lengths=None, weights='ema', mode='sample', uniforms=None, seed=0, temperature=1.0, top_k=0,
+                    top_p=1.0, return_probs=False):
+        """The decoder's teacher-forced reconstruction of x [B][T]: exactly the pass evaluate runs (score workspace, EMA or
+        live weights, the fp32 repeat of a flagged pass, the same `lengths` rules, every piece of training state bit-identical
+        afterwards, also when the call raises), then ONE class per position from its logits (kernels.softmax_sample).
+        Returns (audio fp32 [B][T], idx int32 [B][T]) and, with return_probs, probs fp32 [B][T][Q] (the distribution drawn
+        from).  idx[b][t] is the prediction for sample t given x[b][:t]: it aligns with the labels evaluate scores, and
+        mode 'greedy' hits exactly where evaluate counts a hit.  Positions t >= lengths[b] read idx -1, audio 0, probs 0.
+        mode 'sample': temperature / top_k / top_p as FastGenerator.generate takes them (scalars or one value per row) and
+        uniforms fp32 [B][T] in [0, 1]; None: drawn from a device generator of their own seeded with `seed` (as
+        jitter_uniforms does it: the global torch RNG is never touched; the same seed gives the same uniforms, and the same
+        audio wherever two passes make the same logits -- they differ by about 1e-6, DESIGN 3.8, so a draw whose uniform
+        lies that close to a cdf value can differ between two calls).  Synchronises."""
+        return self._reconstruct('reconstruct', x, spk, lengths, weights, mode, uniforms, seed, temperature, top_k, top_p,
+                                 return_probs, audio=True)
+
+    def _reconstruct(self, who, x, spk, lengths, weights, mode, uniforms, seed, temperature, top_k, top_p, return_probs, audio):
+        from .generator import sampling_settings
+        if mode not in ('sample', 'greedy'):
+            raise ValueError("%s: mode must be 'sample' or 'greedy' (got %r)" % (who, mode))
+        if x.dim() == 2:
+            sampling_settings(x.shape[0], mode, temperature, top_k, top_p)      # refused before anything runs
+            if uniforms is not None and (mode != 'sample' or tuple(uniforms.shape) != tuple(x.shape) or uniforms.dtype != torch.float32):
+                raise ValueError("%s: uniforms must be float32 [B][T] and need mode 'sample'" % who)
+
+        def finish(ws, t_end, f_end):
+            B, T = ws['B'], ws['T']
+            u = uniforms
+            if mode == 'sample' and u is None:
+                if self._recon_gen is None:
+                    self._recon_gen = torch.Generator(device=self.dev)
+                self._recon_gen.manual_seed(mix_seed(int(seed)))
+                u = torch.rand(B, T, generator=self._recon_gen, device=self.dev)
+            Q = ws['logits'].shape[1]
+            out_audio = torch.empty(B, T, device=self.dev) if audio else None
+            probs = torch.empty(B, T, Q, device=self.dev) if return_probs else None
+            idx = K.softmax_sample(ws['logits'], mode=mode, uniforms=u, temperature=temperature, top_k=top_k, top_p=top_p,
+                                   t_end=t_end, audio=out_audio, probs=probs)
+            torch.cuda.synchronize(self.dev)
+            out = ((out_audio,) if audio else ()) + (idx,) + ((probs,) if return_probs else ())
+            return out if len(out) > 1 else out[0]
+        return self._teacher_forced(who, x, spk, lengths, weights, finish)
 
     def _score_pass(self, x, spk, ws):
         if A.POISON:

@@ -174,6 +174,15 @@ class LatentPrior(VQVAE):
         self._check_codes(codes, spk)
         return super().evaluate(codes, spk, lengths=lengths, weights=weights, per_position=per_position)
 
+    def reconstruct(self, codes, spk, lengths=None, weights='ema', mode='sample', uniforms=None, seed=0, temperature=1.0, top_k=0,
+                    top_p=1.0, return_probs=False):
+        """The prior's teacher-forced code predictions next to the true codes: idx int32 [B][T] (idx[b][t] is the prediction
+        for code t given codes[b][:t]; -1 at t >= lengths[b]) and, with return_probs, probs fp32 [B][T][k], as
+        VQVAE.reconstruct (the pass evaluate runs, every piece of training state left bit-identical).  No audio: the classes are codes."""
+        self._check_codes(codes, spk)
+        return self._reconstruct('reconstruct', codes, spk, lengths, weights, mode, uniforms, seed, temperature, top_k, top_p,
+                                 return_probs, audio=False)
+
     def speaker_condition(self, spk, Tz):
         """[B][Cc][Tz]: the speaker embedding tiled over Tz frames (the generator's condition)."""
         B = spk.numel()
