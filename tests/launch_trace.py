@@ -1,0 +1,242 @@
+"""The host's launch sequence as data, recorded on the CPU: what test_launch_trace_cpu.py holds a host-side refactor to.
+
+`install(monkeypatch, pkg)` replaces every public function of the `kernels` module by a recorder and torch.cuda's streams and
+events by fakes, so a VQVAE on device='cpu' runs forward() and backward() without a GPU and leaves one entry per call:
+    [name, stream, {scalar / list arguments}, {tensor arguments}]
+with arguments under their parameter names.  A tensor reads [ordinal of its storage in order of first appearance, storage offset,
+numel, dtype]: the role of a buffer, not its address.  Event records, stream waits and grad_sync.bucket_ready ranges are entries
+too.  Nothing is computed; the tensors hold whatever torch.empty left in them.
+
+`CASES` are the shapes and switches under which Encoder_64 takes each of its branches (plus the two other encoders), `LAYOUTS` the
+configurations whose flat-buffer layout, state_dict and reference names are pinned.  tests/golden/launch_trace.json holds the
+SHA-256 of every case's JSON-serialised trace, its call names (for a readable failure) and the layout facts.
+
+    python tests/launch_trace.py --write          # make the golden file again (only ever from a commit whose launches are the truth)
+    python tests/launch_trace.py --dump CASE      # one case's whole trace as text, to diff two commits
+"""
+import contextlib
+import hashlib
+import importlib
+import inspect
+import json
+import os
+import sys
+import types
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, 'golden', 'launch_trace.json')
+
+# the reference's widths, 2 decoder layers, encoder_filters 256: at B = 1, T = 1024 encoder layer 1 has B * T_out = 256 columns (the
+# fp16x3 engine takes it), layers 2..5 are short (split-K)
+WAVENET = {'quantization_channels': 256, 'num_cycles': 1, 'num_cycle_layers': 2, 'dilation_rates': [1, 2], 'kernel_size': 3,
+           'dilation_filters': 256, 'skip_filters': 512, 'residual_filters': 256, 'preprocess': {'kernel_size': 32, 'filters': 256}}
+MODEL = {'encoder': '64', 'use_vq': True, 'speaker_embedding': 64, 'k': 512, 'latent_dim': 64, 'beta': 0.25, 'encoder_filters': 256,
+         'learning_rate_schedule': {'0': 8e-5}}
+SPEAKERS = 109
+
+# model: keys laid over MODEL; env: VQW_* switches (every other VQW_* variable is unset); active: model._x3_active;
+# encode: _encode(save=False) on a train=False workspace instead of forward() + backward(); grad_sync: with the recording stub
+CASES = {
+    'enc64': dict(),
+    'magenta': dict(model={'encoder': 'Magenta'}),
+    '2019': dict(model={'encoder': '2019'}, T=1280),
+    'enc64-engine-fp32': dict(env={'VQW_ENGINE': 'fp32'}),
+    'enc64-fp32-repeat': dict(active=False),
+    'enc64-wgrad-pp-0': dict(env={'VQW_WGRAD_PP': '0'}),
+    'enc64-enc-x3-0': dict(env={'VQW_ENC_X3': '0'}),
+    'enc64-enc-wgrad-x3-0': dict(env={'VQW_ENC_WGRAD_X3': '0'}),
+    'enc64-sconv-split-0': dict(env={'VQW_SCONV_SPLIT': '0'}),
+    'enc64-overlap-0': dict(env={'VQW_OVERLAP': '0'}),
+    'enc64-encode-nosave': dict(encode=True),
+    'enc64-grad-sync': dict(grad_sync=True),
+    # 768 filters: layer 1 has 12 x 8 x 8 = 768 blocks of 64 x 128 (more than 2 per CU: one unsplit conv_gemm, forward and input
+    # gradient), layer 2 has 384 (split in two) -- VQVAE / Encoder64 _short_layer_split
+    'enc64-unsplit': dict(model={'encoder_filters': 768}, env={'VQW_ENGINE': 'fp32'}, B=8, T=4096),
+}
+LAYOUTS = {'%s-vq%d-spk%d' % (enc, vq, spk): {'encoder': enc, 'use_vq': bool(vq), 'speaker_embedding': spk}
+           for enc in ('64', 'Magenta', '2019') for vq in (1, 0) for spk in (64, 0)}
+
+
+class Recorder:
+    def __init__(self):
+        self.trace, self.storages, self.keep = [], {}, []
+        self.main = FakeStream(self, 'main')
+        self.current, self.n_side, self.n_event = self.main, 0, 0
+
+    def tensor(self, t):
+        key = t.untyped_storage().data_ptr()
+        if key not in self.storages:
+            self.storages[key] = len(self.storages)
+            self.keep.append(t)          # (alive until the case ends: no later storage gets this address)
+        return ['tensor', self.storages[key], t.storage_offset(), t.numel(), str(t.dtype)]
+
+    def describe(self, v):
+        """(JSON value, holds a tensor)"""
+        if torch.is_tensor(v):
+            return self.tensor(v), True
+        if isinstance(v, dict):
+            items = {str(k): self.describe(x) for k, x in v.items()}
+            return {k: d for k, (d, _) in items.items()}, any(h for _, h in items.values())
+        if isinstance(v, (list, tuple)):
+            items = [self.describe(x) for x in v]
+            return [d for d, _ in items], any(h for _, h in items)
+        if v is None or isinstance(v, (bool, int, float, str)):
+            return v, False
+        return repr(type(v)), False
+
+    def add(self, name, args):
+        scalars, tensors = {}, {}
+        for k, v in args.items():
+            d, has = self.describe(v)
+            (tensors if has else scalars)[k] = d
+        self.trace.append([name, self.current.name, scalars, tensors])
+
+    def wrap(self, name, fn, result=None):
+        sig = inspect.signature(fn)
+        var_kw = [p.name for p in sig.parameters.values() if p.kind is p.VAR_KEYWORD]
+
+        def recorded(*a, **kw):
+            args = dict(sig.bind(*a, **kw).arguments)
+            for k in var_kw:
+                args.update(args.pop(k, {}))
+            self.add(name, args)
+            return result(*a, **kw) if result else None
+        return recorded
+
+
+class FakeStream:
+    def __init__(self, rec, name):
+        self.rec, self.name = rec, name
+
+    def wait_event(self, ev):
+        self.rec.trace.append(['wait_event', self.name, {'event': ev.n}, {}])
+
+    def wait_stream(self, other):
+        self.rec.trace.append(['wait_stream', self.name, {'stream': other.name}, {}])
+
+
+class FakeEvent:
+    def __init__(self, rec):
+        self.rec, self.n = rec, rec.n_event
+        rec.n_event += 1
+
+    def record(self, stream=None):
+        self.rec.trace.append(['record', (stream or self.rec.current).name, {'event': self.n}, {}])
+
+    def synchronize(self):
+        pass
+
+
+class GradSyncStub:
+    """parallel.GradAllReduce as far as a single-process backward pass uses it: the ranges it is told are final."""
+    rank, world, active = 0, 1, False
+
+    def __init__(self, rec):
+        self.rec = rec
+
+    def bucket_ready(self, lo, hi):
+        self.rec.trace.append(['grad_sync.bucket_ready', self.rec.current.name, {'lo': int(lo), 'hi': int(hi)}, {}])
+
+
+def install(monkeypatch, pkg):
+    """Put the recorder in place of pkg.kernels' public functions and torch.cuda's streams / events; returns it."""
+    rec, K = Recorder(), pkg.kernels
+    results = {'cond_proj_dgrad_scratch': lambda *a, **kw: 4096,
+               'prior_code_buckets': lambda codes, k: (torch.zeros(codes.numel(), dtype=torch.int32), torch.zeros(k + 1, dtype=torch.int32))}
+    for name, fn in vars(K).items():
+        if inspect.isfunction(fn) and fn.__module__ == K.__name__ and not name.startswith('_'):
+            monkeypatch.setattr(K, name, rec.wrap(name, fn, results.get(name)))
+
+    def side_stream(*a, **kw):
+        rec.n_side += 1
+        return FakeStream(rec, 'side%d' % rec.n_side)
+
+    @contextlib.contextmanager
+    def on_stream(s):
+        prev, rec.current = rec.current, s
+        try:
+            yield
+        finally:
+            rec.current = prev
+    monkeypatch.setattr(torch.cuda, 'current_stream', lambda *a, **kw: rec.current)
+    monkeypatch.setattr(torch.cuda, 'Stream', side_stream)
+    monkeypatch.setattr(torch.cuda, 'Event', lambda *a, **kw: FakeEvent(rec))
+    monkeypatch.setattr(torch.cuda, 'stream', on_stream)
+    monkeypatch.setattr(torch.cuda, 'get_device_properties', lambda *a, **kw: types.SimpleNamespace(multi_processor_count=256))
+    return rec
+
+
+def set_switches(monkeypatch, env):
+    for k in [k for k in os.environ if k.startswith('VQW_')]:
+        monkeypatch.delenv(k)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def run_case(monkeypatch, pkg, name):
+    """The trace of CASES[name]: a fresh model under the case's switches, then forward() + backward() (or _encode alone)."""
+    case = CASES[name]
+    set_switches(monkeypatch, case.get('env', {}))
+    rec = install(monkeypatch, pkg)
+    model = pkg.model.VQVAE(dict(MODEL, **case.get('model', {})), dict(WAVENET), SPEAKERS, device='cpu', seed=0)
+    model._x3_active = case.get('active', True)
+    if case.get('grad_sync'):
+        model.grad_sync = GradSyncStub(rec)
+    B, T = case.get('B', 1), case.get('T', 1024)
+    x, spk = torch.zeros(B, T), torch.zeros(B, dtype=torch.int64)
+    del rec.trace[:]                     # (what the constructor checked its settings with)
+    if case.get('encode'):
+        model._encode(x, spk, model._workspace(B, T, train=False), save=False)
+    else:
+        model.backward(x, spk, model.forward(x, spk))
+    return rec.trace
+
+
+def digest(trace):
+    return hashlib.sha256(json.dumps(trace, sort_keys=True, separators=(',', ':')).encode()).hexdigest()
+
+
+def layout_facts(monkeypatch, pkg, name):
+    """What checkpoints and the grad_sync bucket ranges depend on: segments with offsets, state_dict, reference names."""
+    set_switches(monkeypatch, {})
+    model = pkg.model.VQVAE(dict(MODEL, **LAYOUTS[name]), dict(WAVENET), SPEAKERS, device='cpu', seed=0)
+    shapes = lambda d: [[k, list(v.shape)] for k, v in d.items()]                                   # noqa: E731
+    return {'segments': [[n, off, list(shp)] for n, (off, shp) in model.seg_off.items()], 'n_flat': model.n_flat,
+            'state_dict': shapes(model.state_dict()), 'named_parameters': shapes(model.named_parameters()),
+            'named_parameters_ema': shapes(model.named_parameters(ema=True)), 'named_gradients': shapes(model.named_gradients())}
+
+
+def as_text(trace):
+    return '\n'.join(json.dumps(e, sort_keys=True) for e in trace)
+
+
+def main(argv):
+    import pytest
+    sys.path.insert(0, os.path.dirname(HERE))
+    pkg = importlib.import_module('vq-vae-wavenet_amd')
+    if argv[:1] == ['--dump'] and len(argv) == 2 and argv[1] in CASES:
+        with pytest.MonkeyPatch.context() as mp:
+            print(as_text(run_case(mp, pkg, argv[1])))
+        return 0
+    if argv != ['--write']:
+        print(__doc__)
+        return 2
+    golden = {'cases': {}, 'layouts': {}}
+    for name in CASES:
+        with pytest.MonkeyPatch.context() as mp:
+            trace = run_case(mp, pkg, name)
+        golden['cases'][name] = {'sha256': digest(trace), 'calls': [e[0] for e in trace]}
+        print('%-24s %4d entries  %s' % (name, len(trace), golden['cases'][name]['sha256'][:16]))
+    for name in LAYOUTS:
+        with pytest.MonkeyPatch.context() as mp:
+            golden['layouts'][name] = layout_facts(mp, pkg, name)
+    with open(GOLDEN, 'w') as f:
+        json.dump(golden, f, indent=0, sort_keys=True)
+        f.write('\n')
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main(sys.argv[1:]))

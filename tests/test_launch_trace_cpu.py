@@ -1,0 +1,72 @@
+"""The host issues the launches it issued before: every kernel call of forward() + backward() with its arguments, buffer roles,
+streams, event edges and grad_sync ranges, recorded on the CPU (tests/launch_trace.py) and held to the digests in
+tests/golden/launch_trace.json -- for the three encoders and for every branch of Encoder_64's passes (fp16x3 layers, split-K and
+unsplit short layers, plane or register weight gradients, one or two streams, a pass that saves nothing).  Next to it the facts
+checkpoints and the data-parallel bucket ranges rest on: flat-buffer segments and offsets, state_dict keys, reference names."""
+import json
+import os
+import sys
+
+import pytest
+
+sys.path.insert(0, os.path.dirname(__file__))
+import launch_trace as LT  # noqa: E402
+
+with open(LT.GOLDEN) as f:
+    GOLDEN = json.load(f)
+
+
+def test_golden_file_covers_the_cases():
+    assert sorted(GOLDEN['cases']) == sorted(LT.CASES) and sorted(GOLDEN['layouts']) == sorted(LT.LAYOUTS)
+
+
+@pytest.mark.parametrize('name', list(LT.CASES))
+def test_launches_are_the_golden_ones(pkg, name):
+    want = GOLDEN['cases'][name]
+    with pytest.MonkeyPatch.context() as mp:
+        trace = LT.run_case(mp, pkg, name)
+    assert [e[0] for e in trace] == want['calls']
+    assert LT.digest(trace) == want['sha256'], 'same calls, other arguments / buffers / streams: python tests/launch_trace.py --dump %s' % name
+
+
+@pytest.mark.parametrize('name', ['enc64', 'magenta', '2019', 'enc64-grad-sync'])
+def test_a_second_run_gives_the_same_trace(pkg, name):
+    digests = []
+    for _ in range(2):
+        with pytest.MonkeyPatch.context() as mp:
+            digests.append(LT.digest(LT.run_case(mp, pkg, name)))
+    assert digests[0] == digests[1] == GOLDEN['cases'][name]['sha256']
+
+
+def test_the_cases_reach_the_branches_they_are_named_for(pkg):
+    """(so that a golden file made again from other shapes cannot quietly stop covering a branch)"""
+    def traced(name):
+        with pytest.MonkeyPatch.context() as mp:
+            return LT.run_case(mp, pkg, name)
+    names = lambda t: [e[0] for e in t]                                    # noqa: E731
+    base = traced('enc64')
+    assert names(base).count('f16x3_strided_conv') == 2                    # layer 1: forward and input gradient
+    assert sum(1 for e in base if e[0] == 'conv_gemm' and e[2].get('split_k', 0) > 1) == 4     # layers 2..5 forward
+    assert any(e[0] == 'f16x3_wgrad' and 'p_planes' in e[3] and 'p_tap_chunk' in e[2] for e in base)
+    assert {e[1] for e in base} == {'main', 'side1'}
+    assert {e[1] for e in traced('enc64-overlap-0')} == {'main'}
+    assert 'f16x3_strided_conv' not in names(traced('enc64-enc-x3-0')) and 'f16x3_strided_conv' not in names(traced('enc64-fp32-repeat'))
+    assert not any('p_tap_chunk' in e[2] for e in traced('enc64-wgrad-pp-0'))
+    assert not any('split_slab' in e[3] for e in traced('enc64-sconv-split-0')) and any('split_slab' in e[3] for e in base)
+    unsplit = traced('enc64-unsplit')
+    fwd = [e[2].get('split_k', 0) for e in unsplit if e[0] == 'conv_gemm' and e[2].get('in_stride') == 2]
+    bwd = [e[2].get('split_k', 0) for e in unsplit if e[0] == 'conv_gemm' and e[2].get('out_tstride') == 2]
+    assert fwd[:2] == [0, 2] and bwd[-2:] == [0, 0] and bwd[-4:-2] == [-2, -2]     # layer 1 in one piece, layer 2 in two, both ways
+    ranges = [(e[2]['lo'], e[2]['hi']) for e in traced('enc64-grad-sync') if e[0] == 'grad_sync.bucket_ready']
+    assert len(ranges) == 7 and ranges[0][1] > ranges[0][0] and sorted(ranges)[0][0] == 0
+    assert not any(e[3].get('save_r') or e[3].get('save0') for e in traced('enc64-encode-nosave'))
+
+
+@pytest.mark.parametrize('name', list(LT.LAYOUTS))
+def test_layout_state_dict_and_reference_names(pkg, name):
+    with pytest.MonkeyPatch.context() as mp:
+        got = LT.layout_facts(mp, pkg, name)
+    want = GOLDEN['layouts'][name]
+    for key in want:
+        assert got[key] == want[key], key
+    assert sorted(got) == sorted(want)

@@ -1,8 +1,8 @@
 """VQ-VAE-WaveNet on MI355X: host-side mirror of the reference's model assembly.
 
-Mirrors model.py:7-159 (class VQVAE), Encoder/encoder.py:8-26 (Encoder_64),
-Decoder/decoder.py:12-62 (WavenetDecoder) and Decoder/WaveNet/wavenet.py:24-172 (Wavenet) of
-the reference.  The reference builds a TF graph and lets TF autodiff + the TF runtime do the
+Mirrors model.py:7-159 (class VQVAE), Decoder/decoder.py:12-62 (WavenetDecoder) and
+Decoder/WaveNet/wavenet.py:24-172 (Wavenet) of the reference; its three encoders are the classes
+of encoders.py, of which a model holds one (self.encoder).  The reference builds a TF graph and lets TF autodiff + the TF runtime do the
 work; here one training step is an explicit forward + backward sequence of libvqwave kernels
 on (batch, channel, time) fp32 tensors.  PyTorch only owns device memory and streams.
 
@@ -21,9 +21,8 @@ import torch
 
 from . import _alloc as A
 from . import kernels as K
-from .encoders import Encoder2019, EncoderMagenta
+from .encoders import Encoder64, Encoder2019, EncoderMagenta
 
-BN_EPS = 1e-3  # Keras BatchNormalization default epsilon
 DEFAULT_ENGINE = 'f16x3'
 
 # The model's VQW_* switches (tools/README.md), read ONCE, when a model is constructed (VQVAE.sw): field name = variable name.
@@ -81,19 +80,8 @@ def mix_seed(*words):
     return seed >> 1
 
 
-def same_pads(n, k, s):
-    """TF 'SAME' padding (left, right) -- SURVEY.md Appendix A-4."""
-    out = -(-n // s)
-    total = max((out - 1) * s + k - n, 0)
-    return total // 2, total - total // 2
-
-
 def layer_scope(i, num_cycle_layers, scope='decoder'):
     return '%s/cycle_%d/layer_%d' % (scope, 1 + i // num_cycle_layers, 1 + i % num_cycle_layers)
-
-
-def _suffix(i):
-    return '' if i == 0 else '_%d' % i
 
 
 class VQVAE:
@@ -205,7 +193,8 @@ class VQVAE:
     def _setup_front(self, model_cfg, num_speakers):
         """What feeds the WaveNet's condition: encoder, VQ codebook, speaker embedding (hook: prior.LatentPrior has only the last)."""
         self.enc = model_cfg.get('encoder', '64')
-        if self.enc not in ('64', 'Magenta', '2019'):
+        encoders = {'64': Encoder64, 'Magenta': EncoderMagenta, '2019': Encoder2019}
+        if self.enc not in encoders:
             raise NotImplementedError('encoder %s not implemented' % self.enc)
         self.F = model_cfg.get('encoder_filters', 768)
         self.D = model_cfg['latent_dim']
@@ -223,7 +212,8 @@ class VQVAE:
         self.Cs_eff = self.Cs if self.spk_table else (num_speakers + 15) // 16 * 16
         self.Cc_ref = self.D + (self.Cs if self.spk_table else num_speakers)      # the reference's condition width
         self.Cc = self.D + self.Cs_eff
-        self.magenta = {'Magenta': EncoderMagenta, '2019': Encoder2019}[self.enc](self.D) if self.enc != '64' else None
+        self.encoder = encoders[self.enc](self.D, self.F)     # (constants only: every call hands it the model, encoders.py)
+
     def _build_layout(self):
         R, S, Q, L, ks, Cc = self.R, self.S, self.Q, self.L, self.ks, self.Cc
         seg = OrderedDict()  # internal (grouped) tensors of the flat buffer
@@ -251,20 +241,10 @@ class VQVAE:
 
     def _front_segments(self, seg):
         """Flat-buffer segments in front of the WaveNet's: speaker table, encoder, VQ codebook (hook)."""
-        F, D = self.F, self.D
         if self.spk_table:
             seg['speaker_embedding'] = (self.S_spk, self.Cs)
-        if self.enc == '64':
-            seg['enc_w0'] = (5, F)                 # conv1d/kernel [5,1,F]
-            seg['enc_w'] = (5, 5, F, F)            # conv1d_1..5/kernel
-            seg['enc_b'] = (6, F)
-            seg['enc_w6'] = (F, D)                 # conv1d_6/kernel [1,F,D]
-            seg['enc_b6'] = (D,)
-            seg['bn_gamma'] = (6 * F + D,)
-            seg['bn_beta'] = (6 * F + D,)
-        else:
-            seg.update(self.magenta.segments())
-        seg['embedding'] = (self.Kc, D)
+        seg.update(self.encoder.segments())
+        seg['embedding'] = (self.Kc, self.D)
 
     def _pre_w_shape(self):
         """The preprocess kernel: [pre_k][R] over the one input channel (prior: [pre_k][k][R] over one-hot codes)."""
@@ -313,19 +293,12 @@ class VQVAE:
 
     def _init_front(self, P, uus, glorot):
         """Initial values of the _front_segments (hook)."""
-        F, D = self.F, self.D
         if self.spk_table:
             P['speaker_embedding'].copy_(uus((self.S_spk, self.Cs), self.S_spk, 2.0))   # model.py:23-26
         else:
             self.onehot = torch.eye(self.S_spk, self.Cs_eff, device=self.dev)         # row s = one_hot(s), zero padded
-        if self.enc == '64':
-            P['enc_w0'].copy_(glorot((5, F), 5, 1, F))
-            P['enc_w'].copy_(glorot((5, 5, F, F), 5, F, F))
-            P['enc_w6'].copy_(glorot((F, D), 1, F, D))
-            P['bn_gamma'].fill_(1.0)
-        else:
-            self.magenta.init(P, uus if self.enc == 'Magenta' else glorot)
-        P['embedding'].copy_(uus((self.Kc, D), self.Kc, 1.7))                       # model.py:47-49
+        self.encoder.init(P, uus, glorot)
+        P['embedding'].copy_(uus((self.Kc, self.D), self.Kc, 1.7))                  # model.py:47-49
 
     def _alloc_scratch(self):
         dev = self.dev
@@ -342,10 +315,7 @@ class VQVAE:
 
     def _front_scratch(self):
         """Transposed-kernel scratch of the encoder's input-gradient GEMMs (hook)."""
-        F, D, dev = self.F, self.D, self.dev
-        if self.enc == '64':
-            return {'enc_w': A.empty(5, 5, F, F, device=dev), 'enc_w6': A.empty(D, F, device=dev)}
-        return self.magenta.scratch(dev)
+        return self.encoder.scratch(self.dev)
 
     # ------------------------------------------------------------------ reference-name views
     def _named(self, V, bn_stats=True):
@@ -377,27 +347,9 @@ class VQVAE:
 
     def _named_front(self, V, out, bn_stats=True):
         """The _front_segments under the reference's names (hook)."""
-        F, D = self.F, self.D
         if self.spk_table:
             out['speaker_embedding'] = V['speaker_embedding']
-        if self.enc == '64':
-            out['encoder/conv1d/kernel'] = V['enc_w0'].reshape(5, 1, F)
-            for i in range(1, 6):
-                out['encoder/conv1d_%d/kernel' % i] = V['enc_w'][i - 1]
-            for i in range(6):
-                out['encoder/conv1d%s/bias' % _suffix(i)] = V['enc_b'][i]
-            out['encoder/conv1d_6/kernel'] = V['enc_w6'].reshape(1, F, D)
-            out['encoder/conv1d_6/bias'] = V['enc_b6']
-            for i in range(7):
-                n = F if i < 6 else D
-                sl = slice(i * F, i * F + n)
-                out['encoder/batch_normalization%s/gamma' % _suffix(i)] = V['bn_gamma'][sl]
-                out['encoder/batch_normalization%s/beta' % _suffix(i)] = V['bn_beta'][sl]
-                if bn_stats:
-                    out['encoder/batch_normalization%s/moving_mean' % _suffix(i)] = self.bn_mean[sl]
-                    out['encoder/batch_normalization%s/moving_variance' % _suffix(i)] = self.bn_var[sl]
-        else:
-            self.magenta.named(V, out)
+        self.encoder.named(self, V, out, bn_stats)
         if self.use_vq:          # (the reference only creates the codebook under use_vq, model.py:137-138)
             out['embedding/embedding'] = V['embedding']
 
@@ -478,9 +430,6 @@ class VQVAE:
     def _keeps_layer_planes(self):      # the input planes of EVERY layer are kept (1.6 GB at B = 8) for the weight gradients (p_planes)
         return self.x3_all and self.wg_planes
 
-    def _enc_on_engine(self):           # Encoder_64's long strided layers can run on the guarded fp16x3 engine (_front_workspace)
-        return self.x3_guard and self.enc == '64' and self.F % 256 == 0
-
     def _plane_buffers(self, ws, train):
         """The decoder's operand planes (fp16 pairs / bf16) of a training workspace (train: with what only the backward pass reads) or a score workspace."""
         if not self.gate_f16x3:
@@ -529,108 +478,28 @@ class VQVAE:
 
     def _front_workspace(self, B, T, train):
         """The (B, T) workspace up to the condition: inputs / labels, encoder + VQ buffers, ws['cond'] (hook)."""
-        if self.enc == '64':
-            if T % 64 != 0:
-                raise ValueError('length must be a multiple of 64 for Encoder_64 (got %d)' % T)
-            Tz = T // 64
-        else:
-            Tz = self.magenta.latent_len(T)
-        dev, F, D, R, S, Q, L = self.dev, self.F, self.D, self.R, self.S, self.Q, self.L
+        Tz = self.encoder.latent_len(T)
+        dev, D = self.dev, self.D
         e = lambda *s: A.empty(*s, device=dev)  # noqa: E731
         ws = {'B': B, 'T': T, 'Tz': Tz, 'ratio': T // Tz}
-        ws['Tl'] = [T // (2 ** (i + 1)) for i in range(6)]
         ws['inputs'] = e(B, T)
         ws['labels'] = A.empty(B, T, dtype=torch.int32, device=dev)
-        if self.enc == '64':
-            ws['X'] = [e(B, F, t) for t in ws['Tl']]      # BN outputs of encoder layers 0..5
-            if self._enc_on_engine():      # fp16x3 engine for layers 1..3 (StepPlan.enc_x3)
-                ws['eplanes'] = A.empty(2 * B * F * ws['Tl'][0], dtype=torch.float16, device=dev)   # planes of one layer's operand
-                ws['ewp'] = A.empty(5, 2 * 5 * F * F, dtype=torch.float16, device=dev)
-                ws['enc_amax'] = torch.zeros(12, dtype=torch.int32, device=dev)
-                ws['enc_scale'] = torch.ones(12, device=dev)
-                if train:
-                    ws['ewtp'] = A.empty(5, 2 * 5 * F * F, dtype=torch.float16, device=dev)
-                    if self.wg_planes:     # the planes of each layer's input (space-to-depth) and output gradient are KEPT: the strided weight
-                        # gradients read them (p_planes / q_planes) instead of fetching fp32 one float per request (240 MB at B = 8)
-                        ws['esp'] = {i: A.empty(2 * B * F * ws['Tl'][i - 1], dtype=torch.float16, device=dev) for i in range(1, 6)}
-                        ws['edp'] = {i: A.empty(2 * B * F * ws['Tl'][i], dtype=torch.float16, device=dev) for i in range(1, 6)}
-            if train:
-                ws['r'] = [e(B, F, t) for t in ws['Tl']]      # relu outputs
-                ws['y6'] = e(B, D, Tz)
-                ws['dX'] = [e(B, F, t) for t in ws['Tl']]
-        else:
-            self.magenta.workspace(ws, B, T, dev, train)
+        self.encoder.workspace(self, ws, train)
         ws['z_e'] = e(B, D, Tz)
         ws['idx'] = A.empty(B, Tz, dtype=torch.int64, device=dev)
         ws['e_k'] = e(B, D, Tz)
         ws['mind'] = e(B, Tz)
         ws['cond'] = e(B, self.Cc, Tz)
-        ws['scale'] = e(6 * F + D)
-        ws['shift'] = e(6 * F + D)
         return ws
 
     def _front_workspace_train(self, ws):
-        """Backward buffers of the encoder + VQ (hook)."""
-        e = lambda *s: A.empty(*s, device=self.dev)  # noqa: E731
-        ws['dz'] = e(ws['B'], self.D, ws['Tz'])
-        ws['dscale'] = e(6 * self.F + self.D)
+        """Backward buffers of the VQ (hook; the encoder's are made with its forward buffers)."""
+        ws['dz'] = A.empty(ws['B'], self.D, ws['Tz'], device=self.dev)
 
     # ------------------------------------------------------------------ forward pieces
-    def _bn_affine(self, ws):
-        """Inference-mode BatchNorm as a per-channel affine (encoder.py:20,25; Appendix A-3)."""
-        inv = torch.rsqrt(self.bn_var + BN_EPS)
-        torch.mul(self.P['bn_gamma'], inv, out=ws['scale'])
-        torch.addcmul(self.P['bn_beta'], self.bn_mean, ws['scale'], value=-1.0, out=ws['shift'])
-        return inv
-
     def _encode(self, x, spk, ws, save=True):
-        """encoder.py:13-26 + model.py:57-74 + decoder_ops.py:39-43 -> ws['cond'] [B][Cc][Tz]."""
-        P, F, D, B, T = self.P, self.F, self.D, ws['B'], ws['T']
-        if self.enc != '64':
-            self.magenta.forward(x, ws, P, self.T, save)
-            self._quantise(spk, ws)
-            return
-        self._bn_affine(ws)
-        sc, sh = ws['scale'], ws['shift']
-        pl, _ = same_pads(T, 5, 2)
-        K.conv_cin1_fwd(x, P['enc_w0'], P['enc_b'][0], ws['X'][0], k=5, stride=2, offset=-pl, relu=True,
-                        scale=sc[:F], shift=sh[:F], save_r=ws['r'][0] if save else None)
-        Tin = ws['Tl'][0]
-        # the long strided layers on the fp16x3 engine (space-to-depth planes, DESIGN 3.3): exact power-of-two scales from a
-        # max-abs pass over this step's tensors; a non-finite value raises the step's range flag (-> fp32 repeat)
-        ex3 = ws['enc_x3'] = self._plan(ws, ws is self._ws.get((B, T, True))).enc_x3      # (a training workspace: also under encode())
-        if ex3:
-            ea, es, flag = ws['enc_amax'], ws['enc_scale'], self.x3_flag
-            K.f16x3_amax(P['enc_w'], ea[0:1], flag=flag)
-            K.f16x3_update_scales(ea[0:1], es[0:1], target_exp=14, flag=flag)
-            K.f16x3_pack_weights(P['enc_w'], ws['ewp'], 5 * F, F, F, 1.0, count=5, scale_dev=es[0:1], mode=0)
-        for i in range(1, 6):
-            Tout = ws['Tl'][i]
-            pl, _ = same_pads(Tin, 5, 2)
-            nsplit = self._short_layer_split(F, Tout, B)
-            if i in ex3:
-                K.f16x3_amax(ws['X'][i - 1], ea[i:i + 1], flag=flag)
-                K.f16x3_update_scales(ea[i:i + 1], es[i:i + 1], target_exp=13, flag=flag)
-                epl = ws['esp'][i] if (save and self.wg_planes) else ws['eplanes']
-                K.f16x3_split_activations(ws['X'][i - 1], epl, B, F, Tin, scale_dev=es[i:i + 1], mode=K.X3_S2D)
-                K.f16x3_strided_conv(xp=epl, wp=ws['ewp'][i - 1], out=ws['X'][i], save_r=ws['r'][i] if save else None,
-                                     B=B, T=Tout, Cin=F, M=F, ks=5, pad_left=pl, bias=P['enc_b'][i], bn_scale=sc[i * F:(i + 1) * F],
-                                     bn_shift=sh[i * F:(i + 1) * F], relu=True, x_scale=es[i:i + 1], w_scale=es[0:1], **self._sconv_split(ws))
-            elif nsplit > 1:
-                # short layer (T_out down to 104): too few tiles for 256 CUs, but K = 5*768 is long: split-K into the
-                # output buffer (plain STORE + atomics), then relu / save / BatchNorm affine as a second, tiny pass
-                K.conv_gemm(x0=ws['X'][i - 1], w=P['enc_w'][i - 1], bias=P['enc_b'][i], out0=ws['X'][i], B=B, T_in=Tin,
-                            T_out=Tout, M=F, C0=F, in_stride=2, taps=[j - pl for j in range(5)], tile=12, split_k=nsplit)
-                K.relu_bn_fwd(ws['X'][i], ws['r'][i] if save else None, sc[i * F:(i + 1) * F], sh[i * F:(i + 1) * F])
-            else:
-                K.conv_gemm(x0=ws['X'][i - 1], w=P['enc_w'][i - 1], bias=P['enc_b'][i], out0=ws['X'][i],
-                            save0=ws['r'][i] if save else None, scale=sc[i * F:(i + 1) * F], shift=sh[i * F:(i + 1) * F],
-                            B=B, T_in=Tin, T_out=Tout, M=F, C0=F, in_stride=2, taps=[j - pl for j in range(5)],
-                            out_relu=True)
-            Tin = Tout
-        Tz = ws['Tz']
-        K.conv_gemm(x0=ws['X'][5], w=P['enc_w6'], bias=P['enc_b6'], out0=ws['z_e'], save0=ws['y6'] if save else None,
-                    scale=sc[6 * F:], shift=sh[6 * F:], B=B, T_in=Tz, T_out=Tz, M=D, C0=F, taps=[0])
+        """The encoder + model.py:57-74 + decoder_ops.py:39-43 -> ws['cond'] [B][Cc][Tz]."""
+        self.encoder.forward(self, x, ws, save)
         self._quantise(spk, ws)
 
     def _wslab(self, ws):
@@ -642,30 +511,10 @@ class VQVAE:
             ws['_poison'].append(ws['wslab'])
         return ws['wslab']
 
-    def _sconv_split(self, ws):
-        """Scratch of the strided convs' split-K launches (encoder layers 3-5: 24..78 tiles of 240 K steps on 256 CUs): partial tiles
-        of one launch (at most two rounds of 128-row blocks) and the tiles' ticket counters, which every launch leaves at zero."""
-        if not self.sw.sconv_split:
-            return {}
-        if 'sslab' not in ws:
-            cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
-            ws['sslab'] = A.empty(cus * 65536, device=self.dev)
-            ws['_poison'].append(ws['sslab'])
-            ws['scount'] = torch.zeros(1024, dtype=torch.int32, device=self.dev)
-        return {'split_slab': ws['sslab'], 'split_counters': ws['scount']}
-
     def _side_stream(self):
         if self._side is None:
             self._side = torch.cuda.Stream(device=self.dev)
         return self._side
-
-    @staticmethod
-    def _short_layer_split(M, T_out, B, cus=256):
-        """K slices for a conv whose 64x128 tiles (4 resident per CU) cannot fill the chip: aim at ~4 blocks per CU."""
-        nb = -(-M // 64) * -(-T_out // 128) * B
-        if nb * 2 > 4 * cus:
-            return 1
-        return max(1, min(8, (4 * cus) // nb))
 
     def _quantise(self, spk, ws):
         """model.py:57-74 (VQ) + model.py:22-27 / decoder_ops.py:39-43 (speaker embedding tiled over time)."""
@@ -899,7 +748,7 @@ class VQVAE:
         # encoder layers (1..5) whose conv and input gradient run on the fp16x3 engine (training workspaces only: train_step reads the
         # step's range flag): channel blocks of 128; the 256-column tiles over the flat (batch, time) rows may be partial (layers 4, 5: 1664,
         # 832 columns at B = 8).  Slots of ws['enc_scale'] / ws['enc_amax']: 0 the kernels, i the input of layer i, 5 + i d(its conv output)
-        enc, Tl = self._enc_on_engine(), [T // (2 ** (i + 1)) for i in range(6)]
+        enc, Tl = self.encoder is not None and self.encoder.on_engine(self), [T // (2 ** (i + 1)) for i in range(6)]
         enc_x3 = tuple(i for i in (1, 2, 3, 4, 5) if B * Tl[i] >= 256 and Tl[i - 1] == 2 * Tl[i]) if (enc and active and save and sw.enc_x3) else ()
         return StepPlan(      # (WS, GS: 1.0 where the scales live on the device; enc_wg3: head_x3 or wg_x3 = this step's backward makes the slab)
             save=save, f16x3=f16x3, f16x3_out=f16x3_out, f16x3_skip=f16x3_skip, x3_used=full, gd=gd, calib=self.x3_guard and not active,
@@ -1092,7 +941,7 @@ class VQVAE:
     # ------------------------------------------------------------------ held-out scoring
     def _length_unit(self):
         """What a row's scored length must be a multiple of: the encoder's ratio (hook: the prior has no encoder)."""
-        return 320 if self.enc == '2019' else 64
+        return self.encoder.ratio
 
     def evaluate(self, x, spk, lengths=None, weights='ema', per_position=False):
         """Score held-out rows: the decoder's teacher-forced pass over the padded batch x [B][T] (forward only, on the score
@@ -1297,8 +1146,7 @@ class VQVAE:
 
     def _backward_prepare(self):
         """Transposed kernels of the encoder's backward pass (hook)."""
-        if self.enc != '64':
-            self.magenta.transpose(self.P, self.T)
+        self.encoder.transpose(self)
 
     def backward(self, x, spk, ws):
         """Gradients of loss = CE + vq + commitment (model.py:90-106) w.r.t. every trainable
@@ -1565,9 +1413,7 @@ class VQVAE:
 
     def _backward_front(self, x, spk, ws):
         """From d cond on: speaker embedding, VQ and encoder backward (hook)."""
-        P, G, Tt = self.P, self.G, self.T
-        F, D = self.F, self.D
-        B, T, Tz = ws['B'], ws['T'], ws['Tz']
+        G, D, B, Tz = self.G, self.D, ws['B'], ws['Tz']
         if self.grad_sync is not None:      # decoder gradients are final: exchange them under the encoder backward
             self.grad_sync.bucket_ready(self.seg_off['pre_w'][0], self.n_flat)
         # ---- speaker embedding + VQ (model.py:22-27, 57-74, 99-106)
@@ -1584,105 +1430,7 @@ class VQVAE:
                              cscale=2.0 * self.beta / nd, escale=2.0 / nd, K=self.Kc)
         elif not ws.get('jittered'):
             ws['dz'].copy_(ws['dcond'][:, :D])
-        if self.enc != '64':
-            self.magenta.backward(x, ws, P, G, Tt)
-            if self.grad_sync is not None:
-                self.grad_sync.bucket_ready(0, self.seg_off['pre_w'][0])
-            return
-        # ---- encoder (encoder.py:13-26), BN in inference mode
-        sc, dsc = ws['scale'], ws['dscale']
-        dsc.zero_()
-        dz = ws['dz']
-        # BatchNorm / relu backward with its three sums (d scale, d beta, the conv's bias gradient) in one pass per layer
-        K.bn_relu_bwd_sums(dz, ws['y6'], None, sc[6 * F:], dz, dscale=dsc[6 * F:], dbeta=G['bn_beta'][6 * F:],
-                           dbias=G['enc_b6'])                        # dz := d(conv6 output)
-        K.wgrad_gemm(p=ws['X'][5], q0=dz, dw=G['enc_w6'], B=B, T_q=Tz, T_p=Tz, Cp=F, Q0=D, taps=[0])
-        K.conv_gemm(x0=dz, w=self._tt('enc_w6'), out0=ws['dX'][5], B=B, T_in=Tz, T_out=Tz, M=F, C0=D, taps=[0])
-        main = torch.cuda.current_stream()
-        side = self._side_stream() if self.overlap_wgrad else main
-        # layers 1..5 on the fp16x3 engine: the input gradient where the forward conv ran there (ws['enc_x3']), the weight
-        # gradient (operands split in registers, bias sums riding along) whenever the decoder's ran there this step.  Scales:
-        # exact powers of two from max-abs passes over THIS step's tensors (slots: _enc_x3_layers)
-        ex3, wg3 = ws['plan'].enc_x3, ws['plan'].enc_wg3
-        ea, es, flag = ws.get('enc_amax'), ws.get('enc_scale'), self.x3_flag
-        if ex3:
-            K.f16x3_pack_weights_t(P['enc_w'], ws['ewtp'], 5 * F, F, F, F, F * F, 1.0, count=5, scale_dev=es[0:1], mode=0)
-        for i in range(5, -1, -1):
-            dX, r = ws['dX'][i], ws['r'][i]
-            Ti = ws['Tl'][i]
-            Tin = ws['Tl'][i - 1] if i > 0 else T
-            pl, _ = same_pads(Tin, 5, 2)
-            on_c = i in ex3
-            on_w = wg3 and 1 <= i <= 5 and Ti % 4 == 0 and B * Ti >= 256 and Tin == 2 * Ti and B * F * Tin * 4 < (1 << 31)
-            K.bn_relu_bwd_sums(dX, r, r, sc[i * F:(i + 1) * F], dX, dscale=dsc[i * F:(i + 1) * F],
-                               dbeta=G['bn_beta'][i * F:(i + 1) * F],
-                               dbias=None if on_w else G['enc_b'][i])   # dX := d(conv_i output); (the engine's wgrad sums the bias itself)
-            if on_c or on_w:
-                K.f16x3_amax(dX, ea[5 + i:6 + i], flag=flag)
-                K.f16x3_update_scales(ea[5 + i:6 + i], es[5 + i:6 + i], target_exp=13, flag=flag)
-                if not on_c:                                         # (the forward pass measured X[i-1] otherwise)
-                    K.f16x3_amax(ws['X'][i - 1], ea[i:i + 1], flag=flag)
-                    K.f16x3_update_scales(ea[i:i + 1], es[i:i + 1], target_exp=13, flag=flag)
-            if side is not main:
-                ready = torch.cuda.Event()
-                ready.record(main)
-            # both operands as planes where the forward conv ran on the engine (its space-to-depth input planes were kept):
-            # tap j, e = j - pad_left, is parity block e & 1 at row offset e >> 1
-            w_planes = on_w and on_c and self.wg_planes
-            if w_planes:     # (the split the input gradient needs anyway, into this layer's own buffer, BEFORE the weight gradient)
-                K.f16x3_split_activations(dX, ws['edp'][i], B, F, Ti, scale_dev=es[5 + i:6 + i], mode=0)
-                if side is not main:
-                    ready = torch.cuda.Event()
-                    ready.record(main)
-            with torch.cuda.stream(side):                            # weight / bias gradients: nothing downstream waits
-                if side is not main:
-                    side.wait_event(ready)
-                if w_planes:
-                    K.f16x3_wgrad(p_planes=ws['esp'][i], p_planes_KC=2 * F // 8, p_tap_chunk=[((j - pl) & 1) * (F // 8) for j in range(5)],
-                                  q_planes=ws['edp'][i], dw=G['enc_w'][i - 1], slab=ws['wslab'], B=B, T=Ti, Cp=F, Q0=F,
-                                  taps=[(j - pl) >> 1 for j in range(5)], p_scale=es[i:i + 1], q0_scale=es[5 + i:6 + i],
-                                  q_total=G['enc_b'][i], mode=0)
-                elif on_w:
-                    K.f16x3_wgrad(p=ws['X'][i - 1], q0=dX, dw=G['enc_w'][i - 1], slab=ws['wslab'], B=B, T=Ti, Cp=F, Q0=F,
-                                  taps=[j - pl for j in range(5)], p_scale=es[i:i + 1], q0_scale=es[5 + i:6 + i], p_stride=2, T_p=Tin,
-                                  q_total=G['enc_b'][i], mode=0)
-                else:
-                    if i == 0:
-                        K.conv_cin1_wgrad(x, dX, G['enc_w0'], k=5, stride=2, offset=-pl)
-                    else:
-                        K.wgrad_gemm(p=ws['X'][i - 1], q0=dX, dw=G['enc_w'][i - 1], B=B, T_q=Ti, T_p=Tin, Cp=F, Q0=F, p_stride=2,
-                                     taps=[j - pl for j in range(5)])
-                if self.grad_sync is not None and i >= 2:      # this layer's kernel gradient (11.8 MB) is final: exchange it under
-                    ew, ne = self.seg_off['enc_w'][0], 5 * F * F   # the rest of the encoder backward
-                    self.grad_sync.bucket_ready(ew + (i - 1) * ne, ew + i * ne)
-            if i == 0:
-                break
-            if on_c:
-                if not w_planes:
-                    K.f16x3_split_activations(dX, ws['eplanes'], B, F, Ti, scale_dev=es[5 + i:6 + i], mode=0)
-                K.f16x3_strided_conv(xp=ws['edp'][i] if w_planes else ws['eplanes'], wp=ws['ewtp'][i - 1], out=ws['dX'][i - 1], B=B, T=Ti, Cin=F, M=F, ks=5,
-                                     pad_left=pl, dgrad=True, x_scale=es[5 + i:6 + i], w_scale=es[0:1], **self._sconv_split(ws))
-                continue
-            # transposed conv: output times tau = 2u+p get taps j with j = p + pad_left (mod 2)
-            nsplit = self._short_layer_split(F, (Tin + 1) // 2, B)
-            if nsplit > 1:
-                ws['dX'][i - 1].zero_()        # both parity launches add their K slices into it (split_k < 0)
-            for p in (0, 1):
-                j0 = (p + pl) % 2
-                js = list(range(j0, 5, 2))
-                K.conv_gemm(x0=dX, w=self._tt('enc_w')[i - 1][j0:], w_tap_stride=2 * F * F, out0=ws['dX'][i - 1], B=B,
-                            T_in=Ti, T_out=(Tin - p + 1) // 2, M=F, C0=F, taps=[(p + pl - j) // 2 for j in js],
-                            out_tstride=2, out_toffset=p, T_store=Tin, tile=12 if nsplit > 1 else 0,
-                            split_k=-nsplit if nsplit > 1 else 0)
-        if side is not main:
-            main.wait_stream(side)
-        dsc.addcmul_(self.bn_mean, G['bn_beta'], value=-1.0)         # shift = beta - mean*scale
-        torch.mul(dsc, torch.rsqrt(self.bn_var + BN_EPS), out=dsc)
-        G['bn_gamma'] += dsc
-        if self.grad_sync is not None:      # what the per-layer buckets above left: the first layers' kernels, biases, BatchNorm, codebook
-            ew, ne = self.seg_off['enc_w'][0], 5 * F * F
-            self.grad_sync.bucket_ready(0, ew + ne)
-            self.grad_sync.bucket_ready(ew + 5 * ne, self.seg_off['pre_w'][0])
+        self.encoder.backward(self, x, ws)
 
     # ------------------------------------------------------------------ optimiser
     def lr_at(self, step):

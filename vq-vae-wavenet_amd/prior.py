@@ -74,7 +74,7 @@ class LatentPrior(VQVAE):
             raise ValueError('the latent prior has no encoder and no latents to jitter: time_jitter is a key of the VQ-VAE\'s config')
         if 'codebook_ema' in cfg or 'codebook_restart' in cfg:
             raise ValueError('the latent prior has no codebook: codebook_ema / codebook_restart are keys of the VQ-VAE\'s config')
-        self.enc, self.magenta = None, None
+        self.enc, self.encoder = None, None
         self.F, self.D = 0, 0
         self.Kc = cfg['quantization_channels']
         self.Cs = cfg['speaker_embedding']
