@@ -7,12 +7,15 @@ with arguments under their parameter names.  A tensor reads [ordinal of its stor
 numel, dtype]: the role of a buffer, not its address.  Event records, stream waits and grad_sync.bucket_ready ranges are entries
 too.  Nothing is computed; the tensors hold whatever torch.empty left in them.
 
-`CASES` are the shapes and switches under which Encoder_64 takes each of its branches (plus the two other encoders), `LAYOUTS` the
+`CASES` are the shapes and switches under which Encoder_64 takes each of its branches (plus the two other encoders), the decoder's
+own branches (bf16, the development ladder, the weight-gradient, head and condition switches, a length the plane engine refuses),
+the latent prior, train_step around the passes and the forward-only passes (score, decoder_states, encode); `LAYOUTS` the
 configurations whose flat-buffer layout, state_dict and reference names are pinned.  tests/golden/launch_trace.json holds the
-SHA-256 of every case's JSON-serialised trace, its call names (for a readable failure) and the layout facts.
+SHA-256 of every case's JSON-serialised trace, its call names (for a readable failure; DIGEST_ONLY cases: their number) and the
+layout facts (the prior's: their digest).
 
     python tests/launch_trace.py --write          # make the golden file again (only ever from a commit whose launches are the truth)
-    python tests/launch_trace.py --dump CASE      # one case's whole trace as text, to diff two commits
+    python tests/launch_trace.py --dump CASE      # one case's whole trace as text (or a layout's facts), to diff two commits
 """
 import contextlib
 import hashlib
@@ -36,8 +39,13 @@ MODEL = {'encoder': '64', 'use_vq': True, 'speaker_embedding': 64, 'k': 512, 'la
          'learning_rate_schedule': {'0': 8e-5}}
 SPEAKERS = 109
 
-# model: keys laid over MODEL; env: VQW_* switches (every other VQW_* variable is unset); active: model._x3_active;
-# encode: _encode(save=False) on a train=False workspace instead of forward() + backward(); grad_sync: with the recording stub
+PRIOR = dict(WAVENET, quantization_channels=512, speaker_embedding=64, learning_rate_schedule={'0': 1e-4})
+
+# model: keys laid over MODEL (kind 'prior': over PRIOR); env: VQW_* switches (every other VQW_* variable is unset); active:
+# model._x3_active; grad_sync: with the recording stub; kind: 'prior' = prior.LatentPrior over int32 codes instead of a VQVAE;
+# run: what is recorded instead of forward() + backward() -- '_encode': _encode(save=False) on a train=False workspace,
+# 'train_step': one immediate train_step, 'score': _score_pass on the score workspace, 'states': decoder_states of a 700-step
+# prompt, 'encode': encode() of one utterance for three speakers
 CASES = {
     'enc64': dict(),
     'magenta': dict(model={'encoder': 'Magenta'}),
@@ -49,14 +57,44 @@ CASES = {
     'enc64-enc-wgrad-x3-0': dict(env={'VQW_ENC_WGRAD_X3': '0'}),
     'enc64-sconv-split-0': dict(env={'VQW_SCONV_SPLIT': '0'}),
     'enc64-overlap-0': dict(env={'VQW_OVERLAP': '0'}),
-    'enc64-encode-nosave': dict(encode=True),
+    'enc64-encode-nosave': dict(run='_encode'),
     'enc64-grad-sync': dict(grad_sync=True),
     # 768 filters: layer 1 has 12 x 8 x 8 = 768 blocks of 64 x 128 (more than 2 per CU: one unsplit conv_gemm, forward and input
     # gradient), layer 2 has 384 (split in two) -- VQVAE / Encoder64 _short_layer_split
     'enc64-unsplit': dict(model={'encoder_filters': 768}, env={'VQW_ENGINE': 'fp32'}, B=8, T=4096),
 }
+# ... and the cases of which the golden file holds the digest and the number of entries alone, no list of call names (--dump prints a
+# trace): the file stays small enough to read
+DIGEST_ONLY = {
+    # the decoder's own branches
+    'dec-bf16': dict(env={'VQW_DTYPE': 'bf16'}),
+    **{'dec-ladder-%d' % n: dict(env={'VQW_GATE_F16X3': str(n)}) for n in (1, 2, 3, 4, 5)},
+    'dec-wgrad-batch-0': dict(env={'VQW_WGRAD_BATCH': '0'}),
+    'dec-wgrad-x3-0': dict(env={'VQW_WGRAD_X3': '0'}),
+    'dec-head-x3-0': dict(env={'VQW_HEAD_X3': '0'}),
+    'dec-wgrad-qp-0': dict(env={'VQW_WGRAD_QP': '0'}),
+    'dec-save-tanh-1': dict(env={'VQW_SAVE_TANH': '1'}),
+    'dec-cond-proj-0': dict(env={'VQW_COND_PROJ': '0'}),
+    'dec-skip-groups-2': dict(env={'VQW_SKIP_GROUPS': '2'}),
+    'dec-novq-onehot': dict(model={'use_vq': False, 'speaker_embedding': 0}),
+    'dec-refused-length': dict(T=1088),      # no multiple of 256: the fp32-MFMA engine, with the one-line notice
+    'dec-refused-length-enc-x3-0': dict(T=1088, env={'VQW_ENC_X3': '0'}),     # ... and the encoder's engine layers off: no plane kernel is left
+    # the latent prior
+    'prior': dict(kind='prior'),
+    'prior-engine-fp32': dict(kind='prior', env={'VQW_ENGINE': 'fp32'}),
+    'prior-train-step': dict(kind='prior', run='train_step'),
+    'prior-score': dict(kind='prior', run='score'),
+    # the step around the passes (guard-scale update, the codebook's own update, Adam + EMA), the forward-only passes
+    'train-step': dict(run='train_step'),
+    'train-step-jitter-ema': dict(run='train_step', model={'time_jitter': 0.12, 'codebook_ema': 0.99, 'codebook_restart': 0.5}),
+    'score': dict(run='score'),
+    'states': dict(run='states'),
+    'encode': dict(run='encode'),
+}
+CASES.update(DIGEST_ONLY)
 LAYOUTS = {'%s-vq%d-spk%d' % (enc, vq, spk): {'encoder': enc, 'use_vq': bool(vq), 'speaker_embedding': spk}
            for enc in ('64', 'Magenta', '2019') for vq in (1, 0) for spk in (64, 0)}
+LAYOUTS.update({'prior-spk%d' % spk: {'kind': 'prior', 'speaker_embedding': spk} for spk in (64, 0)})      # (golden: the facts' digest alone)
 
 
 class Recorder:
@@ -175,20 +213,36 @@ def set_switches(monkeypatch, env):
         monkeypatch.setenv(k, v)
 
 
+def make_model(pkg, kind, keys):
+    """A fresh model on the CPU: a VQVAE of MODEL / WAVENET, or (kind 'prior') a LatentPrior of PRIOR, with `keys` laid over."""
+    if kind == 'prior':
+        return pkg.prior.LatentPrior(dict(PRIOR, **keys), SPEAKERS, device='cpu')
+    return pkg.model.VQVAE(dict(MODEL, **keys), dict(WAVENET), SPEAKERS, device='cpu', seed=0)
+
+
 def run_case(monkeypatch, pkg, name):
-    """The trace of CASES[name]: a fresh model under the case's switches, then forward() + backward() (or _encode alone)."""
+    """The trace of CASES[name]: a fresh model under the case's switches, then forward() + backward() (or what the case's `run` names)."""
     case = CASES[name]
     set_switches(monkeypatch, case.get('env', {}))
     rec = install(monkeypatch, pkg)
-    model = pkg.model.VQVAE(dict(MODEL, **case.get('model', {})), dict(WAVENET), SPEAKERS, device='cpu', seed=0)
+    prior, run = case.get('kind') == 'prior', case.get('run')
+    model = make_model(pkg, case.get('kind'), case.get('model', {}))
     model._x3_active = case.get('active', True)
     if case.get('grad_sync'):
         model.grad_sync = GradSyncStub(rec)
     B, T = case.get('B', 1), case.get('T', 1024)
-    x, spk = torch.zeros(B, T), torch.zeros(B, dtype=torch.int64)
+    x, spk = torch.zeros(B, T, dtype=torch.int32 if prior else torch.float32), torch.zeros(B, dtype=torch.int64)
     del rec.trace[:]                     # (what the constructor checked its settings with)
-    if case.get('encode'):
+    if run == '_encode':
         model._encode(x, spk, model._workspace(B, T, train=False), save=False)
+    elif run == 'train_step':
+        model.train_step(x, spk)
+    elif run == 'score':
+        model._score_pass(x, spk, model._workspace(B, T, 'score'))
+    elif run == 'states':
+        model.decoder_states(x, torch.zeros(B, model.Cc, T // 64), 700, lambda l, net_l, s0: None)
+    elif run == 'encode':
+        model.encode(x, torch.zeros(3, dtype=torch.int64))
     else:
         model.backward(x, spk, model.forward(x, spk))
     return rec.trace
@@ -199,10 +253,12 @@ def digest(trace):
 
 
 def layout_facts(monkeypatch, pkg, name):
-    """What checkpoints and the grad_sync bucket ranges depend on: segments with offsets, state_dict, reference names."""
+    """What checkpoints and the grad_sync bucket ranges depend on: segments with offsets, state_dict, reference names
+    (a zero-length tensor holds nothing and is no part of them)."""
     set_switches(monkeypatch, {})
-    model = pkg.model.VQVAE(dict(MODEL, **LAYOUTS[name]), dict(WAVENET), SPEAKERS, device='cpu', seed=0)
-    shapes = lambda d: [[k, list(v.shape)] for k, v in d.items()]                                   # noqa: E731
+    keys = dict(LAYOUTS[name])
+    model = make_model(pkg, keys.pop('kind', None), keys)
+    shapes = lambda d: [[k, list(v.shape)] for k, v in d.items() if v.numel()]                      # noqa: E731
     return {'segments': [[n, off, list(shp)] for n, (off, shp) in model.seg_off.items()], 'n_flat': model.n_flat,
             'state_dict': shapes(model.state_dict()), 'named_parameters': shapes(model.named_parameters()),
             'named_parameters_ema': shapes(model.named_parameters(ema=True)), 'named_gradients': shapes(model.named_gradients())}
@@ -216,9 +272,9 @@ def main(argv):
     import pytest
     sys.path.insert(0, os.path.dirname(HERE))
     pkg = importlib.import_module('vq-vae-wavenet_amd')
-    if argv[:1] == ['--dump'] and len(argv) == 2 and argv[1] in CASES:
+    if argv[:1] == ['--dump'] and len(argv) == 2 and (argv[1] in CASES or argv[1] in LAYOUTS):
         with pytest.MonkeyPatch.context() as mp:
-            print(as_text(run_case(mp, pkg, argv[1])))
+            print(as_text(run_case(mp, pkg, argv[1])) if argv[1] in CASES else json.dumps(layout_facts(mp, pkg, argv[1]), indent=1))
         return 0
     if argv != ['--write']:
         print(__doc__)
@@ -227,11 +283,12 @@ def main(argv):
     for name in CASES:
         with pytest.MonkeyPatch.context() as mp:
             trace = run_case(mp, pkg, name)
-        golden['cases'][name] = {'sha256': digest(trace), 'calls': [e[0] for e in trace]}
+        golden['cases'][name] = dict({'sha256': digest(trace)}, **({'entries': len(trace)} if name in DIGEST_ONLY else {'calls': [e[0] for e in trace]}))
         print('%-24s %4d entries  %s' % (name, len(trace), golden['cases'][name]['sha256'][:16]))
     for name in LAYOUTS:
         with pytest.MonkeyPatch.context() as mp:
-            golden['layouts'][name] = layout_facts(mp, pkg, name)
+            facts = layout_facts(mp, pkg, name)
+        golden['layouts'][name] = {'sha256': digest(facts)} if 'kind' in LAYOUTS[name] else facts
     with open(GOLDEN, 'w') as f:
         json.dump(golden, f, indent=0, sort_keys=True)
         f.write('\n')

@@ -99,6 +99,29 @@ def test_parameter_inventory(pkg, spk_emb):
     assert prior.state_dict()['flat'].numel() == prior.n_flat
 
 
+def test_state_dict_has_no_batchnorm_statistics_and_loads_files_that_do(pkg):
+    """A prior is a WaveNet, not a VQ-VAE: no BatchNorm buffers, none of the VQ-VAE's front.  Its state_dict is the WaveNet's;
+    load_state_dict takes it, and takes a file written when a prior still carried two zero-length bn_mean / bn_var tensors."""
+    import torch
+    prior = pkg.prior.LatentPrior(tiny_prior(), 10, device='cpu', seed=1)
+    for name in ('bn_mean', 'bn_var', 'time_jitter', 'codebook_ema', 'codebook_restart', 'encode', 'encode_codes', 'summaries', 'encoder'):
+        assert not hasattr(prior, name), name
+    prior.global_step = 7
+    prior.adam_m.fill_(0.25)
+    prior.x3_scale.mul_(2.0)
+    sd = prior.state_dict()
+    assert list(sd) == ['flat', 'ema', 'adam_m', 'adam_v', 'x3_scale', 'global_step']
+    old = dict(sd, bn_mean=torch.zeros(0), bn_var=torch.ones(0))          # a file from before
+    for state in (sd, old):
+        other = pkg.prior.LatentPrior(tiny_prior(), 10, device='cpu', seed=2)
+        assert not torch.equal(other.flat, prior.flat)
+        other.load_state_dict({k: v.clone() for k, v in state.items()})
+        assert other.global_step == 7
+        for k in ('flat', 'ema', 'adam_m', 'adam_v', 'x3_scale'):
+            assert torch.equal(getattr(other, k), getattr(prior, k)), k
+        assert list(other.state_dict()) == list(sd)
+
+
 def test_vqvae_inventory_unchanged_by_the_hooks(pkg):
     """The decoder's hooks are pure moves: VQVAE's names, order and shapes are what they were."""
     m = vqvae_cfg(k=32)

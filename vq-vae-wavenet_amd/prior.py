@@ -11,16 +11,15 @@ The prior is the decoder's WaveNet with three differences:
   * its only condition is the speaker: its own speaker table (speaker_embedding 0: one-hot speakers, as in VQVAE), tiled
     over condition frames of 64 code steps, the ratio every condition kernel is built for (T must be a multiple of 64).
 Everything else -- the residual stack, the head, the fp16x3 engine and its guards, the deferred range flag, the two-stream
-backward, the condition projections, Adam + EMA -- is VQVAE's decoder machinery, reached through its hooks.
+backward, the condition projections, Adam + EMA -- is wavenet.WaveNet, which the prior is as the VQ-VAE is, through the same hooks.
 """
 import json
-import os
 
 import torch
 
 from . import _alloc as A
 from . import kernels as K
-from .model import VQVAE
+from .wavenet import WaveNet
 
 CODES_PER_FRAME = 64     # code steps per condition frame
 ENCODER_RATIO = {'64': 64}   # audio samples per code of the encoders a prior can be trained on
@@ -55,7 +54,7 @@ def check_prior_config(cfg, vqvae_cfg=None):
             raise ValueError('encoder %r does not make one code per 64 samples: the prior needs Encoder_64' % enc)
 
 
-class LatentPrior(VQVAE):
+class LatentPrior(WaveNet):
     """WaveNet prior over VQ codes.  train_step(codes int32 [B][T], spk int64 [B]); T a multiple of 64."""
 
     scope = 'prior'
@@ -64,21 +63,17 @@ class LatentPrior(VQVAE):
         check_prior_config(cfg)
         if n_codes is not None and int(n_codes) != int(cfg['quantization_channels']):
             raise ValueError('prior quantization_channels %d != codebook size %d' % (cfg['quantization_channels'], n_codes))
-        if os.environ.get('VQW_DTYPE', cfg.get('dtype', 'f32')) == 'bf16':
-            raise NotImplementedError('the latent prior has no bf16 storage mode')
         super().__init__(cfg, cfg, num_speakers, device=device, seed=seed)
 
-    # ------------------------------------------------------------------ hooks of VQVAE
+    # ------------------------------------------------------------------ hooks of WaveNet
     def _setup_front(self, cfg, num_speakers):
         if 'time_jitter' in cfg:
             raise ValueError('the latent prior has no encoder and no latents to jitter: time_jitter is a key of the VQ-VAE\'s config')
         if 'codebook_ema' in cfg or 'codebook_restart' in cfg:
             raise ValueError('the latent prior has no codebook: codebook_ema / codebook_restart are keys of the VQ-VAE\'s config')
-        self.enc, self.encoder = None, None
-        self.F, self.D = 0, 0
-        self.Kc = cfg['quantization_channels']
+        if self.sw.dtype == 'bf16':
+            raise NotImplementedError('the latent prior has no bf16 storage mode')
         self.Cs = cfg['speaker_embedding']
-        self.beta, self.use_vq = 0.0, False
         self.spk_table = self.Cs > 0
         self.Cs_eff = self.Cs if self.spk_table else (num_speakers + 15) // 16 * 16
         self.Cc_ref = self.Cs if self.spk_table else num_speakers
@@ -96,9 +91,6 @@ class LatentPrior(VQVAE):
             P['speaker_embedding'].copy_(uus((self.S_spk, self.Cs), self.S_spk, 2.0))
         else:
             self.onehot = torch.eye(self.S_spk, self.Cs_eff, device=self.dev)
-
-    def _front_scratch(self):
-        return {}
 
     def _named_front(self, V, out, bn_stats=True):
         if self.spk_table:
@@ -124,12 +116,6 @@ class LatentPrior(VQVAE):
     def _decode_input(self, codes, ws):
         K.prior_input_fwd(codes, self.P['pre_w'], self.P['pre_b'], ws['net'][0], ws['labels'])
 
-    def _front_loss(self, ws):
-        pass
-
-    def _backward_prepare(self):
-        pass
-
     def _backward_input(self, codes, ws, dnet):
         B, T = ws['B'], ws['T']
         order, starts = K.prior_code_buckets(codes, self.Q)
@@ -141,12 +127,6 @@ class LatentPrior(VQVAE):
         if self.spk_table:
             K.speaker_tile_bwd(ws['dcond'], spk, self.G['speaker_embedding'], dcond_bstride=self.Cc * ws['Tz'], row0=0,
                                Cs=self.Cs, Tz=ws['Tz'])
-
-    def losses(self, ws):
-        """(loss, cross-entropy, 0, 0) as python floats: the prior's loss is the cross-entropy alone (synchronises)."""
-        self.finish_steps()
-        ce = float(self.loss_buf[0]) / (ws['B'] * ws['T'])
-        return ce, ce, 0.0, 0.0
 
     # ------------------------------------------------------------------ public
     def _check_codes(self, codes, spk):
@@ -163,9 +143,6 @@ class LatentPrior(VQVAE):
         """One Adam + EMA step on the mean cross-entropy of the next code (codes int32 [B][T], T % 64 == 0)."""
         self._check_codes(codes, spk)
         return super().train_step(codes, spk, on_forward)
-
-    def _length_unit(self):
-        return 1
 
     def evaluate(self, codes, spk, lengths=None, weights='ema', per_position=False):
         """Score held-out code rows (codes int32 [B][T], T % 64 == 0, row b restricted to t < lengths[b]): per row nll_sum,
@@ -190,15 +167,3 @@ class LatentPrior(VQVAE):
         K.speaker_tile_fwd(self.P['speaker_embedding'] if self.spk_table else self.onehot, spk, cond,
                            cond_bstride=self.Cc * Tz, row0=0, Cs=self.Cs_eff, Tz=Tz)
         return cond
-
-    def encode(self, x, spk):
-        raise NotImplementedError('the latent prior has no encoder (VQVAE.encode_codes makes its input)')
-
-    def encode_codes(self, x, spk):
-        raise NotImplementedError('the latent prior has no encoder (VQVAE.encode_codes makes its input)')
-
-    def condition_from_codes(self, codes, spk):
-        raise NotImplementedError('the latent prior has no codebook')
-
-    def summaries(self, ws, bins=30):
-        raise NotImplementedError('summaries are the VQ-VAE\'s; the prior logs its loss (train_prior.py)')
