@@ -156,7 +156,10 @@ int vqw_pointwise_gemm_wgrad(const float* x, const float* dy, float* dw, int B, 
  * Small convs with Cin == 1 (decoder preprocess wavenet.py:42-44, encoder.py:15 layer 1):
  *   v = bias[f] + sum_j w[j][f] * x[b][stride*t + j + offset];   r = relu ? max(v,0) : v
  *   save_r (optional) = r;  out = scale ? scale[f]*r + shift[f] : r
- * x [B][T_in], w [k][F], out [B][F][T_out].                                            */
+ * x [B][T_in] (reads outside [0, T_in) are 0; bias NULL = 0), w [k][F], out [B][F][T_out].
+ * k <= 32, stride <= 4.  Rows of T_out % 4 == 0 are stored (dout of the weight gradient:
+ * loaded) 16 bytes at a time: out, save_r and dout must then be 16-byte aligned; a
+ * misaligned one is an error and nothing is launched.                                   */
 int vqw_conv_cin1_fwd(const float* x, const float* w, const float* bias, const float* scale,
                       const float* shift, float* out, float* save_r, int B, int T_in,
                       int T_out, int F, int k, int stride, int offset, int relu,

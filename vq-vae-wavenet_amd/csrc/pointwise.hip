@@ -581,6 +581,9 @@ extern "C" int vqw_conv_cin1_fwd(const float* x, const float* w, const float* bi
     VQW_CHECK(B > 0 && T_in > 0 && T_out > 0 && F > 0 && k >= 1 && k <= 32 && stride >= 1, "vqw_conv_cin1_fwd: bad shape (k<=32)");
     VQW_CHECK(!scale || shift, "vqw_conv_cin1_fwd: scale needs shift");
     VQW_CHECK(stride <= 4, "vqw_conv_cin1_fwd: stride must be <= 4");
+    // rows of T_out % 4 == 0 are stored 16 bytes at a time
+    VQW_CHECK((T_out & 3) != 0 || ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(save_r)) & 15u) == 0,
+              "vqw_conv_cin1_fwd: out and save_r must be 16-byte aligned when T_out %% 4 == 0");
     constexpr int FT = 16;
     dim3 grid(vqw_cdiv(vqw_cdiv(T_out, 4), 256), vqw_cdiv(F, FT), B);
     typedef void (*kfn_t)(const float*, const float*, const float*, const float*, const float*, float*, float*, int, int, int, int, int, int, int);
@@ -599,6 +602,9 @@ extern "C" int vqw_conv_cin1_wgrad(const float* x, const float* dout, float* dw,
     VQW_CHECK(B > 0 && T_in > 0 && T_out > 0 && F > 0 && k >= 1 && k <= 32 && stride >= 1, "vqw_conv_cin1_wgrad: bad shape (k<=32)");
     VQW_CHECK(stride <= 4, "vqw_conv_cin1_wgrad: stride must be <= 4");
     VQW_CHECK(B <= 65535, "vqw_conv_cin1_wgrad: B must be <= 65535");
+    // rows of T_out % 4 == 0 are loaded 16 bytes at a time
+    VQW_CHECK((T_out & 3) != 0 || (reinterpret_cast<uintptr_t>(dout) & 15u) == 0,
+              "vqw_conv_cin1_wgrad: dout must be 16-byte aligned when T_out %% 4 == 0");
     dim3 grid(F, B);
     typedef void (*kfn_t)(const float*, const float*, float*, int, int, int, int, int, int);
     const int kmax = k <= 8 ? 8 : 32;
