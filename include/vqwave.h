@@ -287,6 +287,17 @@ int vqw_time_jitter_bwd(const float* dout, int64_t dout_bstride, const int32_t* 
 int vqw_softmax_xent(const float* logits, const int32_t* labels, float* dlogits,
                      float* probs, float* loss_sum, float grad_scale, int B, int Q, int T,
                      vqw_stream_t s);
+/* vqw_softmax_xent over a range of every row: the loss of a training step on rows of different lengths.  t_begin / t_end
+ * int32 [B] on the device (either may be NULL: 0 / T).  Position (b, t) is SCORED iff
+ * clamp(t_begin[b], 0, T) <= t < clamp(t_end[b], 0, T) (vqw_softmax_score's convention; t_begin >= t_end: an empty row).
+ *   scored:   loss_sum[0] += CE, dlogits = (softmax - onehot) * grad_scale, probs = softmax -- the operations of
+ *             vqw_softmax_xent in its order: the same bits for the same logits and grad_scale
+ *   unscored: nothing is added to loss_sum; dlogits and probs (where given) are WRITTEN as +0.0f; neither the logits nor the
+ *             label of the position is read (they may hold anything, NaN included)
+ * Every element of dlogits / probs is written.  dlogits may alias logits.  Q % 4 == 0, Q >= 4; any T.              */
+int vqw_softmax_xent_ranged(const float* logits, const int32_t* labels, const int32_t* t_begin, const int32_t* t_end,
+                            float* dlogits, float* probs, float* loss_sum, float grad_scale, int B, int Q, int T,
+                            vqw_stream_t s);
 /* The same op as the two entries SURVEY 8(b) names (tf.nn.sparse_softmax_cross_entropy_with_logits and its gradient,
  * model.py:91-94): _fwd adds the CE sum into loss_sum[0] (probs optional); _bwd writes (softmax - onehot) * grad_scale,
  * recomputed from the logits (dlogits may alias logits).                                */

@@ -9,6 +9,16 @@ samples) and runs one prior training step on those codes and their speakers.  Ch
 `<name>.json` with the prior's config and speaker count).  One GPU: data-parallel prior training is not supported.
 `-clip_norm C` clips the gradients to the global norm C, `-grad_norm` only measures it; either adds `[gnorm ...]` to the
 console line (as train.py).
+
+`-whole_utterances [-min_frames N]`: rows are whole utterances, not crops from the middle of speech.  A file shorter than
+`-length` frames is taken from its first sample, zero-padded, and the step is told its length (LatentPrior.train_step
+lengths=): the loss is the mean over the real codes, so the prior sees utterances begin -- what sampling asks of it at step 0 --
+and end.  Longer files give random windows of `-length` frames as before; files under N frames (default 16) are left out.  The
+console line gains `[scored 0.73]`, the share of the logged step's positions that were scored.
+
+`-eval_list FILE -eval_interval N [-eval_batches M]` (as train.py): every N steps the first M padded batches of the list are
+scored with the EMA weights (LatentPrior.evaluate on the codes of the zero-padded audio, lengths = the rows' frames) and the
+line gains `[eval bits/code ...]`.
 """
 import importlib
 import json
@@ -38,9 +48,38 @@ def main():
                         help='the VQ-VAE\'s parameters file')
     parser.add_argument('-clip_norm', default=None, type=float, dest='clip_norm', metavar='float', help='clip gradients to this global norm (> 0)')
     parser.add_argument('-grad_norm', action='store_true', dest='grad_norm', help='log gradient norms without clipping')
+    parser.add_argument('-whole_utterances', action='store_true', dest='whole', help='train on whole utterances: short files from their '
+                        'first code, zero-padded, with a length-masked loss')
+    parser.add_argument('-min_frames', default=None, type=int, dest='min_frames', metavar='int',
+                        help='shortest admitted utterance in code frames (default 16; needs -whole_utterances)')
+    parser.add_argument('-eval_list', dest='eval_list', metavar='string', help='held-out file list scored during training')
+    parser.add_argument('-eval_interval', default=0, type=int, dest='eval_interval', metavar='int', help='score the list every N steps (0 = never)')
+    parser.add_argument('-eval_batches', default=4, type=int, dest='eval_batches', metavar='int', help='held-out batches per evaluation')
+    parser.add_argument('-eval_dataset', default=None, dest='eval_dataset', metavar='DATASET', help='dataset the list belongs to (default: -dataset)')
+    parser.add_argument('-data_root', default='data/', dest='data_root', metavar='string', help='where the held-out wavs and *_speakers.txt are')
     args = parser.parse_args()
     if args.clip_norm is not None and not args.clip_norm > 0:
         parser.error('-clip_norm must be > 0 (got %r)' % args.clip_norm)
+    if args.min_frames is not None and not args.whole:
+        parser.error('-min_frames needs -whole_utterances')
+    if args.whole:
+        args.min_frames = 16 if args.min_frames is None else args.min_frames
+        if not 1 <= args.min_frames <= args.frames:
+            parser.error('-min_frames must be in 1..-length = %d (got %d)' % (args.frames, args.min_frames))
+    if args.eval_interval < 0 or args.eval_batches < 1:
+        parser.error('-eval_interval must be >= 0 and -eval_batches >= 1')
+    if args.eval_interval > 0 and args.eval_list is None:
+        parser.error('-eval_interval needs -eval_list')
+    if args.eval_list is not None:
+        if args.eval_interval == 0:
+            parser.error('-eval_list needs -eval_interval N (N > 0): the list would never be scored')
+        if not os.path.isfile(args.eval_list):
+            parser.error('-eval_list: no such file: %s' % args.eval_list)
+        args.eval_dataset = args.eval_dataset or ('VCTK' if args.dataset == 'synthetic' else args.dataset)
+        if args.eval_dataset not in ('VCTK', 'LibriSpeech', 'Aishell'):
+            parser.error('-eval_dataset must be VCTK, LibriSpeech or Aishell')
+    elif args.eval_dataset is not None:
+        parser.error('-eval_dataset needs -eval_list')
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         raise NotImplementedError('train_prior.py runs on one GPU (multi-GPU prior training is not supported)')
 
@@ -55,6 +94,8 @@ def main():
     D = pkg.data
     T_audio = args.frames * 64
     dargs = dict(batch_size=args.batch_size, max_len=T_audio, device=dev)
+    if args.whole:
+        dargs.update(whole=True, unit=64, min_len=args.min_frames * 64)
     if args.dataset == 'VCTK':
         dataset = D.VCTK(relative_path='data/', **dargs)
     elif args.dataset == 'LibriSpeech':
@@ -81,17 +122,44 @@ def main():
     if save_dir and not os.path.isdir(save_dir):
         os.makedirs(save_dir)
 
+    eval_set = None
+    if args.eval_list is not None:      # the same rows at every evaluation: read and encoded once (the VQ-VAE does not change)
+        held = D.HeldOutList(args.eval_dataset, args.eval_list, relative_path=args.data_root, ratio=64)
+        if held.num_speakers != dataset.num_speakers:
+            raise ValueError('-eval_list: %d speakers under %s, the model has %d' % (held.num_speakers, args.data_root, dataset.num_speakers))
+        utts, _ = held.utterances()
+        if not utts:
+            raise ValueError('-eval_list: no file of %s holds a code frame' % args.eval_list)
+        eval_set = []
+        for _, ex, espk, lengths in D.padded_batches(utts, args.batch_size, multiple=64 * pkg.prior.CODES_PER_FRAME):
+            if len(eval_set) == args.eval_batches:
+                break
+            espk = espk.to(dev)
+            eval_set.append((vqvae.encode_codes(ex.to(dev), espk), espk, [n // 64 for n in lengths]))
+
     for step in range(1, 1 + args.num_steps):
         t = time.time()
-        x, spk = dataset.next()
+        if args.whole:
+            x, spk, lengths = dataset.next()
+            frames = lengths // 64                   # CPU int32 [B]: the rows' code counts
+        else:
+            (x, spk), frames = dataset.next(), None
         codes = vqvae.encode_codes(x, spk)       # [B][frames] int32
-        prior.train_step(codes, spk)
+        prior.train_step(codes, spk) if frames is None else prior.train_step(codes, spk, lengths=frames)
         gs = prior.global_step
-        if gs % args.interval == 0 or step == args.num_steps:
+        eval_now = eval_set is not None and gs % args.eval_interval == 0
+        if gs % args.interval == 0 or step == args.num_steps or eval_now:
             ws = prior._workspace(args.batch_size, args.frames)
             loss = prior.losses(ws)[0]             # synchronises: only every `interval` steps
             t = time.time() - t
             gnorm = ' [gnorm %.4f]' % prior.grad_norms()['global'] if prior.clip_norm is not None else ''
+            if frames is not None:
+                gnorm += ' [scored %.2f]' % (int(frames.sum()) / (args.batch_size * args.frames))
+            if eval_now:
+                totals = pkg.scoring.Totals()
+                for ecodes, espk, eframes in eval_set:
+                    totals.add(prior.evaluate(ecodes, espk, lengths=eframes, weights='ema'))
+                gnorm += ' [eval bits/code %.5f]' % totals.report('code')['bits_per_code']
             print('\r[step %d] %.2f%% [prior %.5f] [lr %.5f]%s [BATCH %.3fs]     '
                   % (gs, step / args.num_steps * 100, loss, prior.lr_at(gs - 1), gnorm, t), end='', flush=True)
     torch.cuda.synchronize()

@@ -144,7 +144,8 @@ SIGNATURES = {
     'vqw_time_jitter_fwd': (_i, [_fp, _i64, _fp, _f, _f, _fp, _i64, _fp, _i, _i, _i, _fp]),
     'vqw_time_jitter_bwd': (_i, [_fp, _i64, _fp, _fp, _i64, _i, _i, _i, _fp]),
     'vqw_softmax_xent': (_i, [_fp, _fp, _fp, _fp, _fp, _f, _i, _i, _i, _fp]),
-    'vqw_softmax_xent_fwd': (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp]),
+    'vqw_softmax_xent_ranged': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _f, _i, _i, _i, _fp]),
+    'vqw_softmax_xent_fwd':(_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp]),
     'vqw_softmax_xent_bwd': (_i, [_fp, _fp, _fp, _f, _i, _i, _i, _fp]),
     'vqw_softmax_score': (_i, [_fp] * 9 + [_i64, _i, _i, _i, _fp]),
     'vqw_code_histogram': (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp]),

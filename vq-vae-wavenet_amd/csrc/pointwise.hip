@@ -407,8 +407,16 @@ __global__ void transpose_kernel(const float* __restrict__ src, float* __restric
 // ----------------------------------------------------------------------------- softmax CE
 // model.py:91-94.  Block = 4 waves x 64 consecutive time steps; wave w owns channels
 // [w*Q/4, (w+1)*Q/4): every load is a 256-byte row segment.
+// RANGED (vqw_softmax_xent_ranged): position (b, t) is scored iff clamp(t_begin[b], 0, T) <= t < clamp(t_end[b], 0, T) (NULL: 0 / T).
+// A scored position goes through the very statements of the unranged instance (ok is the only thing that differs), so its bits
+// are the same; an unscored one loads neither its logits nor its label, adds nothing to the loss and has +0.0f written to
+// dlogits / probs (the backward pass reads every column of dlogits); a tile with no scored position stores its zeros and returns
+// before the first load.  The unranged instance ignores t_begin / t_end and keeps its arithmetic.
+template <bool RANGED>
 __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restrict__ logits,
                                                            const int32_t* __restrict__ labels,
+                                                           const int32_t* __restrict__ t_begin,
+                                                           const int32_t* __restrict__ t_end,
                                                            float* __restrict__ dlogits,
                                                            float* __restrict__ probs,
                                                            float* __restrict__ loss_sum,
@@ -418,8 +426,32 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
     const int ntile = (T + 63) / 64;
     const int b = blockIdx.x / ntile;
     const int t = (blockIdx.x % ntile) * 64 + lane;
-    const bool ok = t < T;
     const int qn = Q / 4, q0 = w * qn;
+    bool ok = t < T;
+    if (RANGED) {
+        const int tb = t_begin ? min(max(t_begin[b], 0), T) : 0;
+        const int te = t_end ? min(max(t_end[b], 0), T) : T;
+        const int tile0 = t - lane;
+        const bool inb = ok;
+        ok = t >= tb && t < te;                              // (te <= T: a scored position is inside the row)
+        if (max(tb, tile0) >= min(te, tile0 + 64)) {         // block-uniform: nothing of this tile is scored
+            if (inb && (dlogits || probs)) {
+                const size_t base = ((size_t)b * Q + q0) * T + t;
+                for (int q = 0; q < qn; ++q) {
+                    if (probs) probs[base + (size_t)q * T] = 0.0f;
+                    if (dlogits) dlogits[base + (size_t)q * T] = 0.0f;
+                }
+            }
+            return;
+        }
+        if (inb && !ok && (dlogits || probs)) {              // an unscored lane of a partial tile: one write, no read
+            const size_t base = ((size_t)b * Q + q0) * T + t;
+            for (int q = 0; q < qn; ++q) {
+                if (probs) probs[base + (size_t)q * T] = 0.0f;
+                if (dlogits) dlogits[base + (size_t)q * T] = 0.0f;
+            }
+        }
+    }
     const float* lp = logits + ((size_t)b * Q + q0) * T + t;
     const int lab = ok ? labels[(size_t)b * T + t] : 0;
     float m = -INFINITY, s = 0.0f, xl = 0.0f;
@@ -684,8 +716,21 @@ extern "C" int vqw_softmax_xent(const float* logits, const int32_t* labels, floa
                                 float* loss_sum, float grad_scale, int B, int Q, int T, vqw_stream_t s) {
     VQW_CHECK(logits && labels && loss_sum, "vqw_softmax_xent: null pointer");
     VQW_CHECK(B > 0 && T > 0 && Q >= 4 && Q % 4 == 0, "vqw_softmax_xent: Q=%d must be a multiple of 4", Q);
-    hipLaunchKernelGGL(softmax_xent_kernel, dim3(B * vqw_cdiv(T, 64)), dim3(256), 0, (hipStream_t)s, logits, labels, dlogits, probs, loss_sum, grad_scale, Q, T);
+    hipLaunchKernelGGL(softmax_xent_kernel<false>, dim3(B * vqw_cdiv(T, 64)), dim3(256), 0, (hipStream_t)s, logits, labels, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr, dlogits, probs, loss_sum, grad_scale, Q, T);
     VQW_LAUNCH_CHECK("vqw_softmax_xent");
+    return 0;
+}
+
+// The loss of a length-masked training step: vqw_softmax_xent over t_begin[b] <= t < t_end[b] alone, zeros elsewhere.
+extern "C" int vqw_softmax_xent_ranged(const float* logits, const int32_t* labels, const int32_t* t_begin, const int32_t* t_end,
+                                       float* dlogits, float* probs, float* loss_sum, float grad_scale, int B, int Q, int T,
+                                       vqw_stream_t s) {
+    VQW_CHECK(logits && labels && loss_sum, "vqw_softmax_xent_ranged: null pointer");
+    VQW_CHECK(B > 0 && T > 0 && Q >= 4 && Q % 4 == 0, "vqw_softmax_xent_ranged: Q=%d must be a multiple of 4", Q);
+    hipLaunchKernelGGL(softmax_xent_kernel<true>, dim3(B * vqw_cdiv(T, 64)), dim3(256), 0, (hipStream_t)s, logits, labels, t_begin, t_end,
+                       dlogits, probs, loss_sum, grad_scale, Q, T);
+    VQW_LAUNCH_CHECK("vqw_softmax_xent_ranged");
     return 0;
 }
 
@@ -695,7 +740,8 @@ extern "C" int vqw_softmax_xent_fwd(const float* logits, const int32_t* labels, 
                                     vqw_stream_t s) {
     VQW_CHECK(logits && labels && loss_sum, "vqw_softmax_xent_fwd: null pointer");
     VQW_CHECK(B > 0 && T > 0 && Q >= 4 && Q % 4 == 0, "vqw_softmax_xent_fwd: Q=%d must be a multiple of 4", Q);
-    hipLaunchKernelGGL(softmax_xent_kernel, dim3(B * vqw_cdiv(T, 64)), dim3(256), 0, (hipStream_t)s, logits, labels, (float*)nullptr, probs,
+    hipLaunchKernelGGL(softmax_xent_kernel<false>, dim3(B * vqw_cdiv(T, 64)), dim3(256), 0, (hipStream_t)s, logits, labels, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr, (float*)nullptr, probs,
                        loss_sum, 0.0f, Q, T);
     VQW_LAUNCH_CHECK("vqw_softmax_xent_fwd");
     return 0;
@@ -705,7 +751,8 @@ extern "C" int vqw_softmax_xent_bwd(const float* logits, const int32_t* labels, 
                                     vqw_stream_t s) {
     VQW_CHECK(logits && labels && dlogits, "vqw_softmax_xent_bwd: null pointer");
     VQW_CHECK(B > 0 && T > 0 && Q >= 4 && Q % 4 == 0, "vqw_softmax_xent_bwd: Q=%d must be a multiple of 4", Q);
-    hipLaunchKernelGGL(softmax_xent_kernel, dim3(B * vqw_cdiv(T, 64)), dim3(256), 0, (hipStream_t)s, logits, labels, dlogits, (float*)nullptr,
+    hipLaunchKernelGGL(softmax_xent_kernel<false>, dim3(B * vqw_cdiv(T, 64)), dim3(256), 0, (hipStream_t)s, logits, labels, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr, dlogits, (float*)nullptr,
                        (float*)nullptr, grad_scale, Q, T);
     VQW_LAUNCH_CHECK("vqw_softmax_xent_bwd");
     return 0;

@@ -30,13 +30,16 @@ def get_speaker_to_int(speaker_path):
 class Synthetic:
     """SURVEY.md 8(d) synthetic int16-PCM segments (4 sinusoids x slow envelope + noise)."""
 
-    def __init__(self, batch_size, max_len, num_speakers=109, seed=1234, device='cuda'):
+    def __init__(self, batch_size, max_len, num_speakers=109, seed=1234, device='cuda', whole=False, unit=64, min_len=None):
         self.B, self.T, self.num_speakers, self.dev = batch_size, max_len, num_speakers, device
         self.g = torch.Generator().manual_seed(seed)
+        # whole: rows of random lengths as WavDataset(whole=True) hands them out (multiples of unit in [min_len, T], zeros behind),
+        # drawn from a generator of their own: the audio is what it is without the option
+        self.whole, self.unit, self.min_len = whole, unit, _whole_min_len(whole, unit, min_len, max_len)
+        self.g_len = torch.Generator().manual_seed(seed + 104729)
 
     def next(self):
-        x, spk = self.next_host()
-        return x.to(self.dev, non_blocking=True), spk.to(self.dev, non_blocking=True)
+        return _to_device(self.next_host(), self.dev)
 
     def next_host(self):
         B, T, g = self.B, self.T, self.g
@@ -49,14 +52,38 @@ class Synthetic:
         pcm = torch.round(wav * 32767).to(torch.int16)
         x = (pcm.to(torch.float32) + 0.5) / 32767.5
         spk = torch.randint(0, self.num_speakers, (B,), generator=g)
-        return x, spk
+        if not self.whole:
+            return x, spk
+        lo, hi = -(-self.min_len // self.unit), T // self.unit
+        lengths = (torch.randint(lo, hi + 1, (B,), generator=self.g_len) * self.unit).to(torch.int32)
+        x = x * (torch.arange(T)[None, :] < lengths[:, None])
+        return x, spk, lengths
+
+
+def _whole_min_len(whole, unit, min_len, max_len):
+    """The shortest admitted row of a whole-utterance source, checked: 1 <= unit, unit | T, and min_len in [1, T] (default: unit)."""
+    if not whole:
+        if min_len is not None:
+            raise ValueError('min_len is an option of whole-utterance sources (whole=True)')
+        return None
+    min_len = unit if min_len is None else int(min_len)
+    if unit < 1 or max_len % unit or not 1 <= min_len <= max_len:
+        raise ValueError('whole utterances: unit %d must divide max_len %d and min_len %d lie in 1..max_len' % (unit, max_len, min_len))
+    return min_len
+
+
+def _to_device(batch, dev):
+    """(x, spk[, lengths]) of next_host() with x and spk on the device; the lengths stay CPU tensors (the model uploads them)."""
+    return tuple(t.to(dev, non_blocking=True) for t in batch[:2]) + tuple(batch[2:])
 
 
 class Prefetcher:
     """The reference feeds its graph from a tf.data pipeline with prefetch (dataset.py:75-84); here a background thread
     reads / crops / resamples the NEXT batches into pinned host buffers while the GPU runs the current step, and `next()`
     only starts the asynchronous host-to-device copy (8 x 6656 fp32 = 213 KB per batch).  `source.next_host()` must return
-    (x float32 [B, T], speaker ids int64 [B]) as CPU tensors.  `waits` counts the calls that found no batch ready."""
+    (x float32 [B, T], speaker ids int64 [B]) as CPU tensors, or that with more CPU tensors behind (a whole-utterance source:
+    lengths int32 [B]).  next() returns as many: x and the speaker ids on the device, the others as CPU tensors of their own
+    (the model uploads lengths itself).  `waits` counts the calls that found no batch ready."""
 
     def __init__(self, source, depth=3, device='cuda'):
         self.source, self.dev = source, torch.device(device)
@@ -69,16 +96,17 @@ class Prefetcher:
         self.thread = threading.Thread(target=self._produce, name='vqw-prefetch', daemon=True)
         self.thread.start()
 
-    def _slot(self, x, spk):
+    def _slot(self, x, spk, *rest):
         mk = (lambda t: torch.empty_like(t).pin_memory()) if self.pin else torch.empty_like
-        return {'x': mk(x), 'spk': mk(spk), 'event': torch.cuda.Event() if self.pin else None, 'used': False}
+        return {'x': mk(x), 'spk': mk(spk), 'rest': [torch.empty_like(t) for t in rest], 'event': torch.cuda.Event() if self.pin else None,
+                'used': False}
 
     def _produce(self):
         try:
             while not self._stop.is_set():
-                x, spk = self.source.next_host()
+                x, spk, *rest = self.source.next_host()
                 if len(self.slots) < self.depth:
-                    self.slots.append(self._slot(x, spk))
+                    self.slots.append(self._slot(x, spk, *rest))
                     i = len(self.slots) - 1
                 else:
                     while True:
@@ -93,6 +121,8 @@ class Prefetcher:
                     slot['event'].synchronize()          # the copy that last read this pinned buffer has finished
                 slot['x'].copy_(x)
                 slot['spk'].copy_(spk)
+                for dst, src in zip(slot['rest'], rest):
+                    dst.copy_(src)
                 self.ready.put(i)
         except BaseException as e:      # surfaced by next()
             self.error = e
@@ -111,10 +141,11 @@ class Prefetcher:
             x, spk = x.clone(), spk.clone()
         else:
             slot['event'].record()
+        rest = tuple(t.clone() for t in slot['rest'])    # (host tensors of the caller's own: the slot is refilled behind its back)
         slot['used'] = True
         self.free.put(i)
         self.served += 1
-        return x, spk
+        return (x, spk) + rest
 
     def close(self):
         self._stop.set()
@@ -126,8 +157,13 @@ class WavDataset:
     speaker_of = staticmethod(lambda rel: rel.split('/')[0])
 
     def __init__(self, batch_size, max_len, relative_path, list_name, speakers_name, data_dir='', sr=16000,
-                 seed=0, device='cuda', rank=0, world=1):
+                 seed=0, device='cuda', rank=0, world=1, whole=False, unit=64, min_len=None):
+        """whole=True (train_prior.py -whole_utterances): next_host() also returns lengths int32 [B].  A file is trimmed to a
+        multiple of `unit` samples and refused below `min_len` (default: unit); one shorter than max_len is taken WHOLE from its
+        first sample and zero-padded, its length its own; a longer one gives a uniformly random window of max_len samples, as
+        without the option, with length max_len.  Off, nothing changes."""
         self.B, self.T, self.sr, self.dev = batch_size, max_len, sr, device
+        self.whole, self.unit, self.min_len = whole, unit, _whole_min_len(whole, unit, min_len, max_len)
         self.root = relative_path
         self.data_dir = data_dir
         with open(os.path.join(relative_path, list_name)) as f:
@@ -156,10 +192,31 @@ class WavDataset:
         return f.astype(np.float32)
 
     def next(self):
-        x, spk = self.next_host()
-        return x.to(self.dev, non_blocking=True), spk.to(self.dev, non_blocking=True)
+        return _to_device(self.next_host(), self.dev)
+
+    def _next_whole(self):
+        x, ss, ls, tries = np.zeros((self.B, self.T), dtype=np.float32), [], [], 0
+        while len(ss) < self.B:
+            rel = self.files[self.rng.randint(len(self.files))]
+            wav = self._read(rel)
+            n = len(wav) // self.unit * self.unit
+            if n < self.min_len:                        # too short to learn from -> another file
+                tries += 1
+                if tries > 1000 * self.B:
+                    raise ValueError('no file of at least %d samples among 1000 draws per row' % self.min_len)
+                continue
+            if n > self.T:
+                start, n = self.rng.randint(0, n - self.T + 1), self.T
+                x[len(ss)] = wav[start:start + n]
+            else:
+                x[len(ss), :n] = wav[:n]
+            ss.append(self.speaker_to_int[self.speaker_of(rel)])
+            ls.append(n)
+        return torch.from_numpy(x), torch.tensor(ss, dtype=torch.int64), torch.tensor(ls, dtype=torch.int32)
 
     def next_host(self):
+        if self.whole:
+            return self._next_whole()
         xs, ss = [], []
         while len(xs) < self.B:
             rel = self.files[self.rng.randint(len(self.files))]

@@ -738,6 +738,25 @@ def _need_i32(t, n, name):
         raise ValueError('%s must be int32 with at least %d elements' % (name, n))
 
 
+def softmax_xent_ranged(logits, labels, *, loss_sum, dlogits=None, probs=None, grad_scale=1.0, t_begin=None, t_end=None):
+    """vqw_softmax_xent_ranged: softmax_xent over t_begin[b] <= t < t_end[b] (device int32 [B]; None: 0 / T).  Scored positions
+    get softmax_xent's bits; the others add nothing to loss_sum and are written as +0.0 in dlogits / probs (their logits and
+    labels are not read).  dlogits may alias logits."""
+    B, Q, T = logits.shape
+    L.require_cuda(logits, labels, loss_sum, dlogits, probs, t_begin, t_end)
+    if logits.dtype != torch.float32:
+        raise ValueError('logits must be float32 [B][Q][T]')
+    if labels.dtype != torch.int32 or labels.numel() != B * T:
+        raise ValueError('labels must be int32 [B][T]')
+    _need_i32(t_begin, B, 't_begin')
+    _need_i32(t_end, B, 't_end')
+    for t, nm in ((dlogits, 'dlogits'), (probs, 'probs')):
+        if t is not None:
+            _need(t, B * Q * T, nm)
+    L.check(L.lib().vqw_softmax_xent_ranged(L.ptr(logits), L.ptr(labels), L.ptr(t_begin), L.ptr(t_end), L.ptr(dlogits), L.ptr(probs),
+                                            L.ptr(loss_sum), float(grad_scale), B, Q, T, L.stream()))
+
+
 def softmax_score(logits, labels, *, t_begin=None, t_end=None, nll=None, entropy=None, row_sums=None, row_counts=None):
     """vqw_softmax_score: scores of logits [B][Q][T] against labels int32 [B][T] over t_begin[b] <= t < t_end[b] (device
     int32 [B]; None: the whole row).  nll / entropy: optional fp32 [B][T] outputs (0 where not scored).  Returns

@@ -298,6 +298,11 @@ class VQVAE(WaveNet):
         enc_x3 = tuple(i for i in (1, 2, 3, 4, 5) if B * Tl[i] >= 256 and Tl[i - 1] == 2 * Tl[i]) if (enc and active and save and self.sw.enc_x3) else ()
         return enc_x3, enc
 
+    # training on row lengths is the causal WaveNet's (LatentPrior): here the encoder sees the padding, and the VQ / commitment
+    # losses, the codebook statistics and the jitter would each need a mask of their own
+    _masked_training = ('the VQ-VAE does not train on lengths: its encoder is not causal, and the VQ and commitment losses, the '
+                        'codebook statistics and the jitter are not masked')
+
     def _front_loss(self, ws):
         """loss_buf[1] = the sum of the VQ distances (hook)."""
         K.rowsum(ws['mind'].view(1, 1, -1), total=self.loss_buf[1:2])

@@ -135,14 +135,16 @@ class LatentPrior(WaveNet):
         if spk.numel() != codes.shape[0]:
             raise ValueError('%d code rows for %d speaker ids' % (codes.shape[0], spk.numel()))
 
-    def forward(self, codes, spk, compute_grad_seed=True):
+    def forward(self, codes, spk, compute_grad_seed=True, lengths=None):
         self._check_codes(codes, spk)
-        return super().forward(codes, spk, compute_grad_seed)
+        return super().forward(codes, spk, compute_grad_seed, lengths)
 
-    def train_step(self, codes, spk, on_forward=None):
-        """One Adam + EMA step on the mean cross-entropy of the next code (codes int32 [B][T], T % 64 == 0)."""
+    def train_step(self, codes, spk, on_forward=None, lengths=None):
+        """One Adam + EMA step on the mean cross-entropy of the next code (codes int32 [B][T], T % 64 == 0).  lengths: None, or
+        B code counts in 1..T: row b is an utterance of lengths[b] codes from its first one, and the loss is the mean over the
+        sum(lengths) real codes -- whatever the row holds behind them changes nothing (WaveNet.train_step)."""
         self._check_codes(codes, spk)
-        return super().train_step(codes, spk, on_forward)
+        return super().train_step(codes, spk, on_forward, lengths)
 
     def evaluate(self, codes, spk, lengths=None, weights='ema', per_position=False):
         """Score held-out code rows (codes int32 [B][T], T % 64 == 0, row b restricted to t < lengths[b]): per row nll_sum,

@@ -461,11 +461,11 @@ class WaveNet:
             self._side = torch.cuda.Stream(device=self.dev)
         return self._side
 
-    def _forward_step(self, x, spk, step):
+    def _forward_step(self, x, spk, step, lengths=None):
         """forward() as a pass of training step `step`: the only passes in which a front does what belongs to a training step alone."""
         self._jitter_step = step
         try:
-            return self.forward(x, spk)
+            return self.forward(x, spk, lengths=lengths) if lengths is not None else self.forward(x, spk)
         finally:
             self._jitter_step = None
 
@@ -659,13 +659,15 @@ class WaveNet:
         K.conv_gemm(x0=ws['h1'], in_relu=True, w=P['post2_w'], bias=P['post2_b'], out0=ws['logits'], B=B, T_in=T,
                     T_out=T, M=Q, C0=S, taps=[0])                                         # wavenet.py:94-96
 
-    def forward(self, x, spk, compute_grad_seed=True):
+    def forward(self, x, spk, compute_grad_seed=True, lengths=None):
         """model.py:145-151 up to the losses.  x [B][T] raw audio in [-1,1], spk int64 [B].
         Leaves logits (or d loss/d logits when compute_grad_seed) in the workspace and the
-        loss sums in self.loss_buf (no host sync)."""
+        loss sums in self.loss_buf (no host sync).  lengths: None, or what train_step takes: the loss and its gradient seed
+        cover t < lengths[b] alone (the seed is +0.0 behind it) and the mean is over sum(lengths) positions."""
+        B, T = x.shape
+        lens = self._train_lengths('forward', lengths, B, T)     # (refused before anything is launched)
         if self._pending and not self._in_step:      # a caller's own forward pass between deferred steps: settle those first
             self.finish_steps()
-        B, T = x.shape
         ws = self._workspace(B, T)
         if A.POISON:             # debug: every workspace buffer and the transposed-kernel scratch start the step as NaN
             A.repoison(ws['_poison'] + self._poison_T)
@@ -675,29 +677,74 @@ class WaveNet:
         self._encode(x, spk, ws)
         self._decode_layers(ws, plan)
         self.loss_buf.zero_()
-        N = B * T
-        K.softmax_xent(ws['logits'], ws['labels'], loss_sum=self.loss_buf[0:1],
-                       dlogits=ws['logits'] if compute_grad_seed else None, grad_scale=1.0 / N)  # model.py:91-94
+        N = ws['count'] = B * T if lens is None else sum(lens)      # the positions the loss is the mean over (losses())
+        if lens is None:
+            ws['dl'] = ws.get('dl_scale')
+            K.softmax_xent(ws['logits'], ws['labels'], loss_sum=self.loss_buf[0:1],
+                           dlogits=ws['logits'] if compute_grad_seed else None, grad_scale=1.0 / N)  # model.py:91-94
+        else:
+            if 'dl_scale' in ws:     # |d loss / d logits| <= 1 / count now: the fixed scale of its planes follows the count (no host read)
+                ws['dl'] = ws.setdefault('dl_masked', torch.empty(1, device=self.dev)).fill_(2.0 ** math.floor(math.log2(2.0 ** 13 * N)))
+            K.softmax_xent_ranged(ws['logits'], ws['labels'], loss_sum=self.loss_buf[0:1],
+                                  dlogits=ws['logits'] if compute_grad_seed else None, grad_scale=1.0 / N,
+                                  t_end=self._lengths_device(lens))
         self._front_loss(ws)
         return ws
+
+    _masked_training = None     # why a subclass cannot train on lengths (a message), or None: it can
+
+    def _row_lengths(self, who, lengths, B, T):
+        """lengths (None, a host sequence or a CPU tensor) as a list of B ints: positive multiples of _length_unit(), at most T;
+        anything else raises ValueError (named after `who`)."""
+        if lengths is None:
+            return None
+        unit = self._length_unit()
+        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if len(lens) != B:
+            raise ValueError('%s: %d lengths for a batch of %d' % (who, len(lens), B))
+        bad = [v for v in lens if v <= 0 or v > T or v % unit]
+        if bad:
+            raise ValueError('%s: lengths must be positive multiples of %d and at most T = %d (got %s)' % (who, unit, T, bad[:5]))
+        return lens
+
+    def _train_lengths(self, who, lengths, B, T):
+        """_row_lengths for a training pass, with what training on lengths cannot do refused."""
+        if lengths is None:
+            return None
+        if self._masked_training is not None:
+            raise NotImplementedError('%s: %s' % (who, self._masked_training))
+        if self.grad_sync is not None and getattr(self.grad_sync, 'active', True):
+            raise NotImplementedError('%s: lengths with data-parallel gradients (grad_sync) is not supported: the ranks would have to '
+                                      'agree on a global count of scored positions' % who)
+        return self._row_lengths(who, lengths, B, T)
+
+    def _lengths_device(self, lens):
+        """The lengths of one step as a device int32 [B]: staged in pinned host memory and copied without blocking.  The staging
+        block comes from torch's caching host allocator, which holds a block back until the copy that reads it has run: the host
+        may be any number of steps ahead of the device (the fp32 engine's step has no host read at all) and no step waits."""
+        host = torch.tensor(lens, dtype=torch.int32)
+        if self.dev.type != 'cuda':
+            return host
+        return host.pin_memory().to(self.dev, non_blocking=True)
 
     def _front_loss(self, ws):
         """The front's own loss sums into loss_buf[1:] (hook; none)."""
 
-    def forward_checked(self, x, spk, compute_grad_seed=False):
+    def forward_checked(self, x, spk, compute_grad_seed=False, lengths=None):
         """forward() for callers that do not go on to train_step (evaluation, summaries of a held-out batch).  On the guarded
         fp16x3 engine the activation planes are scaled with the PREVIOUS training step's max-abs values (1.0 on a fresh model):
         train_step reads the range flag and repeats a flagged step on the fp32 engine; a bare forward() does not.  This one
         does: the flag is zeroed, read after the pass (one host sync) and a flagged pass is repeated on the fp32 engine."""
+        lens = self._train_lengths('forward_checked', lengths, *x.shape)
         self.finish_steps()
         if not self.x3_guard:
-            return self.forward(x, spk, compute_grad_seed)
+            return self.forward(x, spk, compute_grad_seed, lens)
         self.x3_flag.zero_()
-        ws = self.forward(x, spk, compute_grad_seed)
+        ws = self.forward(x, spk, compute_grad_seed, lens)
         if (ws.get('x3_used') or ws.get('enc_x3')) and int(self.x3_flag.item()) != 0:
             self._x3_active = False
             try:
-                ws = self.forward(x, spk, compute_grad_seed)
+                ws = self.forward(x, spk, compute_grad_seed, lens)
             finally:
                 self._x3_active = True
         return ws
@@ -744,15 +791,7 @@ class WaveNet:
         if x.dim() != 2 or spk.numel() != x.shape[0]:
             raise ValueError('%s: x [B][T] and B speaker ids expected (got %s, %d ids)' % (who, tuple(x.shape), spk.numel()))
         B, T = x.shape
-        unit = self._length_unit()
-        lens = None
-        if lengths is not None:
-            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-            if len(lens) != B:
-                raise ValueError('%s: %d lengths for a batch of %d' % (who, len(lens), B))
-            bad = [v for v in lens if v <= 0 or v > T or v % unit]
-            if bad:
-                raise ValueError('%s: lengths must be positive multiples of %d and at most T = %d (got %s)' % (who, unit, T, bad[:5]))
+        lens = self._row_lengths(who, lengths, B, T)
         self.finish_steps()
         ws = self._workspace(B, T, 'score')
         t_end = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=self.dev)
@@ -818,7 +857,7 @@ class WaveNet:
     def losses(self, ws):
         """(loss, cross-entropy, 0, 0) as python floats: the WaveNet's loss is the cross-entropy alone (synchronises; hook)."""
         self.finish_steps()
-        ce = float(self.loss_buf[0]) / (ws['B'] * ws['T'])
+        ce = float(self.loss_buf[0]) / ws.get('count', ws['B'] * ws['T'])     # (count: sum(lengths) of a masked step)
         return ce, ce, 0.0, 0.0
 
     # ------------------------------------------------------------------ backward
@@ -868,7 +907,7 @@ class WaveNet:
             # the convs around the stack on the fp16x3 engine (forward: _decode_layers): d logits as planes with a fixed scale
             # (|d logits| <= 1 / (B T)), each input gradient hands the next one its planes, the weight gradients split their fp32
             # operands in registers (p = relu of the forward tensor), bias and condition sums ride along
-            dl = ws['dl_scale']
+            dl = ws['dl']               # (forward(): dl_scale, or the masked step's own)
             K.f16x3_pack_weights_t(P['post2_w'], ws['wpost2t'], Q, S, Q, Q, 0, 1.0, scale_dev=sc('WH'), mode=md)
             K.f16x3_pack_weights_t(P['post1_w'], ws['wpost1t'], S, S, S, S, 0, 1.0, scale_dev=sc('WH'), mode=md)
             K.f16x3_pack_weights_t(P['skip0_w'], ws['wskip0t'], S, R, S, S, 0, 1.0, scale_dev=sc('WH'), mode=md)
@@ -1217,27 +1256,32 @@ class WaveNet:
         out = self._gn['out'].tolist()
         return {'global': out[0], 'scale': out[1], 'segments': OrderedDict(zip(self._gn['names'], out[2:]))}
 
-    def train_step(self, x, spk, on_forward=None):
+    def train_step(self, x, spk, on_forward=None, lengths=None):
         """One sess.run(train_op) (train.py:104-114).  on_forward(ws): called between the forward and the backward pass of the
         step that is kept (tests snapshot the relu inputs there: backward overwrites them in place).  With self.grad_sync set (data parallel)
         the flat gradient is sum-all-reduced over RCCL in buckets that overlap the backward pass, and averaged.
         Guarded fp16x3 engine: a step whose planes left fp16's range is repeated on the fp32 engine, which also measures the
         max-abs values the next step's scales come from.  The step's range flag is read before the optimiser runs (one host sync
-        per step) -- or, with self.defer_guard (bench.py, train.py), one step LATE: see _train_step_deferred."""
+        per step) -- or, with self.defer_guard (bench.py, train.py), one step LATE: see _train_step_deferred.
+        lengths (None: the step as it always was): B row lengths, a host sequence or a CPU tensor of positive multiples of
+        _length_unit(), at most T.  The loss is then the mean cross-entropy over the sum(lengths) positions t < lengths[b], and
+        every gradient is that loss's: the stack is causal, so a gradient seed that is zero from lengths[b] on makes whatever
+        the row holds behind it immaterial.  Checked before anything is launched; no host synchronisation is added."""
+        lens = self._train_lengths('train_step', lengths, *x.shape) if lengths is not None else None
         if self.defer_guard and self.x3_guard and on_forward is None:
-            return self._train_step_deferred(x, spk)
+            return self._train_step_deferred(x, spk, lens)
         self.finish_steps()
-        return self._train_step_now(x, spk, on_forward)
+        return self._train_step_now(x, spk, on_forward, lengths=lens)
 
-    def _train_step_now(self, x, spk, on_forward=None, known_flagged=False):
+    def _train_step_now(self, x, spk, on_forward=None, known_flagged=False, lengths=None):
         """The step with its range flag read on the spot.  known_flagged: the fp16x3 attempt of this step already ran and
-        raised the flag (deferred mode): go straight to the repeat."""
+        raised the flag (deferred mode): go straight to the repeat.  lengths: train_step's, already checked."""
         guarded, world, ws = self.x3_guard and known_flagged, 1, None
         gs0 = self.global_step           # (every pass of this step is a pass of step gs0: _forward_step)
         if not known_flagged:
             if self.x3_guard:
                 self.x3_flag.zero_()
-            ws = self._forward_step(x, spk, gs0)
+            ws = self._forward_step(x, spk, gs0, lengths)
             if on_forward is not None:
                 on_forward(ws)
             self.backward(x, spk, ws)
@@ -1251,7 +1295,7 @@ class WaveNet:
                 self._x3_active = False
                 try:
                     self.x3_amax.zero_()
-                    ws, am = self._forward_step(x, spk, gs0), self._slots(self.x3_amax, True)
+                    ws, am = self._forward_step(x, spk, gs0, lengths), self._slots(self.x3_amax, True)
                     for l in range(1, self.L):       # what the layer-input planes would have held (net[L] feeds nothing)
                         K.f16x3_amax(ws['net'][l], am('X', l))
                     K.f16x3_amax(ws['skip'], am('SK'))
@@ -1271,7 +1315,7 @@ class WaveNet:
         self.apply_gradients(1.0 / world)
         return ws
 
-    def _train_step_deferred(self, x, spk):
+    def _train_step_deferred(self, x, spk, lengths=None):
         """The guarded step without a host sync on its path.  Reading the range flag before the optimiser drains the launch queue
         once per step, and the host then needs ~1.2 ms of the next step to get ahead of the GPU again (bench.py's shape: 26.6 ->
         25.5 ms).  Here the verdict stays on the device: the flag is latched into the sticky x3_void, the optimiser is enqueued
@@ -1287,7 +1331,7 @@ class WaveNet:
         self.x3_flag.zero_()
         self._in_step = True
         try:
-            ws = self._forward_step(x, spk, self.global_step)
+            ws = self._forward_step(x, spk, self.global_step, lengths)
             self.backward(x, spk, ws)
         finally:
             self._in_step = False
@@ -1311,7 +1355,7 @@ class WaveNet:
         self._void_host[slot:slot + 1].copy_(self.x3_void, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        self._pending.append({'x': x, 'spk': spk, 'gs0': gs0, 'ev': ev, 'slot': slot})
+        self._pending.append({'x': x, 'spk': spk, 'gs0': gs0, 'ev': ev, 'slot': slot, 'lengths': lengths})      # (lengths: the step's own, for its repeat)
         self.host_enqueue_ms = (time.perf_counter() - t_host) * 1e3        # what the host needs to enqueue one step (it must stay below the step's GPU time)
         while len(self._pending) > 1:
             self._resolve_oldest()
@@ -1328,7 +1372,7 @@ class WaveNet:
         self.x3_void.zero_()
         self.global_step = p['gs0']
         for n, q in enumerate(pend):
-            self._train_step_now(q['x'], q['spk'], known_flagged=(n == 0))
+            self._train_step_now(q['x'], q['spk'], known_flagged=(n == 0), lengths=q['lengths'])
 
     def finish_steps(self):
         """Resolve the deferred steps (defer_guard): afterwards parameters, gradients and losses are those of the last step."""
