@@ -209,12 +209,20 @@ int vqw_transpose(const float* src, float* dst, int batch, int rows, int cols,
  * fp32 with separately rounded multiply and add; idx = lowest index of the minimum.
  * Outputs: idx int64 [B][Tz]; e_k [B][D][Tz]; z_q = z_e + (e_k - z_e) written to
  * zq[b*zq_bstride + d*Tz + t] (so it can land inside the decoder condition tensor);
- * mind [B][Tz] = winning distance.                                                     */
+ * mind [B][Tz] = winning distance.  Each of e_k, zq and mind may be NULL (not written).
+ * A distance that is not below +inf (a NaN in the row, a square that overflows) never wins; a row all of whose distances
+ * are such gets idx 0 and mind = +inf -- the argmin of oracle/vqw_oracle.c, which starts from (+inf, 0) and takes strict
+ * improvements only -- and e_k / zq of code 0.  D % 4 == 0, emb 16-byte aligned.             */
 int vqw_vq_nearest_fwd(const float* z_e, const float* emb, int64_t* idx, float* e_k,
                        float* zq, int64_t zq_bstride, float* mind, int B, int D, int Tz,
                        int K, vqw_stream_t s);
 /* Gradients of model.py:73,100,103 (Appendix A-5 of SURVEY.md):
- *   dz_e = dzq + cscale*(z_e - e_k);   demb[idx] += escale*(e_k - z_e)                  */
+ *   dz_e = dzq + cscale*(z_e - e_k);   demb[idx] += escale*(e_k - z_e)
+ * dzq is read at dzq[b*dzq_bstride + d*Tz + t] (NULL: zero); dz_e or demb may be NULL (not both).  demb [K][D] is ADDED to
+ * by fp32 atomics, and rows of codes no frame chose keep their bits.  Two kernels: when demb is asked for and the table
+ * fits a block's LDS, K*D*4 <= 144 KiB (147 456 bytes), the sums are gathered in an LDS copy of the table first (at most 64
+ * blocks of 256 threads, ~16 elements per thread, striding over the rest); else -- demb NULL, or a larger table -- one
+ * plain grid-stride kernel (at most 2048 blocks of 256 threads) adds straight to demb.                         */
 int vqw_vq_nearest_bwd(const float* z_e, const float* e_k, const int64_t* idx,
                        const float* dzq, int64_t dzq_bstride, float* dz_e, float* demb,
                        float cscale, float escale, int B, int D, int Tz, int K,
@@ -334,7 +342,9 @@ int vqw_code_histogram(const int64_t* idx, const int32_t* f_end, int32_t* counts
  * w[Cc][Mall] (Mall = L * 2R + S); cond [B][Cc][Tz], out / dce [B][Mall][Tz], dcond [B][Cc][Tz].
  *   fwd:    out[b][m][t]   = sum_c w[c][m] cond[b][c][t]
  *   wgrad:  dw[c][m]      += sum_{b,t} cond[b][c][t] dce[b][m][t]     (TF Conv2DBackpropFilter); Cc <= 128, Tz % 4 == 0;
- *           dw is the zeroed gradient buffer (two batch ranges may meet in it by fp32 atomics)
+ *           dw is the zeroed gradient buffer (two batch ranges may meet in it by fp32 atomics): the batch is split into
+ *           KS = 2 ranges [ks*B/KS, (ks+1)*B/KS) when B >= 2 and the ceil(Mall/32) * ceil(Cc/32) tiles are fewer than
+ *           8 * CUs of the current device, else KS = 1 (one wave walks the whole batch and adds its sum to dw once)
  *   dgrad:  dcond[b][c][t] = sum_m w[c][m] dce[b][m][t]               (TF Conv2DBackpropInput); Cc <= 128, Mall % 4 == 0;
  *           scratch: vqw_cond_proj_dgrad_scratch_floats() floats (partial sums over ranges of m, added in a fixed order)
  * fp32 MFMA (v_mfma_f32_32x32x2_f32) fed straight from global memory, one tile per wave: a contraction of Cc ~ 80 over
