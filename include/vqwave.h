@@ -690,7 +690,12 @@ int vqw_f16x3_out_conv(const vqw_f16x3_out_desc* d, vqw_stream_t s);
  *   dgrad = 0: out[b][m][t] = bn_scale[m] * relu(sum_j sum_c w[j][c][m] x[b][c][2t + j - pad_left] + bias[m]) + bn_shift[m],
  *              t < T; xp = vqw_f16x3_split_activations(x [B][Cin][2T], mode | VQW_X3_S2D); save_r (or NULL) gets the relu output
  *   dgrad = 1: out[b][m][u] (u < 2T) = sum_{j, t: 2t + j - pad_left = u} sum_o wt[j][o][m] dy[b][o][t]; xp = plain planes of dy [B][Cin][T]
- * Cin % 32 == 0, M % 128 == 0 (B * T need not be a multiple of the 256-column tiles).  Results are scaled by w_scale_inv / (x_scale[0] * w_scale[0]).           */
+ * Cin % 32 == 0, M % 128 == 0 (B * T need not be a multiple of the 256-column tiles).  Results are scaled by w_scale_inv / (x_scale[0] * w_scale[0]).
+ * Samples outside [0, 2T) read zero on both sides: taps that reach behind 2T read zero as those before 0 do, so the padding behind
+ * is implicit in ks and pad_left (ks - 2 - pad_left zeros; a negative count means the last taps never reach the end), and the
+ * elements of an input gradient that no tap reaches (u = 2T - 1 with pad_left = ks - 1) are written as zero.  A column tile may
+ * straddle batch rows; rows of the operand planes past B * T in the last column tile may be READ (planes are read through their
+ * own extent only) but nothing is stored for them: out, save_r and the input gradient are written at exactly B * M * T (2T) floats. */
 typedef struct vqw_f16x3_sconv_desc {
     const void* xp;
     const void* wp;
@@ -712,7 +717,15 @@ typedef struct vqw_f16x3_sconv_desc {
      * and runs the epilogue (results are bitwise reproducible).  ksplit: 0 = chosen by the launch's tile count, 1 = off, n = n
      * blocks per tile (the K steps of every parity must divide into n even parts).  split_slab: blocks * rows per block * 256
      * floats (CUs * 65536 always suffices); split_counters: one int per tile, ZERO before the first launch (left zero by every
-     * launch).                                                                                                              */
+     * launch).
+     * Exactly: only 128-row blocks split (shape 0 or 2).  With tiles = (M / 128) * ceil(B * T / 256) * (dgrad ? 2 : 1) a launch of S
+     * blocks per tile needs split_slab_floats >= tiles * S * 128 * 256 and split_counters_n >= tiles, writes every float of that part
+     * of the slab and nothing behind it, and is refused where either is smaller or where S does not divide the K steps (Cin / 16 per
+     * tap) of every parity into even parts of at least 8; launches of different tile counts may share the counters without zeroing
+     * in between.  ksplit = 0 takes the largest S <= 8 that fits with tiles * S <= CUs; where none does but three blocks per tile of
+     * the unsplit launch would fit ((tiles / parities) * 3 <= CUs), the largest with tiles * S <= 2 * CUs; otherwise the launch runs
+     * unsplit.  With a forced shape 1, 3, 4 or 5 the scratch and an explicit ksplit > 1 are IGNORED (the launch runs unsplit and
+     * touches neither); ksplit = 1 touches neither on any shape.                                                             */
     float* split_slab;
     int64_t split_slab_floats;
     int32_t* split_counters;
