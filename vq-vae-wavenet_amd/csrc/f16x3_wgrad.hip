@@ -2,6 +2,7 @@
 #include <string.h>
 
 #include "f16x3.h"
+#include "f16x3_wgrad_layout.h"
 
 namespace {
 
@@ -10,6 +11,14 @@ namespace {
 #define VQW_WG_PAT_B 2      // ... and address computations / requests per MFMA in the second stage
 #endif
 constexpr int NSTG = 4;      // LDS stages of the weight-gradient kernel
+#ifndef VQW_WG_DMA_DEPTH
+#define VQW_WG_DMA_DEPTH 2   // both operands as planes (LDS-DMA loop): stages of requests left in flight across a step's barrier
+#endif
+#ifndef VQW_WG_DMA_PAT_MEM
+#define VQW_WG_DMA_PAT_MEM 1 // ... its issue pattern: LDS reads / requests per MFMA ...
+#define VQW_WG_DMA_PAT_ALU 2 // ... and address computations / q-sum arithmetic per MFMA
+#endif
+constexpr int WG_DMA_DEPTH = VQW_WG_DMA_DEPTH, WG_DMA_NSTG = WG_DMA_DEPTH + 2;     // (a stage is requested DEPTH + 1 steps before it is read)
 
 // ---------------------------------------------------------------------------------------------------------------
 // Weight gradients on the fp16 matrix pipe:  dW[j][c][o] += sum_{b,t} p[b][c][t + shift_j] * q[b][o][t]
@@ -116,9 +125,14 @@ __device__ __forceinline__ uint2 split4(const f32x4 v, float sc, uint2& lo) {
 constexpr int WG_QSTR = 576, WG_QPL = 16 * WG_QSTR;                       // bytes per time step / per plane of a stage's q image
 // PP: the same for p (the layer input planes the forward pass wrote, the gated planes): a tap's shift is then a row offset of
 // the planes -- no unaligned 16-byte windows, no ODD variant -- and the loop converts nothing at all.
+// QP && PP: nothing is converted, so nothing needs to pass through registers -- both operands go global -> LDS by LDS-DMA (x3_dma16)
+// into a ring of WG_DMA_NSTG 16-step stages, as in the conv main loop (f16x3_mainloop).  A DMA writes lane-linear 1-KiB pieces, which
+// rules the padded rows out: the image is the XOR-permuted one of f16x3_wgrad_layout.h (8 KiB per plane and stage, no padding).
 template <bool QP, bool PP, bool BF> struct WgStage {
-    static constexpr int BOFF = PP ? (BF ? 1 : 2) * WG_QPL : 16 * 1024;            // q image behind the p image
-    static constexpr int BYTES = BOFF + (QP ? (BF ? 1 : 2) * WG_QPL : 16 * 1024);
+    static constexpr bool DMA = QP && PP;
+    static constexpr int BOFF = DMA ? (BF ? 1 : 2) * wgl::PLANE : (PP ? (BF ? 1 : 2) * WG_QPL : 16 * 1024);      // q image behind the p image
+    static constexpr int BYTES = BOFF + (DMA ? (BF ? 1 : 2) * wgl::PLANE : (QP ? (BF ? 1 : 2) * WG_QPL : 16 * 1024));
+    static constexpr int STAGES = DMA ? WG_DMA_NSTG : NSTG;
 };
 __device__ __forceinline__ uint2 wg_tr_read(const char* p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -373,7 +387,118 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_kernel(const WgArgs a) {
     };
 
     const int npairs = s_end - s_begin;
-    if (npairs > 0) {
+    if constexpr (QP && PP) {
+        // ---- both operands as planes: LDS-DMA ring (no rgp / rgq, no ds_write, no commit).  One step = one 16-step stage, as in
+        // f16x3_mainloop: pair s of the K range is steps 2 (s - s_begin), 2 (s - s_begin) + 1, so the stages -- and with them the
+        // fragments and the order of the MFMAs -- are those of the register loop and dW is the same bit for bit.
+        constexpr int P = 4 * NPL;             // 1-KiB pieces a wave requests per stage: 2 operands x NPL planes x 8 pieces over 4 waves
+        const int wvu = __builtin_amdgcn_readfirstlane(wv);
+        // Piece w = wvu * P + k of a stage, in image order: operand (p, q), plane, time half, chunk group.  Two planes: wave 0 / 1 move
+        // p's plane 0 / 1, wave 2 / 3 q's; one plane (bf16): wave 0 / 1 move p's time half 0 / 1, wave 2 / 3 q's.  A wave therefore
+        // requests from ONE resource with ONE shift (q: none).
+        const bool w_is_p = wvu < 2;
+        const int w_plane = BF ? 0 : (wvu & 1), w_shift = w_is_p ? shift : 0;
+        const size_t pl1q = (QP && !BF) ? (size_t)pr.q_KC * NBq * 16 : 0, pl1p = (PP && !BF) ? (size_t)pr.p_KC * NBq * 16 : 0;
+        // (requests past the block's last stage, rows outside the batch row and steps behind T carry the offset 2^31, outside every
+        // resource -- qspan < 2^31 -- whatever the problem and the number of planes: they land as zeros)
+        const u32x4 rs = x3_rsrc_words((w_is_p ? ppb : qpb) + (w_plane ? (w_is_p ? pl1p : pl1q) : 0), qspan);
+        const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+        const unsigned wdst = lds0 + (unsigned)(wvu * P * wgl::PIECE);
+        // lane = 8 step + slot fetches chunk swz(step, slot) of the piece's chunk group at time step `step` of the piece's time half
+        const int dstep = lane >> 3;
+        const int lane_off = (int)((size_t)wgl::swz(dstep, lane & 7) * NBq * 16) + (dstep + w_shift) * 16;
+        const int cg_off = (int)(8 * NBq * 16);                    // one chunk group further
+        // the stage being requested: batch row (as a byte offset of its first row) and first time step, advanced by 16 steps at a time
+        const int row_steps = a.pairs_row * 32;
+        int rq_b = s_begin / a.pairs_row, rq_t = (s_begin - rq_b * a.pairs_row) * 32, rq_n = 0;
+        int rq_row = rq_b * T * 16;
+        const int nsteps = 2 * npairs;
+        auto request = [&](int k0, int k1) {       // pieces [k0, k1) of the wave's P of stage rq_n
+            const unsigned dst = wdst + (unsigned)((rq_n % WG_DMA_NSTG) * STGB);
+            const bool live = rq_n < nsteps;
+#pragma unroll
+            for (int k = k0; k < k1; ++k) {
+                const int th = BF ? (wvu & 1) : (k >> 2), cg = k & 3;
+                const int tt = rq_t + 8 * th + dstep + w_shift;
+                const int off = (live && tt >= 0 && tt < T) ? lane_off + rq_row + (rq_t + 8 * th) * 16 + cg * cg_off : (int)0x80000000;
+                x3_dma16(rs, dst + (unsigned)(k * wgl::PIECE), off);
+            }
+        };
+        auto advance = [&]() {
+            ++rq_n;
+            rq_t += 16;
+            const bool wrap = rq_t >= row_steps;
+            rq_t = wrap ? 0 : rq_t;
+            rq_row += wrap ? T * 16 : 0;
+        };
+        const int trl = wgl::tr_lane(lane);
+        auto read_a_dma = [&](int i, int stage) {
+            const char* st = smem + (stage % WG_DMA_NSTG) * STGB + wgl::piece_off(0, 0, i >> 1) + (trl ^ ((i & 1) * 64));
+#pragma unroll
+            for (int pl = 0; pl < NPL; ++pl) {
+                const uint2 k0 = wg_tr_read(st + pl * wgl::PLANE), k1 = wg_tr_read(st + pl * wgl::PLANE + 4 * wgl::SLOTS * 16);
+                fa[i][pl] = make_uint4(k0.x, k0.y, k1.x, k1.y);
+            }
+        };
+        auto read_b_dma = [&](uint4 (&b)[2][2], int stage) {
+            const char* st = smem + (stage % WG_DMA_NSTG) * STGB + BOFF + wv * wgl::PIECE;
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int pl = 0; pl < NPL; ++pl) {
+                    const char* sj = st + (trl ^ (j * 64)) + pl * wgl::PLANE;
+                    const uint2 k0 = wg_tr_read(sj), k1 = wg_tr_read(sj + 4 * wgl::SLOTS * 16);
+                    b[j][pl] = make_uint4(k0.x, k0.y, k1.x, k1.y);
+                }
+        };
+        // The compiler does not count the requests (x3_dma16): every wait for them is written here.  Never __syncthreads() while one
+        // is in flight -- its fence would drain the ring.
+        auto wait_barrier = [&](auto n_c) {
+            constexpr int N = decltype(n_c)::value;
+            static_assert(N < 64, "vmcnt is a 6-bit counter");
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(N) : "memory");
+        };
+        if (npairs > 0) {
+            uint4 fbn[2][2];
+#pragma unroll
+            for (int s = 0; s < WG_DMA_NSTG; ++s) { request(0, P); advance(); }
+            wait_barrier(std::integral_constant<int, (WG_DMA_NSTG - 1) * P>{});
+#pragma unroll
+            for (int i = 0; i < 8; ++i) read_a_dma(i, 0);
+            read_b_dma(fb, 0);
+            // Step s (one barrier): the wait retires this wave's pieces of stage s + 1 (DEPTH newer stages stay in flight) and its
+            // fragment reads of stage s; behind the barrier stage s + 1 is complete and slot s % NSTG is free, so stage s + NSTG is
+            // requested into it, in four even parts behind the fragment reads of stage s + 1, all in the shadow of stage s's MFMAs.
+            // No conditionals in the body; the last step re-reads its own stage (never used).
+            auto step = [&](const uint4 (&bc)[2][2], uint4 (&bn)[2][2], int s) {
+                wait_barrier(std::integral_constant<int, WG_DMA_DEPTH * P>{});
+                const int sn = s + 1 < nsteps ? s + 1 : s;
+                sum_frag(bc);
+                read_b_dma(bn, sn);
+#pragma unroll
+                for (int i = 0; i < 8; i += 2) {
+                    mfma_rows(i, bc);
+                    read_a_dma(i, sn);
+                    read_a_dma(i + 1, sn);
+                    request(P * (i / 2) / 4, P * (i / 2 + 1) / 4);
+                }
+                advance();
+#pragma unroll
+                for (int k_ = 0; k_ < (BF ? 2 : 6) * 8; ++k_) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100 | 0x200 | 0x020, BF ? 2 : VQW_WG_DMA_PAT_MEM, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002 | 0x004, VQW_WG_DMA_PAT_ALU, 0);
+                }
+            };
+            for (int s = 0; s < nsteps; s += 2) {
+                step(fb, fbn, s);
+                step(fbn, fb, s + 1);
+                if (do_sum) flush_pair(s_begin + (s >> 1));     // both stages of the pair are in qs_pair
+            }
+            // the requests past the last stage: nothing of the loop may be in flight when the slab stores start
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    } else if (npairs > 0) {
         set_pair(s_begin);
         set_commit_pair(s_begin);
 #pragma unroll
@@ -590,7 +715,7 @@ int vqw_f16x3_wgrad_batch(const vqw_f16x3_wgrad_desc* dp, int nprob, vqw_stream_
     const kfn_t kfn = s2 ? wgrad_f16x3_kernel<false, false, true>
                          : (pp ? kpp[(bf ? 1 : 0) + (qp ? 2 : 0)] : (qp ? kqp : ktab)[(odd ? 1 : 0) + 2 * (bf ? 1 : 0)]);
     const int npl = bf ? 1 : 2;
-    const int lds = NSTG * ((pp ? npl * WG_QPL : 16 * 1024) + (qp ? npl * WG_QPL : 16 * 1024));
+    const int lds = (pp && qp) ? WG_DMA_NSTG * 2 * npl * wgl::PLANE : NSTG * ((pp ? npl * WG_QPL : 16 * 1024) + (qp ? npl * WG_QPL : 16 * 1024));
     if (const int rc = x3_launch(kfn, tiles * nsplit, lds, st, a, "vqw_f16x3_wgrad")) return rc;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(65536 / 4 / 256, tiles), dim3(256), 0, st, a);
     VQW_LAUNCH_CHECK("vqw_f16x3_wgrad");
