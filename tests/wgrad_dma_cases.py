@@ -1,4 +1,4 @@
-"""Seeded cases for the weight gradients with BOTH operands as planes (wgrad_f16x3_kernel<.., QP, PP>: the LDS-DMA loop), at the
+"""Seeded cases for the weight gradients with BOTH operands as planes (wgrad_f16x3_dma_kernel<BF>: the LDS-DMA loop), at the
 shapes where a ring of 16-step stages can go wrong: K ranges shorter than the ring, one pair per block, a long wrap, taps that
 shift by more than a batch row (zeros landing over ring slots that held finite data), batches whose problems differ, output
 column blocks, rows that are no multiple of the 32-step pairs, the stride-2 form with parity blocks, one bf16 plane.

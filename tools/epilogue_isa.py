@@ -24,35 +24,13 @@ Text order is execution order inside a straight-line epilogue; where a kernel ho
 block-uniform branch they follow one another (the FIFO is emptied at s_endpgm and at unconditional branches).
 Only loads, stores and wait counts are looked at."""
 import argparse
-import importlib.util
 from concurrent.futures import ThreadPoolExecutor
-import os
 import re
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = [os.path.join(ROOT, 'vq-vae-wavenet_amd', 'csrc', 'f16x3_%s.hip' % n) for n in ('conv', 'gate_bwd', 'sconv', 'wgrad')]
+from isa_listing import compile_asm, demangle, short, split_kernels
 
-
-def compile_asm(out):
-    spec = importlib.util.spec_from_file_location('vqw_build', os.path.join(ROOT, 'vq-vae-wavenet_amd', 'build.py'))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    cmd = [b._hipcc()] + b.FLAGS + ['--cuda-device-only', '-S', '-o', '-']
-    with ThreadPoolExecutor(len(SRCS)) as ex:
-        parts = list(ex.map(lambda s: subprocess.run(cmd + [s], check=True, capture_output=True, text=True).stdout, SRCS))
-    with open(out, 'w') as f:
-        f.write(''.join(parts))
-
-
-def demangle(names):
-    try:
-        r = subprocess.run(['c++filt'] + names, capture_output=True, text=True, check=True)
-        return dict(zip(names, r.stdout.splitlines()))
-    except (OSError, subprocess.CalledProcessError):
-        return {n: n for n in names}
+SRCS = ['f16x3_%s' % n for n in ('conv', 'gate_bwd', 'sconv', 'wgrad')]
 
 
 LOAD = re.compile(r'^(global|buffer|flat)_load_')
@@ -150,52 +128,27 @@ def main():
     ap.add_argument('--asm', help='read this assembly file instead of compiling')
     ap.add_argument('--keep', help='keep the compiled assembly here')
     a = ap.parse_args()
-    path = a.asm
-    tmp = None
-    if not path:
-        path = a.keep
-        if not path:
-            tmp = tempfile.mkdtemp()
-            path = os.path.join(tmp, 'f16x3.s')
-        compile_asm(path)
-    kernels, name, body = {}, None, []
-    meta = {}
-    with open(path) as f:
-        for line in f:
-            s = line.strip()
-            m = re.match(r'^(_Z\w*f16x3_kernel\w*):', s)
-            if m:
-                name, body = m.group(1), []
-                continue
-            if name is None:
-                m = re.match(r'^; (NumVgprs|NumAgprs|ScratchSize): (\d+)', s)
-                if m and meta.get('_last'):
-                    meta[meta['_last']][m.group(1)] = int(m.group(2))
-                continue
-            if s and not s.startswith((';', '.')) and not s.endswith(':'):
-                body.append(s)
-            if s.startswith('.section') or s.startswith('.amdhsa_kernel'):
-                kernels[name] = body
-                meta[name] = {}
-                meta['_last'] = name
-                name = None
-    meta.pop('_last', None)
+    if a.asm:
+        text = open(a.asm).read()
+    else:
+        with ThreadPoolExecutor(len(SRCS)) as ex:
+            text = ''.join(ex.map(compile_asm, SRCS))
+        if a.keep:
+            with open(a.keep, 'w') as f:
+                f.write(text)
+    kernels = split_kernels(text)
     names = [n for n in kernels if re.search(r'(gate|out|head|gate_bwd)_f16x3_kernel', n)]
     dm = demangle(names)
     print('# tools/epilogue_isa.py: vector-memory instructions behind the last MFMA (see the tool for the legend)')
     for n in names:
-        ev = events(kernels[n])
+        ev = events([s for s in kernels[n][0] if s and not s.startswith((';', '.')) and not s.endswith(':')])
         exposed, dmax, dmin, br, nst, nbare = counts(ev)
-        mt = meta.get(n, {})
-        short = re.sub(r'\(anonymous namespace\)::|void |\(.*\)$', '', dm[n])
-        print('\n%s' % short)
+        mt = kernels[n][2]
+        print('\n%s' % short(dm[n]))
         print('  NumVgprs %s  NumAgprs %s  ScratchSize %s' % (mt.get('NumVgprs', '?'), mt.get('NumAgprs', '?'), mt.get('ScratchSize', '?')))
         print('  loads->w(0) %d   depth@store max %d min %d, %d of %d stores with no load in flight   branches %d' % (exposed, dmax, dmin, nbare, nst, br))
         for l in compact(ev):
             print(l)
-    if tmp:
-        os.remove(path)
-        os.rmdir(tmp)
 
 
 if __name__ == '__main__':

@@ -1,9 +1,9 @@
 """What does the main loop of the planes-both weight-gradient kernels issue?  ("Weight gradients")
 
-    python tools/wgrad_loop_isa.py [--asm FILE.s] > profiles/wgrad_dma_isa_after.txt
+    python tools/wgrad_loop_isa.py [--asm FILE.s] > profiles/wgrad_split_isa.txt
 
 Compiles vq-vae-wavenet_amd/csrc/f16x3_wgrad.hip to gfx950 assembly with build.py's FLAGS (or reads a listing made earlier) and
-prints, for the wgrad_f16x3_kernel instantiations with both operands as planes (QP && PP), every vector-memory, LDS, wait, barrier
+prints, for the wgrad_f16x3_dma_kernel instantiations (both operands as planes), every vector-memory, LDS, wait, barrier
 and branch instruction from the first s_barrier to the last `s_waitcnt vmcnt(0)` in front of the slab stores, in text order:
 
     D  an LDS-DMA request (buffer_load ... lds)    L  another load          S  a store         A  an atomic
@@ -12,22 +12,10 @@ and branch instruction from the first s_barrier to the last `s_waitcnt vmcnt(0)`
 
 Runs are folded (T*4).  Between the loop's barriers there should be no w(0) and no W."""
 import argparse
-import importlib.util
-import os
 import re
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'vq-vae-wavenet_amd', 'csrc', 'f16x3_wgrad.hip')
-
-
-def compile_asm():
-    spec = importlib.util.spec_from_file_location('vqw_build', os.path.join(ROOT, 'vq-vae-wavenet_amd', 'build.py'))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    cmd = [b._hipcc()] + b.FLAGS + ['--cuda-device-only', '-S', '-o', '-', SRC]
-    return subprocess.run(cmd, check=True, capture_output=True, text=True).stdout
+from isa_listing import compile_asm, demangle, short, split_kernels
 
 
 def token(s):
@@ -80,37 +68,16 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--asm', help='read this assembly file instead of compiling')
     a = ap.parse_args()
-    text = open(a.asm).read() if a.asm else compile_asm()
-    kernels, meta, name, body = {}, {}, None, []
-    last = None
-    for line in text.splitlines():
-        s = line.strip()
-        m = re.match(r'^(_Z\w*wgrad_f16x3_kernel\w*):', s)
-        if m:
-            name, body = m.group(1), []
-            continue
-        if name is None:
-            m = re.match(r'^; (NumVgprs|NumAgprs|ScratchSize): (\d+)', s)
-            if m and last:
-                meta[last][m.group(1)] = int(m.group(2))
-            continue
-        if s.startswith('.section') or s.startswith('.amdhsa_kernel'):
-            kernels[name], meta[name], last, name = body, {}, name, None
-            continue
-        if s and not s.startswith(';') and (not s.startswith('.') or re.match(r'^\.LBB\w+:', s)):
-            body.append(s)
-    # template arguments <ODD, BF, S2, QP, PP>: the instantiations with QP && PP
-    names = [n for n in kernels if re.search(r'kernelILb\dELb\dELb\dELb1ELb1EE', n)]
-    try:
-        dm = dict(zip(names, subprocess.run(['c++filt'] + names, capture_output=True, text=True, check=True).stdout.splitlines()))
-    except (OSError, subprocess.CalledProcessError):
-        dm = {n: n for n in names}
+    kernels = split_kernels(open(a.asm).read() if a.asm else compile_asm('f16x3_wgrad'))
+    dm = demangle([n for n in kernels if 'wgrad_f16x3_dma_kernel' in n])
+    names = sorted(dm, key=dm.get)          # <false> (fp16x3) before <true> (bf16), whatever the order in the listing
     print('# tools/wgrad_loop_isa.py: the planes-both weight-gradient loop, first barrier to the wait before the slab stores (see the tool for the legend)')
     for n in names:
-        b = kernels[n]
+        # instructions and branch targets
+        b = [s for s in kernels[n][0] if s and not s.startswith(';') and (not s.startswith('.') or re.match(r'^\.LBB\w+:', s))]
         bars = [i for i, l in enumerate(b) if l.split()[0] == 's_barrier']
-        mt = meta.get(n, {})
-        print('\n%s' % re.sub(r'\(anonymous namespace\)::|void |\(.*\)$', '', dm[n]))
+        mt = kernels[n][2]
+        print('\n%s' % short(dm[n]))
         print('  NumVgprs %s  NumAgprs %s  ScratchSize %s' % (mt.get('NumVgprs', '?'), mt.get('NumAgprs', '?'), mt.get('ScratchSize', '?')))
         if not bars:
             print('  (no s_barrier)')

@@ -1,4 +1,7 @@
-// fp16x3 engine: weight gradients
+// fp16x3 engine: weight gradients.  Two kernels over one work decomposition (WgArgs, wg_decode) and one slab reduction:
+//   wgrad_f16x3_kernel<ODD, BF, S2, QP, PP>  the register loop: at least one operand is read as fp32 and converted on the way to LDS
+//   wgrad_f16x3_dma_kernel<BF>               both operands as planes: global -> LDS by LDS-DMA, nothing passes through registers
+// wg_kernel() maps a launch to one of the 13 instantiations and its LDS bytes.
 #include <string.h>
 
 #include "f16x3.h"
@@ -7,12 +10,12 @@
 namespace {
 
 #ifndef VQW_WG_PAT_A
-#define VQW_WG_PAT_A 4     // weight-gradient loop: VALU / LDS instructions per MFMA while a chunk is converted ...
+#define VQW_WG_PAT_A 4     // register loop: VALU / LDS instructions per MFMA while a chunk is converted ...
 #define VQW_WG_PAT_B 2      // ... and address computations / requests per MFMA in the second stage
 #endif
-constexpr int NSTG = 4;      // LDS stages of the weight-gradient kernel
+constexpr int NSTG = 4;      // LDS stages of the register kernel
 #ifndef VQW_WG_DMA_DEPTH
-#define VQW_WG_DMA_DEPTH 2   // both operands as planes (LDS-DMA loop): stages of requests left in flight across a step's barrier
+#define VQW_WG_DMA_DEPTH 2   // LDS-DMA kernel: stages of requests left in flight across a step's barrier
 #endif
 #ifndef VQW_WG_DMA_PAT_MEM
 #define VQW_WG_DMA_PAT_MEM 1 // ... its issue pattern: LDS reads / requests per MFMA ...
@@ -125,14 +128,11 @@ __device__ __forceinline__ uint2 split4(const f32x4 v, float sc, uint2& lo) {
 constexpr int WG_QSTR = 576, WG_QPL = 16 * WG_QSTR;                       // bytes per time step / per plane of a stage's q image
 // PP: the same for p (the layer input planes the forward pass wrote, the gated planes): a tap's shift is then a row offset of
 // the planes -- no unaligned 16-byte windows, no ODD variant -- and the loop converts nothing at all.
-// QP && PP: nothing is converted, so nothing needs to pass through registers -- both operands go global -> LDS by LDS-DMA (x3_dma16)
-// into a ring of WG_DMA_NSTG 16-step stages, as in the conv main loop (f16x3_mainloop).  A DMA writes lane-linear 1-KiB pieces, which
-// rules the padded rows out: the image is the XOR-permuted one of f16x3_wgrad_layout.h (8 KiB per plane and stage, no padding).
+// QP && PP is a kernel of its own, wgrad_f16x3_dma_kernel below.
 template <bool QP, bool PP, bool BF> struct WgStage {
-    static constexpr bool DMA = QP && PP;
-    static constexpr int BOFF = DMA ? (BF ? 1 : 2) * wgl::PLANE : (PP ? (BF ? 1 : 2) * WG_QPL : 16 * 1024);      // q image behind the p image
-    static constexpr int BYTES = BOFF + (DMA ? (BF ? 1 : 2) * wgl::PLANE : (QP ? (BF ? 1 : 2) * WG_QPL : 16 * 1024));
-    static constexpr int STAGES = DMA ? WG_DMA_NSTG : NSTG;
+    static constexpr int BOFF = PP ? (BF ? 1 : 2) * WG_QPL : 16 * 1024;      // q image behind the p image
+    static constexpr int BYTES = BOFF + (QP ? (BF ? 1 : 2) * WG_QPL : 16 * 1024);
+    static constexpr int STAGES = NSTG;
 };
 __device__ __forceinline__ uint2 wg_tr_read(const char* p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -144,8 +144,60 @@ __device__ __forceinline__ uint2 wg_tr_read(const char* p) {
 #endif
 }
 
+// ---- what the register kernel and the LDS-DMA kernel share as functions.  Their prologue (work item -> tile, scales, plane bases),
+// flush_pair, the q_total add and the slab store stand in both kernel bodies: as functions of their own, or in another order, they
+// compile to other code (tools/isa_identity.py).
+// 12 MFMAs: row tiles i, i+1 (A fragments fa, both planes) x the wave's 2 column tiles (B fragments b), the three terms outermost
+// (small first) so that two MFMAs into the same accumulator are three independent ones apart
+template <bool BF>
+__device__ __forceinline__ void wg_mfma_rows(f32x16 (&acc)[8][2], const uint4 (&fa)[8][2], const uint4 (&b)[2][2], int i) {
+    if constexpr (BF) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            acc[i + (q >> 1)][q & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[i + (q >> 1)][0]), __builtin_bit_cast(bf16x8, b[q & 1][0]), acc[i + (q >> 1)][q & 1], 0, 0, 0);
+    } else {
+#pragma unroll
+        for (int term = 0; term < 3; ++term)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int ii = i + (q >> 1), j = q & 1;
+                const int pa = term == 1 ? 1 : 0, pb = term == 0 ? 1 : 0;
+                acc[ii][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[ii][pa]), __builtin_bit_cast(f16x8, b[j][pb]), acc[ii][j], 0, 0, 0);
+            }
+    }
+}
+
+// q sums from the B fragments (q as planes): lane (channel n of column tile j, k half) holds 8 consecutive time steps of its channel
+// per plane: their sum, over both planes, descaled -- the fp32 value to 2^-22 (the planes carry 22-23 significand bits)
+template <bool BF>
+__device__ __forceinline__ void wg_sum_frag(float (&qs_pair)[2], const uint4 (&b)[2][2], float inv_scq) {
+#ifdef VQW_ABL_WG_NOSUM
+    return;
+#endif
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        float acc_ = 0.0f;
+#pragma unroll
+        for (int pl = 0; pl < (BF ? 1 : 2); ++pl) {
+            const unsigned wds[4] = {b[j][pl].x, b[j][pl].y, b[j][pl].z, b[j][pl].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (BF) {
+                    acc_ += __uint_as_float(wds[e] << 16) + __uint_as_float(wds[e] & 0xffff0000u);
+                } else {
+                    acc_ += (float)__builtin_bit_cast(_Float16, (u16)(wds[e] & 0xffffu)) + (float)__builtin_bit_cast(_Float16, (u16)(wds[e] >> 16));
+                }
+            }
+        }
+        qs_pair[j] += acc_ * inv_scq;
+    }
+}
+
+// ---- the register kernel: an operand read as fp32 passes through registers (rgp / rgq), where it is converted; so does one read
+// as planes, which goes to the padded [time step][channel] image.  A ring of NSTG 16-step stages, one __syncthreads() per pair.
 template <bool ODD, bool BF, bool S2 = false, bool QP = false, bool PP = false>
 __global__ __launch_bounds__(256, 1) void wgrad_f16x3_kernel(const WgArgs a) {
+    static_assert(!(QP && PP), "both operands as planes: wgrad_f16x3_dma_kernel");
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     constexpr int STGB = WgStage<QP, PP, BF>::BYTES, BOFF = WgStage<QP, PP, BF>::BOFF, NPL = BF ? 1 : 2;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
@@ -192,7 +244,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_kernel(const WgArgs a) {
             // 128-byte line per chunk
             if (n < 4 * NPL) {
                 const int chunk = (n & 3) * 8 + (lane & 7), t = 8 * wv + (lane >> 3);
-                // (T need not be a multiple of the 32-step pairs when both operands are planes: steps behind the row's end read as zero)
+                // (steps behind the row's end read as zero; with one operand as fp32 T is a multiple of the 32-step pairs and there are none)
                 const int off = (pt0 + t < T) ? (int)(((size_t)chunk * NBq + (size_t)pb * T + pt0 + t) * 16) : (int)0x80000000;
                 rgq[n] = vqw_buf_load4((n >> 2) ? rqp1 : rqp0, off, 0);
             }
@@ -282,33 +334,9 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_kernel(const WgArgs a) {
         const f32x4 v = rgq[n];
         qs_pair[n >> 2] += (v[0] + v[1]) + (v[2] + v[3]);
     };
-    // QP: lane (channel n of column tile j, k half) holds 8 consecutive time steps of its channel per plane: their sum, over both
-    // planes, descaled -- the fp32 value to 2^-22 (the planes carry 22-23 significand bits)
     const float inv_scq = __builtin_amdgcn_rcpf(scq);
-    auto sum_frag = [&](const uint4 (&b)[2][2]) {
-#ifdef VQW_ABL_WG_NOSUM
-        return;
-#endif
-        if constexpr (QP) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                float acc_ = 0.0f;
-#pragma unroll
-                for (int pl = 0; pl < NPL; ++pl) {
-                    const unsigned wds[4] = {b[j][pl].x, b[j][pl].y, b[j][pl].z, b[j][pl].w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        if (BF) {
-                            acc_ += __uint_as_float(wds[e] << 16) + __uint_as_float(wds[e] & 0xffff0000u);
-                        } else {
-                            acc_ += (float)__builtin_bit_cast(_Float16, (u16)(wds[e] & 0xffffu)) + (float)__builtin_bit_cast(_Float16, (u16)(wds[e] >> 16));
-                        }
-                    }
-                }
-                qs_pair[j] += acc_ * inv_scq;
-            }
-        }
-    };
+    // (through a lambda, here and in the LDS-DMA kernel: called directly the helper compiles to other code)
+    auto sum_frag = [&](const uint4 (&b)[2][2]) { if constexpr (QP) wg_sum_frag<BF>(qs_pair, b, inv_scq); };
     auto flush_pair = [&](int s) {         // pair s is complete in qs_pair: add it to its condition frame, fold it into the totals
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -367,138 +395,9 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_kernel(const WgArgs a) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    // 12 MFMAs: row tiles i, i+1 x this wave's 2 column tiles, the three terms outermost (small first) so that two MFMAs
-    // into the same accumulator are three independent ones apart
-    auto mfma_rows = [&](int i, const uint4 (&b)[2][2]) {
-        if constexpr (BF) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                acc[i + (q >> 1)][q & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[i + (q >> 1)][0]), __builtin_bit_cast(bf16x8, b[q & 1][0]), acc[i + (q >> 1)][q & 1], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int term = 0; term < 3; ++term)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int ii = i + (q >> 1), j = q & 1;
-                    const int pa = term == 1 ? 1 : 0, pb = term == 0 ? 1 : 0;
-                    acc[ii][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[ii][pa]), __builtin_bit_cast(f16x8, b[j][pb]), acc[ii][j], 0, 0, 0);
-                }
-        }
-    };
 
     const int npairs = s_end - s_begin;
-    if constexpr (QP && PP) {
-        // ---- both operands as planes: LDS-DMA ring (no rgp / rgq, no ds_write, no commit).  One step = one 16-step stage, as in
-        // f16x3_mainloop: pair s of the K range is steps 2 (s - s_begin), 2 (s - s_begin) + 1, so the stages -- and with them the
-        // fragments and the order of the MFMAs -- are those of the register loop and dW is the same bit for bit.
-        constexpr int P = 4 * NPL;             // 1-KiB pieces a wave requests per stage: 2 operands x NPL planes x 8 pieces over 4 waves
-        const int wvu = __builtin_amdgcn_readfirstlane(wv);
-        // Piece w = wvu * P + k of a stage, in image order: operand (p, q), plane, time half, chunk group.  Two planes: wave 0 / 1 move
-        // p's plane 0 / 1, wave 2 / 3 q's; one plane (bf16): wave 0 / 1 move p's time half 0 / 1, wave 2 / 3 q's.  A wave therefore
-        // requests from ONE resource with ONE shift (q: none).
-        const bool w_is_p = wvu < 2;
-        const int w_plane = BF ? 0 : (wvu & 1), w_shift = w_is_p ? shift : 0;
-        const size_t pl1q = (QP && !BF) ? (size_t)pr.q_KC * NBq * 16 : 0, pl1p = (PP && !BF) ? (size_t)pr.p_KC * NBq * 16 : 0;
-        // (requests past the block's last stage, rows outside the batch row and steps behind T carry the offset 2^31, outside every
-        // resource -- qspan < 2^31 -- whatever the problem and the number of planes: they land as zeros)
-        const u32x4 rs = x3_rsrc_words((w_is_p ? ppb : qpb) + (w_plane ? (w_is_p ? pl1p : pl1q) : 0), qspan);
-        const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-        const unsigned wdst = lds0 + (unsigned)(wvu * P * wgl::PIECE);
-        // lane = 8 step + slot fetches chunk swz(step, slot) of the piece's chunk group at time step `step` of the piece's time half
-        const int dstep = lane >> 3;
-        const int lane_off = (int)((size_t)wgl::swz(dstep, lane & 7) * NBq * 16) + (dstep + w_shift) * 16;
-        const int cg_off = (int)(8 * NBq * 16);                    // one chunk group further
-        // the stage being requested: batch row (as a byte offset of its first row) and first time step, advanced by 16 steps at a time
-        const int row_steps = a.pairs_row * 32;
-        int rq_b = s_begin / a.pairs_row, rq_t = (s_begin - rq_b * a.pairs_row) * 32, rq_n = 0;
-        int rq_row = rq_b * T * 16;
-        const int nsteps = 2 * npairs;
-        auto request = [&](int k0, int k1) {       // pieces [k0, k1) of the wave's P of stage rq_n
-            const unsigned dst = wdst + (unsigned)((rq_n % WG_DMA_NSTG) * STGB);
-            const bool live = rq_n < nsteps;
-#pragma unroll
-            for (int k = k0; k < k1; ++k) {
-                const int th = BF ? (wvu & 1) : (k >> 2), cg = k & 3;
-                const int tt = rq_t + 8 * th + dstep + w_shift;
-                const int off = (live && tt >= 0 && tt < T) ? lane_off + rq_row + (rq_t + 8 * th) * 16 + cg * cg_off : (int)0x80000000;
-                x3_dma16(rs, dst + (unsigned)(k * wgl::PIECE), off);
-            }
-        };
-        auto advance = [&]() {
-            ++rq_n;
-            rq_t += 16;
-            const bool wrap = rq_t >= row_steps;
-            rq_t = wrap ? 0 : rq_t;
-            rq_row += wrap ? T * 16 : 0;
-        };
-        const int trl = wgl::tr_lane(lane);
-        auto read_a_dma = [&](int i, int stage) {
-            const char* st = smem + (stage % WG_DMA_NSTG) * STGB + wgl::piece_off(0, 0, i >> 1) + (trl ^ ((i & 1) * 64));
-#pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) {
-                const uint2 k0 = wg_tr_read(st + pl * wgl::PLANE), k1 = wg_tr_read(st + pl * wgl::PLANE + 4 * wgl::SLOTS * 16);
-                fa[i][pl] = make_uint4(k0.x, k0.y, k1.x, k1.y);
-            }
-        };
-        auto read_b_dma = [&](uint4 (&b)[2][2], int stage) {
-            const char* st = smem + (stage % WG_DMA_NSTG) * STGB + BOFF + wv * wgl::PIECE;
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int pl = 0; pl < NPL; ++pl) {
-                    const char* sj = st + (trl ^ (j * 64)) + pl * wgl::PLANE;
-                    const uint2 k0 = wg_tr_read(sj), k1 = wg_tr_read(sj + 4 * wgl::SLOTS * 16);
-                    b[j][pl] = make_uint4(k0.x, k0.y, k1.x, k1.y);
-                }
-        };
-        // The compiler does not count the requests (x3_dma16): every wait for them is written here.  Never __syncthreads() while one
-        // is in flight -- its fence would drain the ring.
-        auto wait_barrier = [&](auto n_c) {
-            constexpr int N = decltype(n_c)::value;
-            static_assert(N < 64, "vmcnt is a 6-bit counter");
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(N) : "memory");
-        };
-        if (npairs > 0) {
-            uint4 fbn[2][2];
-#pragma unroll
-            for (int s = 0; s < WG_DMA_NSTG; ++s) { request(0, P); advance(); }
-            wait_barrier(std::integral_constant<int, (WG_DMA_NSTG - 1) * P>{});
-#pragma unroll
-            for (int i = 0; i < 8; ++i) read_a_dma(i, 0);
-            read_b_dma(fb, 0);
-            // Step s (one barrier): the wait retires this wave's pieces of stage s + 1 (DEPTH newer stages stay in flight) and its
-            // fragment reads of stage s; behind the barrier stage s + 1 is complete and slot s % NSTG is free, so stage s + NSTG is
-            // requested into it, in four even parts behind the fragment reads of stage s + 1, all in the shadow of stage s's MFMAs.
-            // No conditionals in the body; the last step re-reads its own stage (never used).
-            auto step = [&](const uint4 (&bc)[2][2], uint4 (&bn)[2][2], int s) {
-                wait_barrier(std::integral_constant<int, WG_DMA_DEPTH * P>{});
-                const int sn = s + 1 < nsteps ? s + 1 : s;
-                sum_frag(bc);
-                read_b_dma(bn, sn);
-#pragma unroll
-                for (int i = 0; i < 8; i += 2) {
-                    mfma_rows(i, bc);
-                    read_a_dma(i, sn);
-                    read_a_dma(i + 1, sn);
-                    request(P * (i / 2) / 4, P * (i / 2 + 1) / 4);
-                }
-                advance();
-#pragma unroll
-                for (int k_ = 0; k_ < (BF ? 2 : 6) * 8; ++k_) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100 | 0x200 | 0x020, BF ? 2 : VQW_WG_DMA_PAT_MEM, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002 | 0x004, VQW_WG_DMA_PAT_ALU, 0);
-                }
-            };
-            for (int s = 0; s < nsteps; s += 2) {
-                step(fb, fbn, s);
-                step(fbn, fb, s + 1);
-                if (do_sum) flush_pair(s_begin + (s >> 1));     // both stages of the pair are in qs_pair
-            }
-            // the requests past the last stage: nothing of the loop may be in flight when the slab stores start
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    } else if (npairs > 0) {
+    if (npairs > 0) {
         set_pair(s_begin);
         set_commit_pair(s_begin);
 #pragma unroll
@@ -526,7 +425,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_kernel(const WgArgs a) {
             set_commit_pair(s_begin + it + 1);
 #pragma unroll
             for (int i = 0; i < 8; i += 2) {
-                mfma_rows(i, fb);
+                wg_mfma_rows<BF>(acc, fa, fb, i);
                 read_a(i, 2 * it + 1);
                 read_a(i + 1, 2 * it + 1);
                 commit_one(i, it + 1);
@@ -546,7 +445,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_kernel(const WgArgs a) {
             if (QP && do_sum) flush_pair(s_begin + it);     // both stages of pair `it` have been read
 #pragma unroll
             for (int i = 0; i < 8; i += 2) {
-                mfma_rows(i, fb);
+                wg_mfma_rows<BF>(acc, fa, fb, i);
                 issue_one(i);
                 issue_one(i + 1);
 #pragma unroll
@@ -571,6 +470,195 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_kernel(const WgArgs a) {
         }
     }
     // ---- partial tile -> slab [tile][split][256][256], rows c, columns o (32 lanes = 128 contiguous bytes)
+    const float inv = __builtin_amdgcn_rcpf(scp * scq);
+    float* out = a.slab + ((size_t)it.gtile * a.nsplit + split) * 65536;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int v4 = 0; v4 < 4; ++v4)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    out[(32 * i + 8 * v4 + 4 * lhi + e) * 256 + 64 * wv + 32 * j + l31] = acc[i][j][v4 * 4 + e] * inv;
+}
+
+// ---- the LDS-DMA kernel: both operands as planes.  Nothing is converted, so nothing needs to pass through registers -- both operands
+// go global -> LDS by LDS-DMA (x3_dma16) into a ring of WG_DMA_NSTG 16-step stages, as in the conv main loop (f16x3_mainloop): no
+// rgp / rgq, no ds_write, no commit.  A DMA writes lane-linear 1-KiB pieces, which rules the padded rows out: the image is the
+// XOR-permuted one of f16x3_wgrad_layout.h (8 KiB per plane and stage, no padding).  A tap's shift is a row offset of p's planes.
+template <bool BF> struct WgDmaStage {
+    static constexpr int BOFF = (BF ? 1 : 2) * wgl::PLANE, BYTES = 2 * BOFF, STAGES = WG_DMA_NSTG;      // q image behind the p image
+};
+template <bool BF>
+__global__ __launch_bounds__(256, 1) void wgrad_f16x3_dma_kernel(const WgArgs a) {
+    extern __shared__ __attribute__((aligned(1024))) char smem[];
+    constexpr int STGB = WgDmaStage<BF>::BYTES, BOFF = WgDmaStage<BF>::BOFF, NPL = BF ? 1 : 2;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
+    // (the register kernel's prologue without its fp32 sources and per-plane resources; statement by statement in its order -- the
+    // second planes' offsets where it forms them -- or the kernel compiles to other code)
+    const WgItem it = wg_decode(vqw_xcd_remap(blockIdx.x, gridDim.x), a);
+    const WgProblem& pr = a.pr[it.prob];
+    const int split = it.split, tap = it.tap, c0 = it.rtl * 256;
+    const int shift = pr.shift[tap];
+    const int o0 = it.nt * 256;
+    const bool from_q1 = o0 >= a.Q0;
+    const float scp = dev_scale(pr.sp) * pr.p_hscale, scq = dev_scale(from_q1 ? pr.sq1 : pr.sq0) * pr.q_hscale;
+    const int T = a.T;
+    const int s_begin = (int)((long)split * a.pairs_total / a.nsplit), s_end = (int)((long)(split + 1) * a.pairs_total / a.nsplit);
+    // one resource per wave (below), based at this block's first chunk of its operand and plane (32 chunks = its 256 rows)
+    const size_t NBq = (size_t)a.B * T;
+    const char* qpb = reinterpret_cast<const char*>(pr.qp) + ((size_t)pr.q_kc0 + o0 / 8) * NBq * 16;
+    const unsigned qspan = (unsigned)(32 * NBq * 16 < 0x7fffffffull ? 32 * NBq * 16 : 0x7fffffffull);
+    const size_t pl1q = !BF ? (size_t)pr.q_KC * NBq * 16 : 0;
+    const char* ppb = reinterpret_cast<const char*>(pr.pp) + ((size_t)pr.p_kc0 + pr.pkoff[tap] + c0 / 8) * NBq * 16;
+    const size_t pl1p = !BF ? (size_t)pr.p_KC * NBq * 16 : 0;
+    float* const q_total = pr.q_total;
+    float* const q_seg = pr.q_seg;
+    // q sums, from the B fragments: lane (channel l31, k half lhi) of the thread's two column tiles
+    const bool do_sum = it.rtl == 0 && tap == 0 && (q_seg != nullptr || (q_total != nullptr && o0 < a.total_o1 && o0 + 256 > a.total_o0));
+    float qs_pair[2] = {0.f, 0.f}, qs_tot[2] = {0.f, 0.f};
+    const float inv_scq = __builtin_amdgcn_rcpf(scq);
+    auto sum_frag = [&](const uint4 (&b)[2][2]) { wg_sum_frag<BF>(qs_pair, b, inv_scq); };
+    auto flush_pair = [&](int s) {         // pair s is complete in qs_pair: add it to its condition frame, fold it into the totals
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float both = qs_pair[h] + __shfl_xor(qs_pair[h], 32, 64);      // the partner lane holds the other k half
+            qs_tot[h] += qs_pair[h];
+            qs_pair[h] = 0.f;
+            if (q_seg && lhi == 0) {
+                const int b = s / a.pairs_row, t0 = (s - b * a.pairs_row) * 32;
+                const int row = o0 + (wv * 2 + h) * 32 + l31;
+                unsafeAtomicAdd(q_seg + (size_t)b * a.seg_bstride + (size_t)row * a.seg_T + t0 / a.seg_ratio, both);
+            }
+        }
+    };
+    uint4 fa[8][2], fb[2][2];                        // A fragments (both planes) of 8 row tiles, B fragments of this wave's 2 column tiles
+    f32x16 acc[8][2];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    const int npairs = s_end - s_begin;
+    // One step = one 16-step stage: pair s of the K range is steps 2 (s - s_begin), 2 (s - s_begin) + 1, so the stages -- and with
+    // them the fragments and the order of the MFMAs -- are those of the register kernel and dW is the same bit for bit.
+    constexpr int P = 4 * NPL;             // 1-KiB pieces a wave requests per stage: 2 operands x NPL planes x 8 pieces over 4 waves
+    const int wvu = __builtin_amdgcn_readfirstlane(wv);
+    // Piece w = wvu * P + k of a stage, in image order: operand (p, q), plane, time half, chunk group.  Two planes: wave 0 / 1 move
+    // p's plane 0 / 1, wave 2 / 3 q's; one plane (bf16): wave 0 / 1 move p's time half 0 / 1, wave 2 / 3 q's.  A wave therefore
+    // requests from ONE resource with ONE shift (q: none).
+    const bool w_is_p = wvu < 2;
+    const int w_plane = BF ? 0 : (wvu & 1), w_shift = w_is_p ? shift : 0;
+    // (requests past the block's last stage, rows outside the batch row and steps behind T carry the offset 2^31, outside every
+    // resource -- qspan < 2^31 -- whatever the problem and the number of planes: they land as zeros)
+    const u32x4 rs = x3_rsrc_words((w_is_p ? ppb : qpb) + (w_plane ? (w_is_p ? pl1p : pl1q) : 0), qspan);
+    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+    const unsigned wdst = lds0 + (unsigned)(wvu * P * wgl::PIECE);
+    // lane = 8 step + slot fetches chunk swz(step, slot) of the piece's chunk group at time step `step` of the piece's time half
+    const int dstep = lane >> 3;
+    const int lane_off = (int)((size_t)wgl::swz(dstep, lane & 7) * NBq * 16) + (dstep + w_shift) * 16;
+    const int cg_off = (int)(8 * NBq * 16);                    // one chunk group further
+    // the stage being requested: batch row (as a byte offset of its first row) and first time step, advanced by 16 steps at a time
+    const int row_steps = a.pairs_row * 32;
+    int rq_b = s_begin / a.pairs_row, rq_t = (s_begin - rq_b * a.pairs_row) * 32, rq_n = 0;
+    int rq_row = rq_b * T * 16;
+    const int nsteps = 2 * npairs;
+    auto request = [&](int k0, int k1) {       // pieces [k0, k1) of the wave's P of stage rq_n
+        const unsigned dst = wdst + (unsigned)((rq_n % WG_DMA_NSTG) * STGB);
+        const bool live = rq_n < nsteps;
+#pragma unroll
+        for (int k = k0; k < k1; ++k) {
+            const int th = BF ? (wvu & 1) : (k >> 2), cg = k & 3;
+            const int tt = rq_t + 8 * th + dstep + w_shift;
+            const int off = (live && tt >= 0 && tt < T) ? lane_off + rq_row + (rq_t + 8 * th) * 16 + cg * cg_off : (int)0x80000000;
+            x3_dma16(rs, dst + (unsigned)(k * wgl::PIECE), off);
+        }
+    };
+    auto advance = [&]() {
+        ++rq_n;
+        rq_t += 16;
+        const bool wrap = rq_t >= row_steps;
+        rq_t = wrap ? 0 : rq_t;
+        rq_row += wrap ? T * 16 : 0;
+    };
+    const int trl = wgl::tr_lane(lane);
+    auto read_a = [&](int i, int stage) {
+        const char* st = smem + (stage % WG_DMA_NSTG) * STGB + wgl::piece_off(0, 0, i >> 1) + (trl ^ ((i & 1) * 64));
+#pragma unroll
+        for (int pl = 0; pl < NPL; ++pl) {
+            const uint2 k0 = wg_tr_read(st + pl * wgl::PLANE), k1 = wg_tr_read(st + pl * wgl::PLANE + 4 * wgl::SLOTS * 16);
+            fa[i][pl] = make_uint4(k0.x, k0.y, k1.x, k1.y);
+        }
+    };
+    auto read_b = [&](uint4 (&b)[2][2], int stage) {
+        const char* st = smem + (stage % WG_DMA_NSTG) * STGB + BOFF + wv * wgl::PIECE;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int pl = 0; pl < NPL; ++pl) {
+                const char* sj = st + (trl ^ (j * 64)) + pl * wgl::PLANE;
+                const uint2 k0 = wg_tr_read(sj), k1 = wg_tr_read(sj + 4 * wgl::SLOTS * 16);
+                b[j][pl] = make_uint4(k0.x, k0.y, k1.x, k1.y);
+            }
+    };
+    // The compiler does not count the requests (x3_dma16): every wait for them is written here.  Never __syncthreads() while one
+    // is in flight -- its fence would drain the ring.
+    auto wait_barrier = [&](auto n_c) {
+        constexpr int N = decltype(n_c)::value;
+        static_assert(N < 64, "vmcnt is a 6-bit counter");
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(N) : "memory");
+    };
+    if (npairs > 0) {
+        uint4 fbn[2][2];
+#pragma unroll
+        for (int s = 0; s < WG_DMA_NSTG; ++s) { request(0, P); advance(); }
+        wait_barrier(std::integral_constant<int, (WG_DMA_NSTG - 1) * P>{});
+#pragma unroll
+        for (int i = 0; i < 8; ++i) read_a(i, 0);
+        read_b(fb, 0);
+        // Step s (one barrier): the wait retires this wave's pieces of stage s + 1 (DEPTH newer stages stay in flight) and its
+        // fragment reads of stage s; behind the barrier stage s + 1 is complete and slot s % NSTG is free, so stage s + NSTG is
+        // requested into it, in four even parts behind the fragment reads of stage s + 1, all in the shadow of stage s's MFMAs.
+        // No conditionals in the body; the last step re-reads its own stage (never used).
+        auto step = [&](const uint4 (&bc)[2][2], uint4 (&bn)[2][2], int s) {
+            wait_barrier(std::integral_constant<int, WG_DMA_DEPTH * P>{});
+            const int sn = s + 1 < nsteps ? s + 1 : s;
+            sum_frag(bc);
+            read_b(bn, sn);
+#pragma unroll
+            for (int i = 0; i < 8; i += 2) {
+                wg_mfma_rows<BF>(acc, fa, bc, i);
+                read_a(i, sn);
+                read_a(i + 1, sn);
+                request(P * (i / 2) / 4, P * (i / 2 + 1) / 4);
+            }
+            advance();
+#pragma unroll
+            for (int k_ = 0; k_ < (BF ? 2 : 6) * 8; ++k_) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100 | 0x200 | 0x020, BF ? 2 : VQW_WG_DMA_PAT_MEM, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002 | 0x004, VQW_WG_DMA_PAT_ALU, 0);
+            }
+        };
+        for (int s = 0; s < nsteps; s += 2) {
+            step(fb, fbn, s);
+            step(fbn, fb, s + 1);
+            if (do_sum) flush_pair(s_begin + (s >> 1));     // both stages of the pair are in qs_pair
+        }
+        // the requests past the last stage: nothing of the loop may be in flight when the slab stores start
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    if (do_sum && q_total) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float both = qs_tot[h] + __shfl_xor(qs_tot[h], 32, 64);
+            const int row = o0 + (wv * 2 + h) * 32 + l31;
+            if (lhi == 0 && row >= a.total_o0 && row < a.total_o1) unsafeAtomicAdd(q_total + row, both);
+        }
+    }
+    // ---- partial tile -> slab, as in wgrad_f16x3_kernel
     const float inv = __builtin_amdgcn_rcpf(scp * scq);
     float* out = a.slab + ((size_t)it.gtile * a.nsplit + split) * 65536;
 #pragma unroll
@@ -613,6 +701,23 @@ __global__ void wgrad_reduce_kernel(const WgArgs a) {
     float* d = a.pr[prob].dw + (size_t)tap * a.dw_tap_stride + (size_t)(rtl * 256 + r) * a.lddw + nt * 256 + col;
     f32x4 old = *reinterpret_cast<const f32x4*>(d);
     *reinterpret_cast<f32x4*>(d) = old + sum;
+}
+
+// (odd, bf, s2, qp, pp) -> the kernel and its dynamic LDS: the 13 instantiations
+struct WgKernel { void (*fn)(WgArgs); int lds; };
+template <bool ODD, bool BF, bool S2, bool QP, bool PP> WgKernel wg_reg() {
+    return {wgrad_f16x3_kernel<ODD, BF, S2, QP, PP>, WgStage<QP, PP, BF>::BYTES * WgStage<QP, PP, BF>::STAGES};
+}
+template <bool BF> WgKernel wg_dma() { return {wgrad_f16x3_dma_kernel<BF>, WgDmaStage<BF>::BYTES * WgDmaStage<BF>::STAGES}; }
+WgKernel wg_kernel(bool odd, bool bf, bool s2, bool qp, bool pp) {
+    if (s2) return wg_reg<false, false, true, false, false>();
+    if (pp && qp) return bf ? wg_dma<true>() : wg_dma<false>();
+    // (p as planes: a tap's shift is a row offset -- the unaligned-window variant is not needed)
+    if (pp) return bf ? wg_reg<false, true, false, false, true>() : wg_reg<false, false, false, false, true>();
+    if (qp) return odd ? (bf ? wg_reg<true, true, false, true, false>() : wg_reg<true, false, false, true, false>())
+                       : (bf ? wg_reg<false, true, false, true, false>() : wg_reg<false, false, false, true, false>());
+    return odd ? (bf ? wg_reg<true, true, false, false, false>() : wg_reg<true, false, false, false, false>())
+               : (bf ? wg_reg<false, true, false, false, false>() : wg_reg<false, false, false, false, false>());
 }
 
 }  // namespace
@@ -699,24 +804,13 @@ int vqw_f16x3_wgrad_batch(const vqw_f16x3_wgrad_desc* dp, int nprob, vqw_stream_
     a.lddw = lddw;
     a.dw_tap_stride = d.dw_tap_stride > 0 ? (long)d.dw_tap_stride : (long)d.Cp * lddw;
     VQW_CHECK((size_t)tiles * nsplit * 65536 <= (size_t)d.slab_floats, "vqw_f16x3_wgrad: slab too small (%d tiles x %d splits x 65536 floats)", tiles, nsplit);
-    typedef void (*kfn_t)(WgArgs);
-    const kfn_t ktab[4] = {wgrad_f16x3_kernel<false, false>, wgrad_f16x3_kernel<true, false>, wgrad_f16x3_kernel<false, true>,
-                           wgrad_f16x3_kernel<true, true>};
-    const kfn_t kqp[4] = {wgrad_f16x3_kernel<false, false, false, true>, wgrad_f16x3_kernel<true, false, false, true>,
-                          wgrad_f16x3_kernel<false, true, false, true>, wgrad_f16x3_kernel<true, true, false, true>};
     const bool qp = d.q_planes != nullptr, pp = d.p_planes != nullptr, bf = (d.mode & 1) != 0;
     VQW_CHECK(!qp || (!s2 && d.Q1 == 0 && (size_t)32 * d.B * d.T * 16 < ((size_t)1 << 31)),
               "vqw_f16x3_wgrad: q as planes needs p_stride 1, Q1 = 0 and B * T < 4 M");
     VQW_CHECK(!pp || (!s2 && !d.p_relu && (size_t)32 * d.B * d.T * 16 < ((size_t)1 << 31)),
               "vqw_f16x3_wgrad: p as planes needs p_stride 1, no p_relu and B * T < 4 M");
-    // (p as planes: a tap's shift is a row offset -- the unaligned-window variant is not needed)
-    const kfn_t kpp[4] = {wgrad_f16x3_kernel<false, false, false, false, true>, wgrad_f16x3_kernel<false, true, false, false, true>,
-                          wgrad_f16x3_kernel<false, false, false, true, true>, wgrad_f16x3_kernel<false, true, false, true, true>};
-    const kfn_t kfn = s2 ? wgrad_f16x3_kernel<false, false, true>
-                         : (pp ? kpp[(bf ? 1 : 0) + (qp ? 2 : 0)] : (qp ? kqp : ktab)[(odd ? 1 : 0) + 2 * (bf ? 1 : 0)]);
-    const int npl = bf ? 1 : 2;
-    const int lds = (pp && qp) ? WG_DMA_NSTG * 2 * npl * wgl::PLANE : NSTG * ((pp ? npl * WG_QPL : 16 * 1024) + (qp ? npl * WG_QPL : 16 * 1024));
-    if (const int rc = x3_launch(kfn, tiles * nsplit, lds, st, a, "vqw_f16x3_wgrad")) return rc;
+    const WgKernel k = wg_kernel(odd, bf, s2, qp, pp);
+    if (const int rc = x3_launch(k.fn, tiles * nsplit, k.lds, st, a, "vqw_f16x3_wgrad")) return rc;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(65536 / 4 / 256, tiles), dim3(256), 0, st, a);
     VQW_LAUNCH_CHECK("vqw_f16x3_wgrad");
     return 0;
