@@ -554,7 +554,11 @@ int vqw_prior_input_wgrad(const int32_t* order, const int32_t* starts, const flo
  * that are fp32-accurate on the fp16 matrix pipe.  Every operand is split into two fp16 planes (x = h1 + h2), products
  * h1 h1 + h1 h2 + h2 h1 in fp32 accumulators.  The gate conv (wavenet_ops.py:104-114, conv1d_v2 k taps + add_condition
  * + tanh*sigmoid), the 1x1 skip / residual convs, gate backward, the input gradient and the weight gradients.
- * Plane layout: [plane 0..1][channel chunk of 8][row][8 fp16] (16-byte entries); 2 * rows * channels bytes each.    */
+ * Plane layout: [plane 0..1][channel chunk of 8][row][8 fp16] (16-byte entries); 2 * rows * channels bytes each.
+ * The planes of scale * x are h1 = fp16(scale * x) and h2 = fp16(scale * x - h1), both rounded to nearest even.  A second
+ * plane that is zero may carry either sign: vqw_f16x3_split_activations and the weight packers write +0, the conv epilogues
+ * that write planes leave -0 for an element that is itself -0.0.  It is the same operand of every product; compare such
+ * an entry by value, not by its bits.                                                                                */
 
 /* `mode` (every vqw_f16x3_* entry point / descriptor) is a bit set:
  *   VQW_X3_BF16        the bf16 engine of BASELINE.json configs[4] -- bf16 storage + fp32 accumulate: ONE bf16 plane per
@@ -618,7 +622,13 @@ typedef struct vqw_f16x3_gate_desc {
     const float* w_scale;  /* are multiplied by w_scale_inv / (x_scale * w_scale)                                    */
     int32_t mode;          /* VQW_X3_* bits (see below)                                                              */
 } vqw_f16x3_gate_desc;
-/* T % 256 == 0, R % 128 == 0, (T / cond_T) % 32 == 0; tap j reads x[t - (ks-1-j)*dilation], zero before t = 0 */
+/* T % 256 == 0, R % 128 == 0, (T / cond_T) % 32 == 0; tap j reads x[t - (ks-1-j)*dilation], zero before t = 0 of each
+ * batch row.  1 <= ks <= 8, dilation >= 1 (it may exceed T: such a tap reads zero); w_scale_inv > 0; mode within
+ * VQW_X3_BF16 | VQW_X3_HALF_BLOCKS; with out_planes_KC > 0, out_planes_kc0 + R/8 <= out_planes_KC; out0 may be NULL only
+ * with out_planes and save1.  A descriptor that breaks one of these is refused before anything is launched: the call
+ * returns non-zero, vqw_last_error names the rule, and no output is touched.
+ * cond is read at cond[b * cond_bstride + m * cond_T + t / (T / cond_T)]; cond_bstride may be wider than the 2R * cond_T
+ * floats read per batch row (the caller keeps it from being narrower: it is not checked).                              */
 int vqw_f16x3_gate_conv(const vqw_f16x3_gate_desc* d, vqw_stream_t s);
 
 /* w [K][ldw] fp32 (row k, column m), times `scale` -> planes [2][K/8][M][8]; K % 8 == 0; `count` matrices back to back
@@ -682,6 +692,15 @@ typedef struct vqw_f16x3_out_desc {
                             * layer's R / 8 chunks from aux0_kc0; scale 1): vqw_f16x3_gate_conv then needs no fp32 out0 at all             */
     int32_t aux0_KC, aux0_kc0;
 } vqw_f16x3_out_desc;
+/* Refused before anything is launched (the call returns non-zero, vqw_last_error names the rule, no output is touched):
+ *   T % 256 != 0; R or S negative or no multiple of 256, or both 0; more than 8 taps;
+ *   Cin (0 = R) below 64 or no multiple of 32 -- any other multiple of 32 from 64 on is a legal contraction, whatever the depth
+ *   of the main loop's ring; xp_kc0 + Cin/8 > xp_KC; xp_kc0 > 0 with more than one tap (the taps of a conv read the planes of
+ *   ONE tensor, chunk 0 first); one plane of the contraction of 2 GiB or more;
+ *   w_scale_inv <= 0; mode outside VQW_X3_BF16 | VQW_X3_HALF_BLOCKS;
+ *   epi 1 and epi 2 with S > 0, R = 0 or Cin = 0 (they state their Cin); epi 1 without aux0 and aux1, or, with flags bit 2,
+ *   aux0_kc0 + R/8 > aux0_KC; epi 2 without net_out, with more than one tap (it is a 1x1 kernel), or with cond and
+ *   (T / cond_T) % 32 != 0 or cond_bstride < R * cond_T.                                                               */
 int vqw_f16x3_out_conv(const vqw_f16x3_out_desc* d, vqw_stream_t s);
 
 /* The encoder's stride-2 convs on the fp16x3 engine (encoder.py:17-18: tf.layers.conv1d(768, 5, strides 2, 'same') -> relu ->

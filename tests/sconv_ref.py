@@ -70,40 +70,12 @@ def unsplit(x32):
     return x, np.zeros_like(x)
 
 
-def _planes(a, s, split):
-    h1, h2 = split(X.scaled(a, s))
-    return np.asarray(h1, np.float64), np.asarray(h2, np.float64)
+# the planes of an operand, the three products and a read with zero outside the batch row: shared with tests/x3_conv_ref.py
+_planes, _three, _gather = X.planes_of, X.three_terms, X.gather
 
 
 def _inv(sa, sb):
     return 1.0 / (float(F32(sa)) * float(F32(sb)))
-
-
-def _mm(w, a):
-    """w [K][M], a [B][K][N] -> [B][M][N]."""
-    return np.matmul(w.T[None], a)
-
-
-def _three(a1, a2, w1, w2, no_h2h1=False):
-    """(sum, sum of absolute values) of a1 w1 + a1 w2 + a2 w1 over K: a [B][K][N], w [K][M]."""
-    val, ab = _mm(w1 + w2, a1), _mm(np.abs(w1) + np.abs(w2), np.abs(a1))
-    if not no_h2h1:
-        val, ab = val + _mm(w1, a2), ab + _mm(np.abs(w1), np.abs(a2))
-    return val, ab
-
-
-def _gather(x, idx, leak=False):
-    """x [B][C][L] read at idx [N] of every batch row -> [B][C][N]; outside [0, L) zero.  leak: the batch rows are one flat
-    (batch, time) axis and only its two ends read zero -- the neighbouring batch row is read instead."""
-    B, C, L = x.shape
-    idx = np.asarray(idx)
-    if not leak:
-        ok = (idx >= 0) & (idx < L)
-        return x[:, :, np.clip(idx, 0, L - 1)] * ok
-    flat = x.transpose(1, 0, 2).reshape(C, B * L)
-    f = (np.arange(B) * L)[:, None] + idx[None, :]
-    ok = (f >= 0) & (f < B * L)
-    return (flat[:, np.clip(f, 0, B * L - 1)] * ok).transpose(1, 0, 2)
 
 
 # ---------------------------------------------------------------------------------------------------- forward

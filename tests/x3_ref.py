@@ -129,6 +129,36 @@ def contract(a, b, sa=1.0, sb=1.0, flush=False):
     return (a1 @ b1 + a1 @ b2 + a2 @ b1) / (float(np.float32(sa)) * float(np.float32(sb)))
 
 
+def planes_of(a, s, split_=split):
+    """The two planes of s * a as float64 (split_: what stands in for split, e.g. an evaluation without the split)."""
+    h1, h2 = split_(scaled(a, s))
+    return np.asarray(h1, np.float64), np.asarray(h2, np.float64)
+
+
+def three_terms(a1, a2, w1, w2, no_h2h1=False):
+    """(sum, sum of absolute values) of a1 w1 + a1 w2 + a2 w1 over K: a [B][K][N], w [K][M] -> [B][M][N].
+    no_h2h1: the a2 w1 term is left out (a deliberately wrong evaluation)."""
+    mm = lambda w, a: np.matmul(w.T[None], a)  # noqa: E731
+    val, ab = mm(w1 + w2, a1), mm(np.abs(w1) + np.abs(w2), np.abs(a1))
+    if not no_h2h1:
+        val, ab = val + mm(w1, a2), ab + mm(np.abs(w1), np.abs(a2))
+    return val, ab
+
+
+def gather(x, idx, leak=False):
+    """x [B][C][L] read at idx [N] of every batch row -> [B][C][N]; outside [0, L) zero.  leak: the batch rows are one flat
+    (batch, time) axis and only its two ends read zero -- the neighbouring batch row is read instead."""
+    B, C, L = x.shape
+    idx = np.asarray(idx)
+    if not leak:
+        ok = (idx >= 0) & (idx < L)
+        return x[:, :, np.clip(idx, 0, L - 1)] * ok
+    flat = x.transpose(1, 0, 2).reshape(C, B * L)
+    f = (np.arange(B) * L)[:, None] + idx[None, :]
+    ok = (f >= 0) & (f < B * L)
+    return (flat[:, np.clip(f, 0, B * L - 1)] * ok).transpose(1, 0, 2)
+
+
 def contract_bf16(a, b, sa=1.0, sb=1.0):
     """The bf16 engine's product of a [M][K] and b [K][N] (fp32): both operands scaled as in the fp16 path, each rounded to its
     ONE bf16 plane, multiplied in float64 (a bf16 x bf16 product is exact in fp32, so only the summation is left to the device),
