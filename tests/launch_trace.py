@@ -45,7 +45,8 @@ PRIOR = dict(WAVENET, quantization_channels=512, speaker_embedding=64, learning_
 # model._x3_active; grad_sync: with the recording stub; kind: 'prior' = prior.LatentPrior over int32 codes instead of a VQVAE;
 # run: what is recorded instead of forward() + backward() -- '_encode': _encode(save=False) on a train=False workspace,
 # 'train_step': one immediate train_step, 'score': _score_pass on the score workspace, 'states': decoder_states of a 700-step
-# prompt, 'encode': encode() of one utterance for three speakers
+# prompt, 'encode': encode() of one utterance for three speakers, 'deferred': defer_guard set (void: the sticky void flag preset, so
+# both steps are voided, the older is repeated on the fp32 engine and the second runs again), two train_steps, finish_steps()
 CASES = {
     'enc64': dict(),
     'magenta': dict(model={'encoder': 'Magenta'}),
@@ -90,6 +91,9 @@ DIGEST_ONLY = {
     'score': dict(run='score'),
     'states': dict(run='states'),
     'encode': dict(run='encode'),
+    # the deferred range flag: two steps and their resolution; with the void flag preset, the whole replay path
+    'train-step-deferred': dict(run='deferred'),
+    'train-step-deferred-flagged': dict(run='deferred', void=True),
 }
 CASES.update(DIGEST_ONLY)
 LAYOUTS = {'%s-vq%d-spk%d' % (enc, vq, spk): {'encoder': enc, 'use_vq': bool(vq), 'speaker_embedding': spk}
@@ -203,6 +207,7 @@ def install(monkeypatch, pkg):
     monkeypatch.setattr(torch.cuda, 'Event', lambda *a, **kw: FakeEvent(rec))
     monkeypatch.setattr(torch.cuda, 'stream', on_stream)
     monkeypatch.setattr(torch.cuda, 'get_device_properties', lambda *a, **kw: types.SimpleNamespace(multi_processor_count=256))
+    monkeypatch.setattr(torch.Tensor, 'pin_memory', lambda self, *a, **kw: self)      # (the deferred step's host copy of the void flag)
     return rec
 
 
@@ -243,6 +248,13 @@ def run_case(monkeypatch, pkg, name):
         model.decoder_states(x, torch.zeros(B, model.Cc, T // 64), 700, lambda l, net_l, s0: None)
     elif run == 'encode':
         model.encode(x, torch.zeros(3, dtype=torch.int64))
+    elif run == 'deferred':
+        model.defer_guard = True
+        if case.get('void'):
+            model.x3_void.fill_(1)
+        model.train_step(x, spk)
+        model.train_step(x, spk)
+        model.finish_steps()
     else:
         model.backward(x, spk, model.forward(x, spk))
     return rec.trace

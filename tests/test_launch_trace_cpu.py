@@ -30,7 +30,7 @@ def test_launches_are_the_golden_ones(pkg, name):
     assert LT.digest(trace) == want['sha256'], 'same calls, other arguments / buffers / streams: python tests/launch_trace.py --dump %s' % name
 
 
-@pytest.mark.parametrize('name', ['enc64', 'magenta', '2019', 'enc64-grad-sync'])
+@pytest.mark.parametrize('name', ['enc64', 'magenta', '2019', 'enc64-grad-sync', 'train-step-deferred', 'train-step-deferred-flagged'])
 def test_a_second_run_gives_the_same_trace(pkg, name):
     digests = []
     for _ in range(2):
@@ -76,6 +76,10 @@ def test_the_cases_reach_the_branches_they_are_named_for(pkg):
     jitter = names(traced('train-step-jitter-ema'))
     assert {'time_jitter_fwd', 'time_jitter_bwd', 'vq_cluster_stats', 'vq_codebook_ema_step'} <= set(jitter)
     assert not {'time_jitter_fwd', 'vq_cluster_stats', 'vq_codebook_ema_step'} & set(names(traced('train-step')))
+    # the deferred range flag: a voided step is repeated on the fp32 engine (the stack's wgrad_gemm; the encoder's short layers
+    # use that kernel on either engine), once: the second step runs again on the plane engine; a clean one is not
+    flagged = traced('train-step-deferred-flagged')
+    assert len(in_stack(flagged)) == 1 and not in_stack(traced('train-step-deferred'))
     # a refused length: the only plane-engine calls are the encoder's (its kernels alone, and none once its engine layers are off)
     refused = {e[0] for e in traced('dec-refused-length') if e[0].startswith('f16x3_')}
     assert 'f16x3_strided_conv' in refused and not refused & {'f16x3_gate_conv', 'f16x3_out_conv', 'f16x3_pack_gate_weights', 'f16x3_wgrad_batch'}

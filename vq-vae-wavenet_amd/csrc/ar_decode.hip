@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ar_persist.h"
+#include "mu_law.h"
 #include "vqw_common.h"
 
 namespace {
@@ -55,17 +56,6 @@ struct GemvArgs {
     const ArState* st;
 };
 
-__device__ __forceinline__ float mu_enc(float x) {
-    x = fminf(fmaxf(x, -1.0f), 1.0f);
-    const float s = (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f);
-    return s * log1pf(255.0f * fabsf(x)) / 5.5451774444795623f;
-}
-__device__ __forceinline__ float mu_dec(float idx) {
-    const float y = 2.0f * idx / 255.0f - 1.0f;
-    const float s = (y > 0.0f) ? 1.0f : ((y < 0.0f) ? -1.0f : 0.0f);
-    return s * (powf(256.0f, fabsf(y)) - 1.0f) / 255.0f;
-}
-
 // wavenet.py:113-124: x = mu_law_encode(input_t); fast_conv1d(k=pre_k, dilation 1, Cin=1).
 __global__ void ar_pre_kernel(const ArState* st, const float* prev, float* xring, const float* pre_w,
                               const float* pre_b, float* cur, int pre_k, int R) {
@@ -73,7 +63,7 @@ __global__ void ar_pre_kernel(const ArState* st, const float* prev, float* xring
     const int b = blockIdx.x;
     const int step = st->step;
     float* ring = xring + (size_t)b * pre_k;
-    const float x_new = mu_enc(prev[b]);
+    const float x_new = vqw_mu_encode(prev[b]);
     if (threadIdx.x < pre_k) {
         const int j = threadIdx.x;                      // tap j multiplies x(t - (pre_k-1-j))
         const int tau = step - (pre_k - 1 - j);
@@ -251,7 +241,7 @@ __global__ __launch_bounds__(256) void ar_sample_kernel(ArState* st, const float
                 const int idx = ar_sample_truncated(sp, Q, st->samp[b], st->uniforms[(size_t)b * st->n_steps + i_out],
                                                     st->probs_last ? st->probs_last + (size_t)b * Q : probs + (size_t)b * Q);
                 if (lane == 0) {
-                    const float dec = mu_dec((float)idx);
+                    const float dec = vqw_mu_decode((float)idx);
                     if (st->audio) st->audio[(size_t)b * st->n_steps + i_out] = dec;
                     if (st->indices) st->indices[(size_t)b * st->n_steps + i_out] = idx;
                     prev[b] = dec;
@@ -313,7 +303,7 @@ __global__ __launch_bounds__(256) void ar_sample_kernel(ArState* st, const float
                     if (c < u) idx = q + 1;
                 }
             }
-            const float dec = mu_dec((float)idx);
+            const float dec = vqw_mu_decode((float)idx);
             if (st->audio) st->audio[(size_t)b * st->n_steps + i_out] = dec;
             if (st->indices) st->indices[(size_t)b * st->n_steps + i_out] = idx;
             prev[b] = dec;
@@ -538,7 +528,7 @@ __global__ void ar_prefill_finish_kernel(ArState* st, float* prev, float* xring,
     if (audio_tail) {
         for (int i = threadIdx.x; i < B * pre_k; i += blockDim.x) {
             const int b = i / pre_k, s = t_end - pre_k + i % pre_k;
-            if (s >= 0) xring[b * pre_k + (s + 1) % pre_k] = mu_enc(audio_tail[i]);
+            if (s >= 0) xring[b * pre_k + (s + 1) % pre_k] = vqw_mu_encode(audio_tail[i]);
         }
         if (t_end > 0)
             for (int b = threadIdx.x; b < B; b += blockDim.x) prev[b] = audio_tail[b * pre_k + pre_k - 1];

@@ -37,6 +37,7 @@
 
 #include "ar_persist.h"
 #include "ar_sampling.h"
+#include "mu_law.h"
 
 namespace {
 
@@ -131,17 +132,6 @@ __host__ __device__ inline Carve make_carve(int L, int ks, int R, int S, int Q, 
     c.dtab = c.tab + 2 * L;                              // mu-law decode / re-encode of every class index 0..Q
     c.total = c.dtab + 2 * (Q + 1);
     return c;
-}
-
-__device__ __forceinline__ float p_mu_enc(float x) {
-    x = fminf(fmaxf(x, -1.0f), 1.0f);
-    const float s = (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f);
-    return s * log1pf(255.0f * fabsf(x)) / 5.5451774444795623f;
-}
-__device__ __forceinline__ float p_mu_dec(float idx) {
-    const float y = 2.0f * idx / 255.0f - 1.0f;
-    const float s = (y > 0.0f) ? 1.0f : ((y < 0.0f) ? -1.0f : 0.0f);
-    return s * (powf(256.0f, fabsf(y)) - 1.0f) / 255.0f;
 }
 
 __device__ __forceinline__ void publish(u64* p, unsigned tag, float v) {
@@ -278,7 +268,7 @@ __device__ __forceinline__ void emit_row(const PArgs& a, int bi, int b, int t, i
         }
         return;
     }
-    const float dec = dtab[idx];                   // p_mu_dec(idx), p_mu_enc(that): tabulated once per launch
+    const float dec = dtab[idx];                   // vqw_mu_decode(idx), vqw_mu_encode(that): tabulated once per launch
     xh[b * a.pre_k + ((t + 1) % a.pre_k)] = dtab[Q + 1 + idx];
     if (bi == 0) {
         if (a.audio) a.audio[(size_t)b * a.n_steps + it] = dec;
@@ -405,12 +395,12 @@ __global__ __launch_bounds__(NTHR, 1) void ar_persist_kernel(const PGroup grp) {
     for (int i = tid; i < B * a.pre_k; i += NTHR) xh[i] = a.xhist[i];
     if (tid == 0) *fail = 0;
     for (int i = tid; i <= Q; i += NTHR) {
-        const float dec = p_mu_dec((float)i);
+        const float dec = vqw_mu_decode((float)i);
         lds[cv.dtab + i] = dec;
-        lds[cv.dtab + Q + 1 + i] = p_mu_enc(dec);
+        lds[cv.dtab + Q + 1 + i] = vqw_mu_encode(dec);
     }
     __syncthreads();
-    if (tid < B && !a.n_codes) xh[tid * a.pre_k + (t0 % a.pre_k)] = p_mu_enc(a.prev[tid]);   // x_in(t0) = mu_law_encode(previous sample)
+    if (tid < B && !a.n_codes) xh[tid * a.pre_k + (t0 % a.pre_k)] = vqw_mu_encode(a.prev[tid]);   // x_in(t0) = mu_law_encode(previous sample)
     // (code mode: the history saved by the last run already holds the previous code, or 0 = none after a reset)
     __syncthreads();
 
@@ -1088,7 +1078,7 @@ __global__ void arp_prefill_finish_kernel(float* xhist, float* prev, int* state,
     for (int i = threadIdx.x; i < B * pre_k; i += blockDim.x) {
         const int b = i / pre_k, s = t_end - pre_k + i % pre_k;
         if (s < 0) continue;
-        xhist[b * pre_k + (s + 1) % pre_k] = audio_tail ? p_mu_enc(audio_tail[i]) : (float)(code_tail[i] + 1);
+        xhist[b * pre_k + (s + 1) % pre_k] = audio_tail ? vqw_mu_encode(audio_tail[i]) : (float)(code_tail[i] + 1);
     }
     if (audio_tail && t_end > 0)
         for (int b = threadIdx.x; b < B; b += blockDim.x) prev[b] = audio_tail[b * pre_k + pre_k - 1];

@@ -1,6 +1,7 @@
 // HBM-bound kernels of the hot path for gfx950: mu-law companding, Cin==1 convs, row
 // reductions, transposes, softmax cross-entropy and the fused Adam+EMA step.
 // Reference call sites are cited per kernel; numerics follow SURVEY.md Appendix A.
+#include "mu_law.h"
 #include "mu_law_table.h"
 #include "vqw_common.h"
 
@@ -8,14 +9,7 @@ namespace {
 
 __device__ __constant__ unsigned int VQW_MU_LAW_THR_BITS_DEV[255] = VQW_MU_LAW_THR_BITS_LIST;
 
-// ----------------------------------------------------------------------------- mu-law
-__device__ __forceinline__ float mu_encode_f(float x) {
-    // mu_law_ops.py:6-8
-    x = fminf(fmaxf(x, -1.0f), 1.0f);
-    const float s = (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f);
-    return s * log1pf(255.0f * fabsf(x)) / 5.5451774444795623f;
-}
-
+// ----------------------------------------------------------------------------- mu-law (the float forms: mu_law.h)
 // label(x) = #{thr <= clip(x)}: compares only => bit-exact vs the fp32 formula
 // (mu_law_ops.py:11); table from tools/gen_mu_law_table.py.
 __device__ __forceinline__ int mu_encode_i(float x, const float* thr) {
@@ -39,7 +33,7 @@ __device__ __forceinline__ void load_thr(float* thr) {
 
 __global__ void mu_encode_f32_kernel(const float* __restrict__ x, float* __restrict__ y, size_t n) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        y[i] = mu_encode_f(x[i]);
+        y[i] = vqw_mu_encode(x[i]);
 }
 
 __global__ void mu_encode_i32_kernel(const float* __restrict__ x, int32_t* __restrict__ y, size_t n) {
@@ -50,12 +44,8 @@ __global__ void mu_encode_i32_kernel(const float* __restrict__ x, int32_t* __res
 }
 
 __global__ void mu_decode_f32_kernel(const float* __restrict__ idx, float* __restrict__ x, size_t n) {
-    // mu_law_ops.py:26-31
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float y = 2.0f * idx[i] / 255.0f - 1.0f;
-        const float s = (y > 0.0f) ? 1.0f : ((y < 0.0f) ? -1.0f : 0.0f);
-        x[i] = s * (powf(256.0f, fabsf(y)) - 1.0f) / 255.0f;
-    }
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        x[i] = vqw_mu_decode(idx[i]);
 }
 
 // wavenet.py:33-37: labels from x, decoder input from shift_right(x) (wavenet_ops.py:9-14)
@@ -68,7 +58,7 @@ __global__ void wavenet_inputs_kernel(const float* __restrict__ x, float* __rest
         const int t = (int)(i % T);
         const float v = x[i];
         if (labels) labels[i] = mu_encode_i(v, thr);
-        if (inputs) inputs[i] = (t == 0) ? 0.0f : mu_encode_f(x[i - 1]);
+        if (inputs) inputs[i] = (t == 0) ? 0.0f : vqw_mu_encode(x[i - 1]);
     }
 }
 

@@ -9,15 +9,9 @@
 #include <algorithm>
 
 #include "ar_sampling.h"
+#include "mu_law.h"
 
 namespace {
-
-// mu_law_ops.py:26-31, the expression of mu_decode_f32_kernel (pointwise.hip): the same bits for the same index
-__device__ __forceinline__ float smp_mu_dec(float i) {
-    const float y = 2.0f * i / 255.0f - 1.0f;
-    const float s = (y > 0.0f) ? 1.0f : ((y < 0.0f) ? -1.0f : 0.0f);
-    return s * (powf(256.0f, fabsf(y)) - 1.0f) / 255.0f;
-}
 
 // ----------------------------------------------------------------------------- greedy without probs
 // The argmax path of softmax_score_kernel (score.hip): block = NW waves x 64 consecutive time steps of one batch row, wave w
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(NW * 64) void greedy_kernel(const float* __restrict
         if (sv[i][lane] > BV) { BV = sv[i][lane]; BI = si[i][lane]; }
     BI = min(BI, Q - 1);                        // nothing compared greater (-inf or NaN everywhere): still a class
     idx[(size_t)b * T + t] = in ? BI : -1;
-    if (audio) audio[(size_t)b * T + t] = in ? smp_mu_dec((float)BI) : 0.0f;
+    if (audio) audio[(size_t)b * T + t] = in ? vqw_mu_decode((float)BI) : 0.0f;
 }
 
 // ----------------------------------------------------------------------------- sample (and greedy with probs)
@@ -179,7 +173,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_tile_kernel(const float* _
     if (tid < NT && t0 + tid < T) {
         const int c = sidx[tid];
         idx[(size_t)b * T + t0 + tid] = c;
-        if (audio) audio[(size_t)b * T + t0 + tid] = c >= 0 ? smp_mu_dec((float)c) : 0.0f;
+        if (audio) audio[(size_t)b * T + t0 + tid] = c >= 0 ? vqw_mu_decode((float)c) : 0.0f;
     }
 }
 

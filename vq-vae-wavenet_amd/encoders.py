@@ -31,8 +31,19 @@ import torch
 
 from . import _alloc as A
 from . import kernels as K
+from .wavenet import causal_taps, mirrored_taps, side_after, side_mark
 
 BN_EPS = 1e-3  # Keras BatchNormalization default epsilon
+
+
+def strided_conv_dgrad(dy, wt, dx, B, F, ks, pad_left, T_q, T_in, **split):
+    """The input gradient dx [B][F][T_in] of a stride-2 conv of ks taps (F -> F, output gradient dy [B][F][T_q], transposed
+    kernel wt) as a transposed conv in two parity launches: output times tau = 2u + p get the taps j with j = p + pad_left
+    (mod 2).  split: conv_gemm's split-K arguments (tile, split_k < 0: both launches add their K slices into a zeroed dx)."""
+    for p in (0, 1):
+        j0 = (p + pad_left) % 2
+        K.conv_gemm(x0=dy, w=wt[j0:], w_tap_stride=2 * F * F, out0=dx, B=B, T_in=T_q, T_out=(T_in - p + 1) // 2, M=F, C0=F,
+                    taps=[(p + pad_left - j) // 2 for j in range(j0, ks, 2)], out_tstride=2, out_toffset=p, T_store=T_in, **split)
 
 
 def same_pads(n, k, s):
@@ -259,20 +270,14 @@ class Encoder64(Encoder):
                 self._measure(model, ws, dX, 5 + i)
                 if not on_c:                                         # (the forward pass measured X[i-1] otherwise)
                     self._measure(model, ws, ws['X'][i - 1], i)
-            if side is not main:
-                ready = torch.cuda.Event()
-                ready.record(main)
+            ready = side_mark(main, side)
             # both operands as planes where the forward conv ran on the engine (its space-to-depth input planes were kept):
             # tap j, e = j - pad_left, is parity block e & 1 at row offset e >> 1
             w_planes = on_w and on_c and model.wg_planes
             if w_planes:     # (the split the input gradient needs anyway, into this layer's own buffer, BEFORE the weight gradient)
                 K.f16x3_split_activations(dX, ws['edp'][i], B, F, Ti, scale_dev=es[5 + i:6 + i], mode=0)
-                if side is not main:
-                    ready = torch.cuda.Event()
-                    ready.record(main)
-            with torch.cuda.stream(side):                            # weight / bias gradients: nothing downstream waits
-                if side is not main:
-                    side.wait_event(ready)
+                ready = side_mark(main, side)
+            with side_after(side, ready):                            # weight / bias gradients: nothing downstream waits
                 if w_planes:
                     K.f16x3_wgrad(p_planes=ws['esp'][i], p_planes_KC=2 * F // 8, p_tap_chunk=[((j - pl) & 1) * (F // 8) for j in range(5)],
                                   q_planes=ws['edp'][i], dw=G['enc_w'][i - 1], slab=ws['wslab'], B=B, T=Ti, Cp=F, Q0=F,
@@ -298,17 +303,11 @@ class Encoder64(Encoder):
                 K.f16x3_strided_conv(xp=ws['edp'][i] if w_planes else ws['eplanes'], wp=ws['ewtp'][i - 1], out=ws['dX'][i - 1], B=B, T=Ti, Cin=F, M=F, ks=5,
                                      pad_left=pl, dgrad=True, x_scale=es[5 + i:6 + i], w_scale=es[0:1], **self._sconv_split(model, ws))
                 continue
-            # transposed conv: output times tau = 2u+p get taps j with j = p + pad_left (mod 2)
             nsplit = self._short_layer_split(F, (Tin + 1) // 2, B)
             if nsplit > 1:
                 ws['dX'][i - 1].zero_()        # both parity launches add their K slices into it (split_k < 0)
-            for p in (0, 1):
-                j0 = (p + pl) % 2
-                js = list(range(j0, 5, 2))
-                K.conv_gemm(x0=dX, w=model._tt('enc_w')[i - 1][j0:], w_tap_stride=2 * F * F, out0=ws['dX'][i - 1], B=B,
-                            T_in=Ti, T_out=(Tin - p + 1) // 2, M=F, C0=F, taps=[(p + pl - j) // 2 for j in js],
-                            out_tstride=2, out_toffset=p, T_store=Tin, tile=12 if nsplit > 1 else 0,
-                            split_k=-nsplit if nsplit > 1 else 0)
+            strided_conv_dgrad(dX, model._tt('enc_w')[i - 1], ws['dX'][i - 1], B, F, 5, pl, Ti, Tin,
+                               tile=12 if nsplit > 1 else 0, split_k=-nsplit if nsplit > 1 else 0)
         if side is not main:
             main.wait_stream(side)
         dsc.addcmul_(model.bn_mean, G['bn_beta'], value=-1.0)         # shift = beta - mean*scale
@@ -411,7 +410,7 @@ class EncoderMagenta(Encoder):
                         C0=F, in_stride=2, taps=[0])                                               # 'dilated'
             K.conv_gemm(x0=dd, w=P['mag_gf_w'][i], bias=P['mag_gf_b'][i], out0=ws['m_gated'][i],
                         save0=ws['m_th'][i] if save else None, save1=ws['m_sg'][i] if save else None, B=B, T_in=To,
-                        T_out=To, M=2 * F, C0=F, taps=[-(k - 1 - j) * d for j in range(k)], epilogue=K.EPI_GATE)
+                        T_out=To, M=2 * F, C0=F, taps=causal_taps(k, d), epilogue=K.EPI_GATE)
             K.conv_gemm(x0=ws['m_gated'][i], w=P['mag_r_w'][i], bias=P['mag_r_b'][i], out0=en[i + 1], out1=en[i + 1],
                         aux1=dd, B=B, T_in=To, T_out=To, M=F, M0=0, C0=F, taps=[0], epilogue=K.EPI_ACCUM_SPLIT)
             Tin = To
@@ -437,11 +436,10 @@ class EncoderMagenta(Encoder):
             K.rowsum(g_out, total=G['mag_r_b'][i])
             K.conv_gemm(x0=g_out, w=Tt['mag_r_w'][i], out0=dpre, aux0=ws['m_th'][i], aux1=ws['m_sg'][i], B=B, T_in=To,
                         T_out=To, M=F, C0=F, taps=[0], epilogue=K.EPI_GATE_BWD)
-            K.wgrad_gemm(p=ws['m_dd'][i], q0=dpre, dw=G['mag_gf_w'][i], B=B, T_q=To, T_p=To, Cp=F, Q0=2 * F,
-                         taps=[-(k - 1 - j) * d for j in range(k)])
+            K.wgrad_gemm(p=ws['m_dd'][i], q0=dpre, dw=G['mag_gf_w'][i], B=B, T_q=To, T_p=To, Cp=F, Q0=2 * F, taps=causal_taps(k, d))
             K.rowsum(dpre, total=G['mag_gf_b'][i])
             K.conv_gemm(x0=dpre, w=Tt['mag_gf_w'][i], out0=ddd, out1=ddd, aux1=g_out, B=B, T_in=To, T_out=To, M=F,
-                        M0=0, C0=2 * F, taps=[(k - 1 - j) * d for j in range(k)], epilogue=K.EPI_ACCUM_SPLIT)
+                        M0=0, C0=2 * F, taps=mirrored_taps(k, d), epilogue=K.EPI_ACCUM_SPLIT)
             # dd = conv1x1(en_i, stride 2)
             K.wgrad_gemm(p=en[i], q0=ddd, dw=G['mag_d_w'][i], B=B, T_q=To, T_p=Tin, Cp=F, Q0=F, p_stride=2, taps=[0])
             K.rowsum(ddd, total=G['mag_d_b'][i])
@@ -593,12 +591,7 @@ class Encoder2019(Encoder):
         pl, _ = same_pads(Fr, 4, 2)
         K.wgrad_gemm(p=a[1], q0=da[2], dw=G['e19_w2'], B=B, T_q=Tz, T_p=Fr, Cp=F, Q0=F, p_stride=2,
                      taps=[j - pl for j in range(4)])
-        for p in (0, 1):
-            j0 = (p + pl) % 2
-            js = list(range(j0, 4, 2))
-            K.conv_gemm(x0=da[2], w=Tt['e19_w2'][j0:], w_tap_stride=2 * F * F, out0=da[1], B=B, T_in=Tz,
-                        T_out=(Fr - p + 1) // 2, M=F, C0=F, taps=[(p + pl - j) // 2 for j in js], out_tstride=2,
-                        out_toffset=p, T_store=Fr)
+        strided_conv_dgrad(da[2], Tt['e19_w2'], da[1], B, F, 4, pl, Tz, Fr)
         # a_1 = relu(conv_1(a_0)) + a_0
         K.bn_relu_bwd(da[1], r[1], ones, dc[0])
         K.rowsum(dc[0], total=G['e19_b'][1])

@@ -10,6 +10,7 @@ Parameters live in ONE flat fp32 buffer (so gradients are one contiguous all-red
 and Adam+EMA is one kernel); `named_parameters()` exposes them under the reference's TF
 variable names and shapes.
 """
+import contextlib
 import json
 import math
 import os
@@ -66,6 +67,38 @@ def prefill_window(t_end, ks, dilations, pre_k, ratio):
     s0 = max(0, t_end - W) // ratio * ratio
     end = -(-t_end // ratio) * ratio
     return W, s0, end
+
+
+def causal_taps(ks, d):
+    """The input shifts of a causal conv of ks taps with dilation d, oldest tap first: tap j reads t - (ks - 1 - j) d."""
+    return [-(ks - 1 - j) * d for j in range(ks)]
+
+
+def mirrored_taps(ks, d):
+    """causal_taps mirrored: the shifts of that conv's input gradient (tap j reads t + (ks - 1 - j) d of the output gradient)."""
+    return [(ks - 1 - j) * d for j in range(ks)]
+
+
+def side_mark(main, side):
+    """Fork work to the side stream, first half: the point on main it may start behind, as a recorded event (None when
+    side is main: nothing to wait for)."""
+    if side is main:
+        return None
+    mark = torch.cuda.Event()
+    mark.record(main)
+    return mark
+
+
+@contextlib.contextmanager
+def side_after(side, mark):
+    """... second half: what runs inside is enqueued on the side stream, behind side_mark's mark (on the current stream when
+    there is none).  Nothing downstream waits for it until main waits for the side stream."""
+    if mark is None:
+        yield
+        return
+    with torch.cuda.stream(side):
+        side.wait_event(mark)
+        yield
 
 
 def mix_seed(*words):
@@ -628,7 +661,7 @@ class WaveNet:
             K.conv_gemm(x0=net[l], w=P['gated_w'][l], bias=P['gated_b'][l], out0=ws['gated'][l],
                         save0=ws['th'][l] if save else None, save1=ws['sg'][l] if save else None,
                         cond=ce_flat[l * 2 * R * Tz:], cond_T=Tz, cond_bstride=cbs, B=B, T_in=T, T_out=T,
-                        M=2 * R, C0=R, taps=[-(self.ks - 1 - j) * d for j in range(self.ks)],
+                        M=2 * R, C0=R, taps=causal_taps(self.ks, d),
                         epilogue=K.EPI_GATE)                                              # wavenet_ops.py:104-114
             K.conv_gemm(x0=ws['gated'][l], w=P['out_w'][l], bias=P['out_b'][l], out0=ws['skip'], out1=net[l + 1],
                         aux1=net[l], B=B, T_in=T, T_out=T, M=S + R, M0=S, C0=R, taps=[0],
@@ -741,12 +774,9 @@ class WaveNet:
             return self.forward(x, spk, compute_grad_seed, lens)
         self.x3_flag.zero_()
         ws = self.forward(x, spk, compute_grad_seed, lens)
-        if (ws.get('x3_used') or ws.get('enc_x3')) and int(self.x3_flag.item()) != 0:
-            self._x3_active = False
-            try:
+        if self._ran_guarded(ws) and int(self.x3_flag.item()) != 0:
+            with self._fp32_engine():
                 ws = self.forward(x, spk, compute_grad_seed, lens)
-            finally:
-                self._x3_active = True
         return ws
 
     # ------------------------------------------------------------------ held-out scoring
@@ -803,12 +833,9 @@ class WaveNet:
                 self.flat.copy_(self.ema)
             self.x3_flag.zero_()
             self._score_pass(x, spk, ws)
-            if self.x3_guard and (ws.get('x3_used') or ws.get('enc_x3')) and int(self.x3_flag.item()) != 0:
-                self._x3_active = False
-                try:
+            if self.x3_guard and self._ran_guarded(ws) and int(self.x3_flag.item()) != 0:
+                with self._fp32_engine():
                     self._score_pass(x, spk, ws)
-                finally:
-                    self._x3_active = True
             return finish(ws, t_end, f_end)
         finally:
             if live is not None:
@@ -1002,18 +1029,13 @@ class WaveNet:
         pend_gate, pend_res = {False: [], True: []}, []
 
         def on_side(launch):           # weight gradients: nothing downstream waits for them
-            if side is main:
-                return launch()
-            ev = torch.cuda.Event()
-            ev.record(main)
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
+            with side_after(side, side_mark(main, side)):
                 launch()
 
         def flush_gate(odd):
             layers, pend_gate[odd] = pend_gate[odd], []
             if layers:
-                probs = [dict(dw=G['gated_w'][i], taps=[-(ks - 1 - j) * self.dil[i] for j in range(ks)],
+                probs = [dict(dw=G['gated_w'][i], taps=causal_taps(ks, self.dil[i]),
                               p_scale=sc('X', i), q0_scale=sc('DP', i), q_seg=dce.view(-1)[i * 2 * R * Tz:],
                               **(dict(p_planes=ws['xp_all'][i]) if pp else dict(p=net[i])),
                               **(dict(q_planes=ws['dp_all'][i], q_planes_scale=GS) if qp else dict(q0=ws['dpre_all'][i]))) for i in layers]
@@ -1057,10 +1079,8 @@ class WaveNet:
                             epilogue=K.EPI_GATE_BWD, tile=self.tiles['gate_bwd'])
             if calib:
                 K.f16x3_amax(dpre, am('DP', l))
-            if side is not main:
-                ready = torch.cuda.Event()
-                ready.record(main)
-            taps_b = [(ks - 1 - j) * d for j in range(ks)]
+            ready = side_mark(main, side)
+            taps_b = mirrored_taps(ks, d)
             if dgrad_x3:
                 if not gbwd_x3:      # (gate backward hands dpre over as planes)
                     K.f16x3_split_activations(dpre, ws['dp'], B, 2 * R, T, scale=GS, mode=md)
@@ -1079,7 +1099,7 @@ class WaveNet:
             if calib:
                 K.f16x3_amax(dnet_next, am('G'))
             if batched:
-                odd = any(((ks - 1 - j) * d) % 4 for j in range(ks))
+                odd = any(shift % 4 for shift in taps_b)
                 pend_gate[odd].append(l)
                 if len(pend_gate[odd]) >= plan.gate_batch:      # 6: 36 tiles x 7 K splits = 252 blocks (tools/wg_batch_sweep.sh)
                     flush_gate(odd)
@@ -1089,24 +1109,21 @@ class WaveNet:
                         flush_res()
                 dnet = dnet_next
                 continue
-            with torch.cuda.stream(side):
-                if side is not main:
-                    side.wait_event(ready)
+            with side_after(side, ready):
                 if wg_x3:    # weight gradients on the fp16 pipe too: operands split in registers with the planes' guard scales;
                     # the bias sums and the condition gradient (sums of dpre per condition frame) come out of the same kernels
                     K.f16x3_wgrad(p=ws['gated'][l], q0=dskip, q1=None if top else dnet, dw=G['out_w'][l], slab=ws['wslab'], B=B,
                                   T=T, Cp=R, Q0=S, Q1=0 if top else R, lddw=S + R, taps=[0], q0_scale=sc('G'), q1_scale=sc('G'),
                                   q_total=None if top else G['out_b'][l], total_cols=(S, S + R), mode=md)
                     K.f16x3_wgrad(p=net[l], q0=dpre, dw=G['gated_w'][l], slab=ws['wslab'], B=B, T=T, Cp=R, Q0=2 * R,
-                                  taps=[-(ks - 1 - j) * d for j in range(ks)], p_scale=sc('X', l), q0_scale=sc('DP', l),
+                                  taps=causal_taps(ks, d), p_scale=sc('X', l), q0_scale=sc('DP', l),
                                   q_seg=dce.view(-1)[l * 2 * R * Tz:], seg_T=Tz, seg_bstride=cbs, mode=md)
                 else:
                     K.wgrad_gemm(p=ws['gated'][l], q0=dskip, q1=None if top else dnet, dw=G['out_w'][l], B=B, T_q=T, T_p=T,
                                  Cp=R, Q0=S, Q1=0 if top else R, lddw=S + R, taps=[0])
                     if not top:
                         K.rowsum(dnet, total=G['out_b'][l][S:])
-                    K.wgrad_gemm(p=net[l], q0=dpre, dw=G['gated_w'][l], B=B, T_q=T, T_p=T, Cp=R, Q0=2 * R,
-                                 taps=[-(ks - 1 - j) * d for j in range(ks)])
+                    K.wgrad_gemm(p=net[l], q0=dpre, dw=G['gated_w'][l], B=B, T_q=T, T_p=T, Cp=R, Q0=2 * R, taps=causal_taps(ks, d))
                     K.rowsum(dpre, seg_out=seg_l, total=G['gated_b'][l], seg=ratio)
                     dce[:, l * 2 * R:(l + 1) * 2 * R].copy_(seg_l)
                 if side is not main:
@@ -1273,6 +1290,44 @@ class WaveNet:
         self.finish_steps()
         return self._train_step_now(x, spk, on_forward, lengths=lens)
 
+    @contextlib.contextmanager
+    def _fp32_engine(self):
+        """A pass repeated on the fp32 engine: inside, no plan puts anything on the plane engine."""
+        self._x3_active = False
+        try:
+            yield
+        finally:
+            self._x3_active = True
+
+    @staticmethod
+    def _ran_guarded(ws):
+        """Whether the pass in this workspace ran anything on the guarded engine (the stack or the front's layers): whether its range flag says anything."""
+        return bool(ws.get('x3_used') or ws.get('enc_x3'))
+
+    def _attempt(self, x, spk, step, lengths, *hooks):
+        """One attempt at training step `step`: forward, the hooks (called with the workspace between the passes; None: skipped),
+        backward, the end of the gradient exchange.  Returns (workspace, data-parallel world size)."""
+        self._in_step = True           # (forward() settles deferred steps for every other caller)
+        try:
+            ws = self._forward_step(x, spk, step, lengths)
+            for hook in hooks:
+                if hook is not None:
+                    hook(ws)
+            self.backward(x, spk, ws)
+        finally:
+            self._in_step = False
+        return ws, self.grad_sync.finish() if self.grad_sync is not None else 1
+
+    def _commit(self, ws, world, scales=True, skip=None):
+        """Keep the attempt: the next step's plane scales (scales=False: the pass measured none), what the front updates by itself,
+        Adam + EMA.  skip: device int32, non-zero when the kernels run = each of the three changes nothing."""
+        guard = {} if skip is None else {'skip': skip}      # (an unguarded step names none: the calls are what they were)
+        if scales:     # the planes written inside the kernels: max-abs * scale in [2^12, 2^13), 8x headroom
+            n0 = self.SL['G']
+            K.f16x3_update_scales(self.x3_amax[n0:], self.x3_scale[n0:], target_exp=13, **guard)
+        self._front_step(ws, **guard)
+        self.apply_gradients(1.0 / world, **guard)
+
     def _train_step_now(self, x, spk, on_forward=None, known_flagged=False, lengths=None):
         """The step with its range flag read on the spot.  known_flagged: the fp16x3 attempt of this step already ran and
         raised the flag (deferred mode): go straight to the repeat.  lengths: train_step's, already checked."""
@@ -1281,38 +1336,25 @@ class WaveNet:
         if not known_flagged:
             if self.x3_guard:
                 self.x3_flag.zero_()
-            ws = self._forward_step(x, spk, gs0, lengths)
-            if on_forward is not None:
-                on_forward(ws)
-            self.backward(x, spk, ws)
-            world = self.grad_sync.finish() if self.grad_sync is not None else 1
+            ws, world = self._attempt(x, spk, gs0, lengths, on_forward)
             if self.bf16 and ws.get('x3_used'):
                 self.x3_steps += 1
-            guarded = bool(self.x3_guard and (ws.get('x3_used') or ws.get('enc_x3')))
-        if guarded:
-            if known_flagged or self._x3_overflowed():
-                self.x3_fallbacks += 1
-                self._x3_active = False
-                try:
-                    self.x3_amax.zero_()
-                    ws, am = self._forward_step(x, spk, gs0, lengths), self._slots(self.x3_amax, True)
-                    for l in range(1, self.L):       # what the layer-input planes would have held (net[L] feeds nothing)
-                        K.f16x3_amax(ws['net'][l], am('X', l))
-                    K.f16x3_amax(ws['skip'], am('SK'))
-                    K.f16x3_amax(ws['h1'], am('H1'))
-                    if on_forward is not None:
-                        on_forward(ws)
-                    self.backward(x, spk, ws)
-                    world = self.grad_sync.finish() if self.grad_sync is not None else 1
-                finally:
-                    self._x3_active = True
-            else:
-                self.x3_steps += 1
-            # next step's scales of the planes written inside the kernels (max-abs * scale in [2^12, 2^13): 8x headroom)
-            n0 = self.SL['G']
-            K.f16x3_update_scales(self.x3_amax[n0:], self.x3_scale[n0:], target_exp=13)
-        self._front_step(ws)
-        self.apply_gradients(1.0 / world)
+            guarded = bool(self.x3_guard and self._ran_guarded(ws))
+        if guarded and (known_flagged or self._x3_overflowed()):
+            self.x3_fallbacks += 1
+
+            def measure(ws):                     # what the layer-input planes would have held (net[L] feeds nothing)
+                am = self._slots(self.x3_amax, True)
+                for l in range(1, self.L):
+                    K.f16x3_amax(ws['net'][l], am('X', l))
+                K.f16x3_amax(ws['skip'], am('SK'))
+                K.f16x3_amax(ws['h1'], am('H1'))
+            with self._fp32_engine():
+                self.x3_amax.zero_()
+                ws, world = self._attempt(x, spk, gs0, lengths, measure, on_forward)
+        elif guarded:
+            self.x3_steps += 1
+        self._commit(ws, world, scales=guarded)
         return ws
 
     def _train_step_deferred(self, x, spk, lengths=None):
@@ -1329,25 +1371,15 @@ class WaveNet:
         finish_steps() before reading what a step left behind (losses, gradients, parameters; state_dict() / encode() do)."""
         t_host = time.perf_counter()
         self.x3_flag.zero_()
-        self._in_step = True
-        try:
-            ws = self._forward_step(x, spk, self.global_step, lengths)
-            self.backward(x, spk, ws)
-        finally:
-            self._in_step = False
-        world = self.grad_sync.finish() if self.grad_sync is not None else 1
-        if not (ws.get('x3_used') or ws.get('enc_x3')):       # nothing on the guarded engine in this workspace
-            self._front_step(ws)
-            self.apply_gradients(1.0 / world)
+        ws, world = self._attempt(x, spk, self.global_step, lengths)
+        if not self._ran_guarded(ws):       # nothing on the guarded engine in this workspace
+            self._commit(ws, world, scales=False)
             return ws
         if self.grad_sync is not None and self.grad_sync.active:
             self.grad_sync.all_reduce_max(self.x3_flag)       # every rank takes the same branch
         torch.maximum(self.x3_void, self.x3_flag, out=self.x3_void)
-        n0 = self.SL['G']
-        K.f16x3_update_scales(self.x3_amax[n0:], self.x3_scale[n0:], target_exp=13, skip=self.x3_void)
         gs0 = self.global_step
-        self._front_step(ws, skip=self.x3_void)
-        self.apply_gradients(1.0 / world, skip=self.x3_void)
+        self._commit(ws, world, skip=self.x3_void)
         if self._void_host is None:
             self._void_host = torch.zeros(4, dtype=torch.int32).pin_memory()
         slot = self._void_slot
@@ -1429,7 +1461,7 @@ class WaveNet:
             d = self.dil[l]
             K.conv_gemm(x0=cur, w=P['gated_w'][l], bias=P['gated_b'][l], out0=gated, cond=ce_flat[l * 2 * R * Tzw:],
                         cond_T=Tzw, cond_bstride=Mall * Tzw, B=B, T_in=Tw, T_out=Tw, M=2 * R, C0=R,
-                        taps=[-(self.ks - 1 - j) * d for j in range(self.ks)], epilogue=K.EPI_GATE)
+                        taps=causal_taps(self.ks, d), epilogue=K.EPI_GATE)
             # the residual half of the 1x1 skip | residual conv only (the skip sum is not part of the state): M0 = 0, every
             # row goes to out1 = aux1 + conv (out0 is never written)
             K.conv_gemm(x0=gated, w=P['out_w'][l].view(-1)[S:], ldw=S + R, bias=P['out_b'][l][S:], out1=nxt, aux1=cur,
