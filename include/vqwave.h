@@ -379,6 +379,17 @@ int vqw_adam_ema_step_scaled(float* param, const float* grad, float* m, float* v
                              float decay, float grad_scale, const int32_t* skip, const float* scale, vqw_stream_t s);
 
 /* ------------------------------------------------------------------------------------
+ * Gradient accumulation over micro-batches (WaveNet.accumulate): one pass over n floats,
+ *   acc NULL:      out[i] = grad[i]              (a guarded copy: a window's first micro-step)
+ *   acc non-NULL:  out[i] = acc[i] + grad[i]     (one fp32 add per element)
+ * out may be the same pointer as acc or as grad: element i is read before it is written and no other element is touched.  Any
+ * other overlap of out with an input is undefined.  skip (may be NULL): a device int32 read when the kernel RUNS; non-zero =
+ * nothing is written (the rule of vqw_adam_ema_step_guarded).  n = 0 returns 0 without a launch; NULL out or grad is an error.
+ * Pointers need 4-byte alignment; with all pointers in use 16-byte aligned the kernel moves 16-byte vectors plus a scalar
+ * tail of n % 4, otherwise scalars.  Bound by HBM: two (copy) or three (add) streams of n floats.                          */
+int vqw_grad_accumulate(float* out, const float* acc, const float* grad, size_t n, const int32_t* skip, vqw_stream_t s);
+
+/* ------------------------------------------------------------------------------------
  * Global and per-segment L2 norms of a flat fp32 buffer and the scale of tf.clip_by_global_norm, left on the device.
  *   g[i]        = buf[i] * grad_scale                (fp32, as the optimiser forms it; 1/world under data parallel)
  *   seg_norm[k] = sqrt(sum of g[i]^2 over the chunks of segment k)

@@ -33,6 +33,11 @@ code (sonnet's VectorQuantizerEMA) instead of by Adam on the codebook loss; `-co
 code whose moving count falls below T (e.g. 0.05) is restarted on an encoder output of the batch.  They override `codebook_ema`
 / `codebook_restart` of the parameters file (0 = off).  Adds `[codebook used U/K restarted R]` to the console line and
 `codebook_used`, `codebook_restarted` to summaries.jsonl, on logged steps.
+
+`-accumulate N`: every optimiser step sums the gradients of N batches of `-batch` rows (VQVAE.accumulate: one Adam + EMA step on
+a batch of N x `-batch` rows, up to fp32 summation order; data parallel: one gradient exchange per step).  `-step` stays the
+number of optimiser steps; logging, evaluation, audio and saving happen on a step's last batch, and the logged losses are that
+batch's.  Adds `[accum N]` to the console line and `accumulate` to summaries.jsonl.  Not together with `-codebook_ema`.
 """
 import importlib
 import json
@@ -86,7 +91,13 @@ def main():
                         help='decay in (0, 1) of the codebook\'s moving averages (0 = off: Adam trains the codebook)')
     parser.add_argument('-codebook_restart', default=None, type=float, dest='codebook_restart', metavar='float',
                         help='restart a code whose moving count falls below this threshold in (0, 1) (0 = never; needs -codebook_ema)')
+    parser.add_argument('-accumulate', default=1, type=int, dest='accumulate', metavar='int',
+                        help='batches whose gradients are summed before each optimiser step (1 = off)')
     args = parser.parse_args()
+    if args.accumulate < 1:
+        parser.error('-accumulate must be an integer >= 1 (got %r)' % args.accumulate)
+    if args.accumulate > 1 and args.codebook_ema:
+        parser.error('-accumulate > 1 cannot be combined with -codebook_ema (the codebook\'s own update per batch has no rule yet)')
     if args.clip_norm is not None and not args.clip_norm > 0:
         parser.error('-clip_norm must be > 0 (got %r)' % args.clip_norm)
     if args.time_jitter is not None and not 0.0 <= args.time_jitter <= 1.0:
@@ -159,6 +170,7 @@ def main():
         model.grad_sync = pkg.parallel.GradAllReduce(model.grad)
     model.defer_guard = os.environ.get('VQW_DEFER_GUARD', '1') != '0'     # the engine's range flag is read one step late (no host sync per step)
     model.clip_norm = args.clip_norm if args.clip_norm is not None else (float('inf') if args.grad_norm else None)
+    model.accumulate = args.accumulate
     gs, lr = model.global_step, model.lr_at(model.global_step)
     if rank == 0:
         print('[restore] last global step: %d, learning rate: %.5f' % (gs, lr))
@@ -190,8 +202,9 @@ def main():
 
     for step in range(1, 1 + args.num_steps):
         t = time.time()
-        x, spk = dataset.next()
-        ws = model.train_step(x, spk)
+        for _ in range(args.accumulate):      # one window: global_step advances on its last batch, and only then is anything logged
+            x, spk = dataset.next()
+            ws = model.train_step(x, spk)
         gs = model.global_step
         eval_now = eval_set is not None and gs % args.eval_interval == 0
         audio_now = audio_dir is not None and gs % args.audio_interval == 0
@@ -225,6 +238,9 @@ def main():
                 msg += ' [eval bits %.5f]' % extra['eval']['bits_per_sample']
             if audio_now:
                 msg += ' [audio %d]' % ax.shape[0]
+            if args.accumulate > 1:               # (the losses are those of the window's last batch)
+                extra['accumulate'] = args.accumulate
+                msg += ' [accum %d]' % args.accumulate
             print(progress + msg + display_time(t, (args.num_steps - step) * t), end='', flush=True)
             # the reference writes its merged summaries to a TensorBoard event file here (train.py:104-109); without
             # TensorFlow the same tags go to <save_dir>/summaries.jsonl, one line per logged step

@@ -19,6 +19,14 @@ console line gains `[scored 0.73]`, the share of the logged step's positions tha
 `-eval_list FILE -eval_interval N [-eval_batches M]` (as train.py): every N steps the first M padded batches of the list are
 scored with the EMA weights (LatentPrior.evaluate on the codes of the zero-padded audio, lengths = the rows' frames) and the
 line gains `[eval bits/code ...]`.
+
+`-accumulate N` (as train.py): every optimiser step sums the gradients of N batches (LatentPrior.accumulate); `-step` stays the
+number of optimiser steps, and logging, evaluation and saving happen on a step's last batch, whose loss is the one logged.  With
+`-whole_utterances` every batch contributes the mean over its own scored codes: a step is the average of N such means, not the
+mean over all codes of the N batches.  The console line gains `[accum N]`.
+
+Every logged step also appends one line to `summaries.jsonl` next to `-save`: `global_step`, `learning_rate`, `loss`, with
+`-clip_norm` / `-grad_norm` `grad_norm`, with `-accumulate N > 1` `accumulate`.
 """
 import importlib
 import json
@@ -57,7 +65,11 @@ def main():
     parser.add_argument('-eval_batches', default=4, type=int, dest='eval_batches', metavar='int', help='held-out batches per evaluation')
     parser.add_argument('-eval_dataset', default=None, dest='eval_dataset', metavar='DATASET', help='dataset the list belongs to (default: -dataset)')
     parser.add_argument('-data_root', default='data/', dest='data_root', metavar='string', help='where the held-out wavs and *_speakers.txt are')
+    parser.add_argument('-accumulate', default=1, type=int, dest='accumulate', metavar='int',
+                        help='batches whose gradients are summed before each optimiser step (1 = off)')
     args = parser.parse_args()
+    if args.accumulate < 1:
+        parser.error('-accumulate must be an integer >= 1 (got %r)' % args.accumulate)
     if args.clip_norm is not None and not args.clip_norm > 0:
         parser.error('-clip_norm must be > 0 (got %r)' % args.clip_norm)
     if args.min_frames is not None and not args.whole:
@@ -116,6 +128,7 @@ def main():
         prior.load_state_dict(torch.load(args.prior_path, map_location='cpu', weights_only=True))
     prior.defer_guard = os.environ.get('VQW_DEFER_GUARD', '1') != '0'
     prior.clip_norm = args.clip_norm if args.clip_norm is not None else (float('inf') if args.grad_norm else None)
+    prior.accumulate = args.accumulate
     gs = prior.global_step
     print('[restore] last global step: %d, learning rate: %.5f' % (gs, prior.lr_at(gs)))
     save_dir, save_name = os.path.split(args.save_path)
@@ -139,20 +152,28 @@ def main():
 
     for step in range(1, 1 + args.num_steps):
         t = time.time()
-        if args.whole:
-            x, spk, lengths = dataset.next()
-            frames = lengths // 64                   # CPU int32 [B]: the rows' code counts
-        else:
-            (x, spk), frames = dataset.next(), None
-        codes = vqvae.encode_codes(x, spk)       # [B][frames] int32
-        prior.train_step(codes, spk) if frames is None else prior.train_step(codes, spk, lengths=frames)
+        for _ in range(args.accumulate):      # one window: global_step advances on its last batch, and only then is anything logged
+            if args.whole:
+                x, spk, lengths = dataset.next()
+                frames = lengths // 64                   # CPU int32 [B]: the rows' code counts
+            else:
+                (x, spk), frames = dataset.next(), None
+            codes = vqvae.encode_codes(x, spk)       # [B][frames] int32
+            prior.train_step(codes, spk) if frames is None else prior.train_step(codes, spk, lengths=frames)
         gs = prior.global_step
         eval_now = eval_set is not None and gs % args.eval_interval == 0
         if gs % args.interval == 0 or step == args.num_steps or eval_now:
             ws = prior._workspace(args.batch_size, args.frames)
             loss = prior.losses(ws)[0]             # synchronises: only every `interval` steps
             t = time.time() - t
-            gnorm = ' [gnorm %.4f]' % prior.grad_norms()['global'] if prior.clip_norm is not None else ''
+            summary = {'global_step': gs, 'learning_rate': prior.lr_at(gs - 1), 'loss': loss}
+            gnorm = ''
+            if prior.clip_norm is not None:
+                summary['grad_norm'] = prior.grad_norms()['global']
+                gnorm = ' [gnorm %.4f]' % summary['grad_norm']
+            if args.accumulate > 1:               # (the loss is that of the window's last batch)
+                summary['accumulate'] = args.accumulate
+                gnorm += ' [accum %d]' % args.accumulate
             if frames is not None:
                 gnorm += ' [scored %.2f]' % (int(frames.sum()) / (args.batch_size * args.frames))
             if eval_now:
@@ -162,6 +183,8 @@ def main():
                 gnorm += ' [eval bits/code %.5f]' % totals.report('code')['bits_per_code']
             print('\r[step %d] %.2f%% [prior %.5f] [lr %.5f]%s [BATCH %.3fs]     '
                   % (gs, step / args.num_steps * 100, loss, prior.lr_at(gs - 1), gnorm, t), end='', flush=True)
+            with open(os.path.join(save_dir or '.', 'summaries.jsonl'), 'a') as f:
+                f.write(json.dumps(summary) + '\n')
     torch.cuda.synchronize()
     path = '%s-%d.pt' % (args.save_path, prior.global_step)
     torch.save(prior.state_dict(), path)

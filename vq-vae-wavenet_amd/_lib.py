@@ -157,7 +157,8 @@ SIGNATURES = {
     'vqw_adam_ema_step': (_i, [_fp, _fp, _fp, _fp, _fp, _sz, _f, _f, _f, _f, _f, _f, _fp]),
     'vqw_adam_ema_step_guarded': (_i, [_fp, _fp, _fp, _fp, _fp, _sz, _f, _f, _f, _f, _f, _f, _fp, _fp]),
     'vqw_adam_ema_step_scaled': (_i, [_fp, _fp, _fp, _fp, _fp, _sz, _f, _f, _f, _f, _f, _f, _fp, _fp, _fp]),
-    'vqw_grad_norm_segmented': (_i, [_fp, _fp, _i, _i, _fp, _f, _f, _fp, _fp]),
+    'vqw_grad_accumulate': (_i, [_fp, _fp, _fp, _sz, _fp, _fp]),
+    'vqw_grad_norm_segmented':(_i, [_fp, _fp, _i, _i, _fp, _f, _f, _fp, _fp]),
     'vqw_ar_decode_create': (_i, [C.POINTER(_fp), C.POINTER(ArWeights), _i]),
     'vqw_ar_decode_create_ex': (_i, [C.POINTER(_fp), C.POINTER(ArWeights), _i, _i]),
     'vqw_ar_decode_reset': (_i, [_fp, _fp]),

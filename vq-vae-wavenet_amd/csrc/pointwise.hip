@@ -554,6 +554,26 @@ __global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__
     }
 }
 
+// ----------------------------------------------------------------------------- gradient accumulation
+// out = grad (ADD false) or acc + grad (ADD true), one fp32 add per element, behind the optimiser's skip guard.  out may be acc
+// or grad: every element is read at the index it is written at, before the write -- hence no __restrict__ on the three.
+template <bool ADD>
+__global__ void grad_accumulate_kernel(float* out, const float* acc, const float* grad, size_t n4, size_t n,
+                                       const int* __restrict__ skip) {
+    if (skip && *skip) return;          // a voided micro-step: the accumulator (or the flat gradient) keeps what it held
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
+        f32x4 G = reinterpret_cast<const f32x4*>(grad)[i];
+        if (ADD) G = reinterpret_cast<const f32x4*>(acc)[i] + G;
+        reinterpret_cast<f32x4*>(out)[i] = G;
+    }
+    // tail (n not a multiple of 4), or everything where a pointer is not 16-byte aligned (n4 = 0)
+    for (size_t i = 4 * n4 + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float G = grad[i];
+        out[i] = ADD ? acc[i] + G : G;
+    }
+}
+
 inline int grid_for(size_t n, int block) {
     size_t g = (n + block - 1) / block;
     if (g > 2048) g = 2048;
@@ -760,6 +780,18 @@ extern "C" int vqw_adam_ema_step_scaled(float* param, const float* grad, float* 
     hipLaunchKernelGGL(scale ? adam_ema_kernel<true> : adam_ema_kernel<false>, dim3(grid_for(n4 ? n4 : n, 256)), dim3(256), 0, (hipStream_t)s,
                        param, grad, m, v, ema, n4, n, lr_t, beta1, beta2, eps, decay, grad_scale, skip, scale);
     VQW_LAUNCH_CHECK("vqw_adam_ema_step");
+    return 0;
+}
+
+extern "C" int vqw_grad_accumulate(float* out, const float* acc, const float* grad, size_t n, const int32_t* skip, vqw_stream_t s) {
+    if (n == 0) return 0;
+    VQW_CHECK(out && grad, "vqw_grad_accumulate: null pointer");
+    const uintptr_t al = reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(acc);   // (acc NULL: no bits)
+    VQW_CHECK((al & 3u) == 0, "vqw_grad_accumulate: pointers must be 4-byte aligned");
+    const size_t n4 = (al & 15u) ? 0 : n / 4;
+    hipLaunchKernelGGL(acc ? grad_accumulate_kernel<true> : grad_accumulate_kernel<false>, dim3(grid_for(n4 ? n4 : n, 256)), dim3(256), 0,
+                       (hipStream_t)s, out, acc, grad, n4, n, skip);
+    VQW_LAUNCH_CHECK("vqw_grad_accumulate");
     return 0;
 }
 

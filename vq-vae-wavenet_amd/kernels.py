@@ -884,7 +884,21 @@ def adam_ema_step(param, grad, m, v, ema, *, lr_t, beta1=0.9, beta2=0.999, eps=1
                                              L.ptr(skip), L.ptr(scale), L.stream()))
 
 
-GRAD_NORM_CHUNK = 16384      # floats per workgroup of the norm pass: ~2100 chunks for the 35 M parameters, several per CU
+def grad_accumulate(out, grad, acc=None, skip=None):
+    """vqw_grad_accumulate over n = out.numel() floats: out = grad (acc None: a guarded copy) or out = acc + grad, one fp32 add per
+    element.  out may be the same tensor as acc or as grad.  skip: device int32 read when the kernel runs; non-zero = nothing
+    is written (adam_ema_step's rule)."""
+    _need(out, 0, 'out')
+    n = out.numel()
+    _need(grad, n, 'grad')
+    if acc is not None:
+        _need(acc, n, 'acc')
+    if skip is not None and (skip.dtype != torch.int32 or skip.numel() < 1 or not skip.is_cuda):
+        raise ValueError('grad_accumulate: skip must be a device int32')
+    L.check(L.lib().vqw_grad_accumulate(L.ptr(out), L.ptr(acc), L.ptr(grad), n, L.ptr(skip), L.stream()))
+
+
+GRAD_NORM_CHUNK = 16384     # floats per workgroup of the norm pass: ~2100 chunks for the 35 M parameters, several per CU
 GRAD_NORM_MAX_SEG = 2048     # vqw_grad_norm_segmented keeps the segments' ranges and sums in LDS
 
 

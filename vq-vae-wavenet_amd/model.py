@@ -158,14 +158,16 @@ class VQVAE(WaveNet):
 
     def jitter_uniforms(self, B, Tz, step):
         """The uniforms [B][Tz] (fp32 in [0, 1), on the device) that decide step `step`'s jitter: a pure function of
-        (jitter_seed, step, data-parallel rank) -- a device generator of its own, seeded again at every call, so the global
+        (jitter_seed, step, data-parallel rank; with accumulate > 1 also accum_index) -- a device generator of its own, seeded again at every call, so the global
         torch RNG is never touched and every pass that belongs to one step (the fp16x3 attempt, its fp32 repeat, a deferred
         step run again) draws the same values.  No host sync.  Each data-parallel rank draws its own stream: a sharded batch
         is not the same draw as the full batch."""
         if self._jitter_gen is None:
             self._jitter_gen = torch.Generator(device=self.dev)
         rank = self.grad_sync.rank if self.grad_sync is not None else 0
-        self._jitter_gen.manual_seed(mix_seed(self.jitter_seed, step, rank))
+        # (accumulate > 1: the micro-step's place in its window is a seed word too -- the micro-batches of one step draw apart)
+        words = (step, rank) if self._accumulate == 1 else (step, rank, self._accum_k)
+        self._jitter_gen.manual_seed(mix_seed(self.jitter_seed, *words))
         return torch.rand(B, Tz, generator=self._jitter_gen, device=self.dev)
 
     def jitter_moved(self, ws):
@@ -202,6 +204,8 @@ class VQVAE(WaveNet):
         K.codebook_ema_constants(decay, restart)      # (refuses what is no decay / no threshold)
         if (float(decay) != 0.0 or float(restart) != 0.0) and not self.use_vq:
             raise ValueError('codebook_ema / codebook_restart need a codebook (use_vq is false)')
+        if float(decay) > 0.0 and self._accumulate > 1:      # (the other order is refused by WaveNet.accumulate)
+            raise ValueError("codebook_ema with accumulate > 1 is not supported: the codebook's own update per micro-batch has no rule yet")
         self._codebook_ema, self._codebook_restart = float(decay), float(restart)
 
     def _world(self):

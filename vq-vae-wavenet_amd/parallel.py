@@ -24,10 +24,19 @@ class GradAllReduce:
         self.cuda = flat_grad.is_cuda
         self.stream = torch.cuda.Stream(device=flat_grad.device) if self.cuda else None
         self.pending = []
+        # hold: set by a model that accumulates gradients over micro-batches (WaveNet.accumulate) for every pass of a window --
+        # bucket_ready then launches nothing and finish() waits for nothing; the model releases it on the window's last micro-step
+        # and hands over the whole flat buffer, the summed gradient, in the ranges the held pass was refused (last_held: the
+        # bucket boundaries of a normal step): one exchange per window.  all_reduce_max is never held.
+        self.hold = False
+        self.held, self.last_held = [], []
 
     def bucket_ready(self, lo, hi):
         """flat[lo:hi] holds final local gradients: start summing it across ranks."""
         if not self.active or hi <= lo:
+            return
+        if self.hold:
+            self.held.append((lo, hi))
             return
         self.buckets.append((lo, hi))
         view = self.flat[lo:hi]
@@ -39,7 +48,10 @@ class GradAllReduce:
             self.pending.append(dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
 
     def finish(self):
-        """Wait for all buckets; returns the world size (the caller scales by 1/world)."""
+        """Wait for all buckets; returns the world size (the caller scales by 1/world).  Held: nothing was launched, nothing to wait for."""
+        if self.hold:
+            self.last_held, self.held = self.held, []
+            return self.world
         if self.cuda and self.active:
             torch.cuda.current_stream().wait_stream(self.stream)
         for w in self.pending:

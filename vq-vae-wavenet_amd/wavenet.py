@@ -125,6 +125,9 @@ class WaveNet:
     scope = 'decoder'      # name scope of the WaveNet's variables (named_parameters)
     _recon_gen = None      # the device generator of reconstruct's uniforms
     _jitter_step = None    # the step whose forward pass is running inside train_step (_forward_step); None: a pass outside a step (forward(), evaluate, ...)
+    _accumulate = 1        # micro-batches per optimiser step (accumulate; 1 = off: the step is what it always was)
+    _accum_k = 0           # micro-steps already in the open window (accum_index)
+    _acc = None            # the window's running sum, one more n_flat buffer: made at the first accumulating step
 
     def __init__(self, model_cfg, wavenet_cfg, num_speakers, device='cuda', seed=0):
         self.m, self.w = model_cfg, wavenet_cfg
@@ -1213,6 +1216,58 @@ class WaveNet:
             self._gn['steps'] = 0                     # what a step measured before clipping was switched off is not reported later
         self._clip_norm = value
 
+    @property
+    def accumulate(self):
+        """Micro-batches per optimiser step.  1: off, train_step is what it was without this attribute.  N > 1: a
+        window of N consecutive train_step calls sums their gradients in fp32, in call order (fl(fl(g0 + g1) + g2) ...), and the
+        N-th call takes ONE Adam + EMA step on the sum scaled by 1 / (N * world): with inference-mode BatchNorm and losses that
+        are means over rows, the step of one batch of N * B rows up to fp32 summation order.  global_step advances on that call
+        alone; under data parallel the window's one gradient exchange runs there too.  Every micro-step stays a whole guarded
+        pass.  Settable at a window boundary (accum_index == 0); refused together with codebook_ema; not part of state_dict."""
+        return self._accumulate
+
+    @accumulate.setter
+    def accumulate(self, value):
+        if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+            raise ValueError('accumulate must be an integer >= 1 (got %r)' % (value,))
+        if self._accum_k != 0:
+            raise ValueError('accumulate cannot change while a window is open (%d of %d micro-steps done)' % (self._accum_k, self._accumulate))
+        if value > 1 and getattr(self, '_codebook_ema', 0.0) > 0.0:
+            raise ValueError("accumulate > 1 with codebook_ema is not supported: the codebook's own update per micro-batch has no rule yet")
+        self._accumulate = value
+
+    @property
+    def accum_index(self):
+        """Micro-steps already in the open window: 0 at a window boundary (read-only)."""
+        return self._accum_k
+
+    def _commit_window(self, ws, world, guard):
+        """The tail of _commit with accumulate = N > 1, micro-step k of the window.  k = 0: acc = grad, a guarded copy (the
+        accumulator is never assumed clean); 0 < k < N - 1: acc += grad; k = N - 1: grad = acc + grad -- acc is NOT written --
+        then the window's gradient exchange and the optimiser on grad.  A voided micro-step (skip set when the kernels run)
+        therefore changes neither acc nor a parameter: what the replay of an older window still needs stays, and grad is
+        scratch that every pass rewrites."""
+        N, k = self._accumulate, self._accum_k
+        if self._acc is None:
+            self._acc = torch.empty(self.n_flat, device=self.dev)
+        if k < N - 1:
+            if k == 0:
+                K.grad_accumulate(self._acc, self.grad, **guard)
+            else:
+                K.grad_accumulate(self._acc, self.grad, acc=self._acc, **guard)
+            self._accum_k = k + 1
+            return
+        K.grad_accumulate(self.grad, self.grad, acc=self._acc, **guard)
+        gs = self.grad_sync
+        if gs is not None:      # the one exchange of the window: the whole flat buffer in the buckets of a normal step (the ranges
+            gs.hold = False     # this pass's backward was refused: they tile [0, n_flat) once), not overlapped with a backward pass
+            for lo, hi in gs.last_held:
+                gs.bucket_ready(lo, hi)
+            world = gs.finish()
+        self._front_step(ws, **guard)
+        self.apply_gradients(1.0 / (N * world), **guard)
+        self._accum_k = 0
+
     def _grad_norm_state(self):
         """Chunk table and output buffer of the norm pass, made at the first clipped step.  Segment k is the k-th trainable
         variable under its reference name: the flat elements its view (_named) covers, a column block of a grouped kernel
@@ -1283,7 +1338,9 @@ class WaveNet:
         lengths (None: the step as it always was): B row lengths, a host sequence or a CPU tensor of positive multiples of
         _length_unit(), at most T.  The loss is then the mean cross-entropy over the sum(lengths) positions t < lengths[b], and
         every gradient is that loss's: the stack is causal, so a gradient seed that is zero from lengths[b] on makes whatever
-        the row holds behind it immaterial.  Checked before anything is launched; no host synchronisation is added."""
+        the row holds behind it immaterial.  Checked before anything is launched; no host synchronisation is added.
+        With accumulate = N > 1 a call is one micro-step of a window of N: the passes and the guard are those of a step, the
+        optimiser (and global_step) moves on the N-th call alone (accumulate, _commit_window)."""
         lens = self._train_lengths('train_step', lengths, *x.shape) if lengths is not None else None
         if self.defer_guard and self.x3_guard and on_forward is None:
             return self._train_step_deferred(x, spk, lens)
@@ -1308,6 +1365,8 @@ class WaveNet:
         """One attempt at training step `step`: forward, the hooks (called with the workspace between the passes; None: skipped),
         backward, the end of the gradient exchange.  Returns (workspace, data-parallel world size)."""
         self._in_step = True           # (forward() settles deferred steps for every other caller)
+        if self.grad_sync is not None:          # no bucket leaves during a window's passes: _commit_window exchanges the sum
+            self.grad_sync.hold = self._accumulate > 1
         try:
             ws = self._forward_step(x, spk, step, lengths)
             for hook in hooks:
@@ -1320,11 +1379,14 @@ class WaveNet:
 
     def _commit(self, ws, world, scales=True, skip=None):
         """Keep the attempt: the next step's plane scales (scales=False: the pass measured none), what the front updates by itself,
-        Adam + EMA.  skip: device int32, non-zero when the kernels run = each of the three changes nothing."""
+        Adam + EMA.  skip: device int32, non-zero when the kernels run = each of the three changes nothing.  With accumulate > 1
+        the part behind the scales is _commit_window's: the optimiser runs on a window's last micro-step alone."""
         guard = {} if skip is None else {'skip': skip}      # (an unguarded step names none: the calls are what they were)
         if scales:     # the planes written inside the kernels: max-abs * scale in [2^12, 2^13), 8x headroom
             n0 = self.SL['G']
             K.f16x3_update_scales(self.x3_amax[n0:], self.x3_scale[n0:], target_exp=13, **guard)
+        if self._accumulate > 1:
+            return self._commit_window(ws, world, guard)
         self._front_step(ws, **guard)
         self.apply_gradients(1.0 / world, **guard)
 
@@ -1367,6 +1429,8 @@ class WaveNet:
         was flagged, it and step k + 1 (enqueued behind it, voided by the sticky guard) have changed nothing: the guard is
         cleared, the step counter rewound, step k is repeated on the fp32 engine and step k + 1 is run again -- the same steps are repeated as in the immediate mode
         and the state agrees with it as closely as two runs of that mode do (tests/test_model_gpu.py::test_deferred_guard_matches_immediate: tolerances).
+        With accumulate > 1 an entry also records its place k in its window, and k is rewound with the step counter: a voided
+        micro-step has changed neither the accumulator nor anything else (_commit_window).
         Callers keep x / spk unchanged until the step is resolved (finish_steps(), or the next-but-one train_step) and call
         finish_steps() before reading what a step left behind (losses, gradients, parameters; state_dict() / encode() do)."""
         t_host = time.perf_counter()
@@ -1378,7 +1442,7 @@ class WaveNet:
         if self.grad_sync is not None and self.grad_sync.active:
             self.grad_sync.all_reduce_max(self.x3_flag)       # every rank takes the same branch
         torch.maximum(self.x3_void, self.x3_flag, out=self.x3_void)
-        gs0 = self.global_step
+        gs0, k0 = self.global_step, self._accum_k
         self._commit(ws, world, skip=self.x3_void)
         if self._void_host is None:
             self._void_host = torch.zeros(4, dtype=torch.int32).pin_memory()
@@ -1387,7 +1451,7 @@ class WaveNet:
         self._void_host[slot:slot + 1].copy_(self.x3_void, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        self._pending.append({'x': x, 'spk': spk, 'gs0': gs0, 'ev': ev, 'slot': slot, 'lengths': lengths})      # (lengths: the step's own, for its repeat)
+        self._pending.append({'x': x, 'spk': spk, 'gs0': gs0, 'k': k0, 'ev': ev, 'slot': slot, 'lengths': lengths})      # (lengths: the step's own, for its repeat; k: its place in its window)
         self.host_enqueue_ms = (time.perf_counter() - t_host) * 1e3        # what the host needs to enqueue one step (it must stay below the step's GPU time)
         while len(self._pending) > 1:
             self._resolve_oldest()
@@ -1404,6 +1468,7 @@ class WaveNet:
         self.x3_void.zero_()
         self.global_step = p['gs0']
         for n, q in enumerate(pend):
+            self._accum_k = q['k']      # (the oldest's rewinds the window; the others' are what its replay leaves)
             self._train_step_now(q['x'], q['spk'], known_flagged=(n == 0), lengths=q['lengths'])
 
     def finish_steps(self):
@@ -1474,6 +1539,9 @@ class WaveNet:
         self._ws.clear()
 
     def state_dict(self):
+        if self._accum_k != 0:      # (the accumulator is no part of a checkpoint)
+            raise ValueError('state_dict: a window of accumulate = %d is open (%d micro-steps done): a checkpoint is taken at a window boundary'
+                             % (self._accumulate, self._accum_k))
         self.finish_steps()
         # x3_scale: the guarded engine's power-of-two plane scales (measured by the last step, used by the next): with them a
         # resumed run continues exactly as the uninterrupted one would (without them its first step runs on the start-up scales)
@@ -1488,3 +1556,4 @@ class WaveNet:
         if 'x3_scale' in sd and tuple(sd['x3_scale'].shape) == tuple(self.x3_scale.shape):      # (absent in round-2 files)
             self.x3_scale.copy_(sd['x3_scale'].to(self.dev))
         self.global_step = int(sd['global_step'])
+        self._accum_k = 0           # (a loaded state starts a window)
