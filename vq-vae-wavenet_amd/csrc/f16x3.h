@@ -159,7 +159,28 @@ __device__ __forceinline__ void f16x3_mainloop(f32x16 (&acc)[MR][2], char* smem,
     constexpr int NSTG_ = DEPTH + 2, STGB = X3Shape<MR>::STAGE_BYTES, BOFF = MR * 2 * 1024;      // (a stage is requested DEPTH + 1 steps before it is read)
     const int l31 = lane & 31, lhi = lane >> 5;
     const int KCA = (TAB ? g.wks : g.ks) * g.Cin / 8, KCB = g.Cin / 8, spt = g.Cin / 16;   // spt: K steps per tap
-    const int nsteps = TAB ? g.sn : g.ks * spt;
+    // Live taps (not TAB): a tap whose shift puts every one of the block's 256 columns before its batch row (causal padding; behind
+    // it for an input gradient) multiplies nothing but zeros -- all of its Cin / 16 steps would request zeros, read them and issue
+    // their MFMAs.  Such taps are left out of the K range: `live` lists the others in ascending order, four bits each (ks <= 8 is
+    // checked by the callers), and a step looks its tap up by shifting that scalar.  The result keeps its bits: the accumulators
+    // start at +0, the weights are finite, and a skipped step would have added products with an all-zero B fragment -- zeros of
+    // either sign, which leave an accumulator that is not -0 as it is (and none ever becomes -0: that takes two -0 addends).  The
+    // steps that remain run in the order they had.  The tap with shift 0 is always live: n_live >= 1, nsteps stays even with spt.
+    unsigned live = 0;
+    int n_live = 0;
+    if constexpr (!TAB) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int sh = (g.ks - 1 - j) * g.dilation * (g.dir < 0 ? -1 : 1);
+            const bool on = j < g.ks && g.t0 + 255 - sh >= 0 && g.t0 - sh < g.T;
+            live |= on ? (unsigned)j << (4 * n_live) : 0u;
+            n_live += on ? 1 : 0;
+        }
+        // (block-uniform by construction; said so, the list and its length sit in scalar registers whatever unit built them)
+        live = __builtin_amdgcn_readfirstlane(live);
+        n_live = __builtin_amdgcn_readfirstlane(n_live);
+    }
+    const int nsteps = TAB ? g.sn : n_live * spt;
     // Weight resource `ra` (below): NP planes -- the requests past the last K step must fall outside the resource, and read as zero,
     // in bf16 mode too, where the weight planes end after ONE plane.
     // One buffer resource per activation plane, based at the contraction's first chunk: 32-bit offsets then only span the
@@ -198,11 +219,11 @@ __device__ __forceinline__ void f16x3_mainloop(f32x16 (&acc)[MR][2], char* smem,
 #if VQW_X3_TAP_MINOR
         // K order: channel chunk outermost, taps innermost -- the taps of one chunk read the same activation lines a few rows apart,
         // in consecutive steps instead of Cin / 16 steps apart, while they are still in L2 (HBM reads of the gate conv d=8: 172 -> 104 MB)
-        const int ji = TAB ? s / spt : s % g.ks, kc = TAB ? (s - ji * spt) * 2 : (s / g.ks) * 2;
+        const int ji = TAB ? s / spt : s % n_live, kc = TAB ? (s - ji * spt) * 2 : (s / n_live) * 2;
 #else
         const int ji = s / spt, kc = (s - ji * spt) * 2;
 #endif
-        const int j = TAB ? g.tj0 + g.tjstep * ji : ji;
+        const int j = TAB ? g.tj0 + g.tjstep * ji : (int)((live >> ((4 * ji) & 31)) & 7u);      // (past the last step: any tap, into a slot nobody reads)
         const int e_ = TAB ? j - g.toff : 0;
         const int shift = TAB ? g.tsgn * (e_ >> 1) : (g.ks - 1 - j) * g.dilation * (g.dir < 0 ? -1 : 1);   // rows before / behind the batch row read as zero
         const int kcx = TAB ? kc + (g.ts2d ? (e_ & 1) * KCB : 0) : kc;
@@ -382,9 +403,6 @@ __device__ __forceinline__ void x3_pin_guard(float& gmax, bool& gbad) {
 }
 #ifndef VQW_X3_EPI_DEPTH
 #define VQW_X3_EPI_DEPTH 2
-#endif
-#ifndef VQW_X3_GATE_EPI_DEPTH
-#define VQW_X3_GATE_EPI_DEPTH 0      // the gate conv's 24 operand registers per group: depth 1 and 2 spill (40-240 bytes of scratch per lane)
 #endif
 constexpr int EPI_DEPTH = VQW_X3_EPI_DEPTH;
 

@@ -32,42 +32,87 @@ __global__ __launch_bounds__(256, MR == 8 ? 1 : 2) void gate_f16x3_kernel(const 
     // ---- epilogue: + bias + upsampled condition (add_condition, wavenet_ops.py:93-101), tanh(filter) * sigmoid(gate).
     // With one block per CU nothing overlaps it, so it is kept lean: one 64-bit row offset per four channels, 32-bit
     // offsets inside, v_rcp_f32 instead of IEEE divisions (1 ulp; the quotients feed tanh/sigmoid values in [-1, 1]).
-    // Groups go through x3_epilogue_pipeline like the other epilogues', but at depth 0 (VQW_X3_GATE_EPI_DEPTH): its operands
-    // are L2 hits and prefetching them costs more registers than the kernel has.
+    // The per-row constants, bias[c] + cond[b][c][frame], depend on neither the lane's column nor the group: requested group by
+    // group (24 loads of L2 hits, every lane of a half-wave the same word, and a wait before anything is computed) they cost
+    // 2 MR exposed round trips per block and 24 registers.  LDSC, the 128-row blocks: the block's four waves fetch them ONCE
+    // instead, into the ring the main loop has left: HB channels x the frames its 256 columns touch -- at most 8 (32 | ratio), all
+    // 8 slots are filled, the frames past the block's last one with that one's values -- as table[frame - first frame][block row],
+    // the sums formed as the groups form them (bias + cond, an absent operand masked to +0: x3_masked), so that a group reads four
+    // rows of one frame with one 16-byte LDS read that every lane of a half-wave shares.  The 256-row blocks keep the requests:
+    // with every register taken they need 20-50 bytes more scratch per lane for the table's reads than for the loads.
+    constexpr bool LDSC = MR == 4;
     const bool hb = d.bias != nullptr, hc = d.cond != nullptr;
     const float* bp = hb ? d.bias : reinterpret_cast<const float*>(d.wp);      // absent operands read a valid dummy address
     const float* cb = hc ? d.cond + (size_t)b * d.cond_bstride : reinterpret_cast<const float*>(d.wp);
     const int tcol = t0 + 64 * wv + l31;
-    const int tz0 = (t0 + 64 * wv) / a.ratio, tz1 = (t0 + 64 * wv + 32) / a.ratio;   // 32 | ratio: one frame per tile row
-    const float winv = inv_scales(d.w_scale_inv, d.x_scale, d.w_scale);
     const unsigned mb = x3_present(hb), mc = x3_present(hc);
-    struct Ops { float bf[4], bg[4], f0[4], f1[4], g0[4], g1[4]; };
+    const int tzb = t0 / a.ratio, tzl = (t0 + 255) / a.ratio;      // the block's first and last frame
+    // (32 | ratio: one frame per tile row; without a condition ratio is 1 and every frame index is masked to 0)
+    const int tz0 = (t0 + 64 * wv) / a.ratio, tz1 = (t0 + 64 * wv + 32) / a.ratio;
+    const int fz0 = x3_masked(tz0 - tzb, mc), fz1 = x3_masked(tz1 - tzb, mc);
+    const float* table = reinterpret_cast<const float*>(smem);
+    if constexpr (LDSC) {
+        __syncthreads();      // every wave has drained its own requests (f16x3_mainloop) and read its last fragments: the ring is dead
+        constexpr int NV = HB * 8 / 256;
+        float tb[NV], tc[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const int idx = tid + 256 * v, row = idx >> 3, f = idx & 7;      // (frames innermost: a channel's frames are one 32-byte read)
+            const int c = (row < HH ? 0 : R - HH) + HH * mt + row;
+            const int tz = tzb + f < tzl ? tzb + f : tzl;
+            tb[v] = bp[x3_masked(c, mb)];
+            tc[v] = cb[x3_masked(c * d.cond_T + tz, mc)];
+        }
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const int idx = tid + 256 * v, row = idx >> 3, f = idx & 7;
+            reinterpret_cast<float*>(smem)[f * HB + row] = x3_masked(tb[v], mb) + x3_masked(tc[v], mc);
+        }
+        __syncthreads();
+    }
+    const float winv = inv_scales(d.w_scale_inv, d.x_scale, d.w_scale);
     // STEP: the outputs the training step asks for (sigmoid + gated planes) are known at compile time -- no branch around any
     // store; every other combination takes the same body with its block-uniform conditions tested at run time
     auto epilogue = [&](auto step_c) {
         constexpr bool STEP = decltype(step_c)::value;
         const bool s0 = STEP ? false : d.save0 != nullptr, s1 = STEP ? true : d.save1 != nullptr;
         const bool w0 = STEP ? false : d.out0 != nullptr, wp_ = STEP ? true : d.out_planes != nullptr;
+        struct OpsMem { float bf[4], bg[4], f0[4], f1[4], g0[4], g1[4]; };
+        struct OpsLds { float4 f0, f1, g0, g1; };
+        typedef std::conditional_t<LDSC, OpsLds, OpsMem> Ops;
         auto request = [&](int g, Ops& o) {
             const int i = g >> 2, v4 = g & 3;
-            const int c0 = HH * mt + 32 * i + 8 * v4 + 4 * lhi;          // first of this lane's four channels
+            const int r0 = 32 * i + 8 * v4 + 4 * lhi;          // first of this lane's four filter rows of the block; gate rows: + HH
+            if constexpr (LDSC) {
+                o.f0 = *reinterpret_cast<const float4*>(table + fz0 * HB + r0); o.f1 = *reinterpret_cast<const float4*>(table + fz1 * HB + r0);
+                o.g0 = *reinterpret_cast<const float4*>(table + fz0 * HB + HH + r0); o.g1 = *reinterpret_cast<const float4*>(table + fz1 * HB + HH + r0);
+            } else {
+                const int c0 = HH * mt + r0;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                o.bf[e] = bp[x3_masked(c0 + e, mb)]; o.bg[e] = bp[x3_masked(R + c0 + e, mb)];
-                const int cf = (c0 + e) * d.cond_T, cg = (R + c0 + e) * d.cond_T;
-                o.f0[e] = cb[x3_masked(cf + tz0, mc)]; o.f1[e] = cb[x3_masked(cf + tz1, mc)];
-                o.g0[e] = cb[x3_masked(cg + tz0, mc)]; o.g1[e] = cb[x3_masked(cg + tz1, mc)];
+                for (int e = 0; e < 4; ++e) {
+                    o.bf[e] = bp[x3_masked(c0 + e, mb)]; o.bg[e] = bp[x3_masked(R + c0 + e, mb)];
+                    const int cf = (c0 + e) * d.cond_T, cg = (R + c0 + e) * d.cond_T;
+                    o.f0[e] = cb[x3_masked(cf + tz0, mc)]; o.f1[e] = cb[x3_masked(cf + tz1, mc)];
+                    o.g0[e] = cb[x3_masked(cg + tz0, mc)]; o.g1[e] = cb[x3_masked(cg + tz1, mc)];
+                }
             }
         };
         auto finish = [&](int g, const Ops& o) {
             const int i = g >> 2, v4 = g & 3;
-            const int c0 = HH * mt + 32 * i + 8 * v4 + 4 * lhi;
+            const int c0 = HH * mt + 32 * i + 8 * v4 + 4 * lhi;          // first of this lane's four channels
             float addf[4][2], addg[4][2];
+            if constexpr (LDSC) {
+                const float tf[2][4] = {{o.f0.x, o.f0.y, o.f0.z, o.f0.w}, {o.f1.x, o.f1.y, o.f1.z, o.f1.w}};
+                const float tg[2][4] = {{o.g0.x, o.g0.y, o.g0.z, o.g0.w}, {o.g1.x, o.g1.y, o.g1.z, o.g1.w}};
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float bfv = o.bf[e], bgv = o.bg[e], f0 = o.f0[e], f1 = o.f1[e], g0 = o.g0[e], g1 = o.g1[e];
-                addf[e][0] = x3_masked(bfv, mb) + x3_masked(f0, mc); addf[e][1] = x3_masked(bfv, mb) + x3_masked(f1, mc);
-                addg[e][0] = x3_masked(bgv, mb) + x3_masked(g0, mc); addg[e][1] = x3_masked(bgv, mb) + x3_masked(g1, mc);
+                for (int e = 0; e < 4; ++e) { addf[e][0] = tf[0][e]; addf[e][1] = tf[1][e]; addg[e][0] = tg[0][e]; addg[e][1] = tg[1][e]; }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float bfv = o.bf[e], bgv = o.bg[e], f0 = o.f0[e], f1 = o.f1[e], g0 = o.g0[e], g1 = o.g1[e];
+                    addf[e][0] = x3_masked(bfv, mb) + x3_masked(f0, mc); addf[e][1] = x3_masked(bfv, mb) + x3_masked(f1, mc);
+                    addg[e][0] = x3_masked(bgv, mb) + x3_masked(g0, mc); addg[e][1] = x3_masked(bgv, mb) + x3_masked(g1, mc);
+                }
             }
             const size_t off = ((size_t)b * R + c0) * T + tcol;
             float* po = (w0 ? d.out0 : d.save1) + off;
@@ -98,7 +143,9 @@ __global__ __launch_bounds__(256, MR == 8 ? 1 : 2) void gate_f16x3_kernel(const 
                                      n0 + 64 * wv + 32 * j + l31, lhi, gq[j]);
             }
         };
-        x3_epilogue_pipeline<MR * 2, VQW_X3_GATE_EPI_DEPTH, Ops>(request, finish);
+        // (a group is requested, computed and stored before the next one: the 256-row blocks have no registers for a second
+        // group of 24 loads -- 40-240 bytes of scratch per lane at depth 1 and 2 --, and the table's reads are LDS reads)
+        x3_epilogue_pipeline<MR * 2, 0, Ops>(request, finish);
     };
     if (!d.out0 && !d.save0 && d.save1 && d.out_planes) epilogue(std::true_type{});
     else epilogue(std::false_type{});
