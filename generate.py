@@ -24,6 +24,12 @@ prefills the prior with the utterance's first N codes (encode_codes), samples `-
 with the audio generator prefilled with the utterance's first N x 64 samples (which the wav holds verbatim); the codes file
 holds all N + frames codes.  With `-seed`, uniforms are drawn for the generated samples / codes only.
 
+`-audio_list FILE` (one wav path per line; `-data_root` for relative paths) converts every utterance of the list to every
+speaker with the wide generator (generator.WideGenerator): every (utterance, speaker) pair is one row, `-rows` (1..1024, default
+256) rows per batch, batches formed by length (generator.plan_rows); each utterance is encoded on its own as `-audio` does it, and
+with `-seed` row i draws from a generator seeded with (seed, i), so a row's audio does not depend on `-rows`.  Writes
+`<out_dir>/<step>_<basename>_<speaker>.wav`.  Not with `-audio`, `-prior`, a prompt or `-teacher_forced`.
+
 `-teacher_forced` with `-audio` and `-speakers`: no autoregression.  The decoder is given the TRUE past of the utterance and
 every sample is decided from its logits in one pass (VQVAE.reconstruct), by `-mode` with `-seed / -temperature / -top_k /
 -top_p`: what the decoder predicts when nothing it predicted is fed back.  The utterance is trimmed to a multiple of the
@@ -68,7 +74,14 @@ def main():
                         help='with -prior and -audio: continue the first N codes (N x 64 samples) of the utterance')
     parser.add_argument('-teacher_forced', action='store_true',
                         help='with -audio: the decoder\'s one-pass reconstruction given the true past (<step>_<speaker>_teacher.wav)')
+    parser.add_argument('-audio_list', dest='audio_list', help='text file of wav paths, one per line: convert every utterance '
+                        'to every speaker with the wide generator (<step>_<basename>_<speaker>.wav)')
+    parser.add_argument('-rows', default=256, type=int, help='with -audio_list: (utterance, speaker) rows per batch, 1..1024')
+    parser.add_argument('-data_root', default='', help='with -audio_list: directory the list\'s relative paths start from')
+    parser.add_argument('-out_dir', default=None, help='with -audio_list: where the wavs go (default: beside the weights)')
     args = parser.parse_args()
+    if args.audio_list is not None:
+        return convert_list(args, parser)
     if args.teacher_forced and (args.prior_path is not None or args.prompt_samples or args.prompt_frames):
         parser.error('-teacher_forced reconstructs -audio in one pass: not with -prior, -prompt_samples or -prompt_frames')
     if args.teacher_forced and args.audio_path is None:
@@ -148,6 +161,129 @@ def main():
             s = 'no_speaker' if args.speakers[i] == 'None' else args.speakers[i]
             wavfile.write(save_path + '/%d_%s.wav' % (gs, s), 16000, out[j])
             print('wrote', save_path + '/%d_%s.wav' % (gs, s))
+
+
+def read_list(path, data_root):
+    """The wav paths of an -audio_list file: one per line, blank lines and lines starting with # skipped, relative paths
+    taken from data_root."""
+    with open(path) as f:
+        names = [ln.strip() for ln in f]
+    return [n if os.path.isabs(n) else os.path.join(data_root, n) for n in names if n and not n.startswith('#')]
+
+
+def row_uniforms(seed, row, n):
+    """The n uniforms of row `row` (list order, then speaker order): seeded by (seed, row) alone, so a row's draw does not
+    depend on -rows, on the batch it lands in or on the sharding; unseeded without -seed."""
+    if seed is None:
+        return torch.rand(n)
+    s = int(np.random.SeedSequence([seed, row]).generate_state(1, np.uint64)[0] >> np.uint64(1))
+    return torch.rand(n, generator=torch.Generator().manual_seed(s))
+
+
+def convert_list(args, parser):
+    """-audio_list: every (utterance, speaker) pair is one row of the wide generator (generator.WideGenerator).  Each
+    utterance is read, trimmed and encoded on its own, exactly as -audio does it, so no utterance sees another's padding;
+    rows are batched by length (generator.plan_rows), a batch's conditions are padded to its longest row by repeating the
+    last frame, and each row's audio is cut to its own length."""
+    for flag, on in (('-audio', args.audio_path is not None), ('-prior', args.prior_path is not None),
+                     ('-prompt_samples', args.prompt_samples != 0), ('-prompt_frames', args.prompt_frames != 0),
+                     ('-teacher_forced', args.teacher_forced)):
+        if on:
+            parser.error('-audio_list converts whole utterances with the wide generator: not with %s' % flag)
+    if not 1 <= args.rows <= 1024:
+        parser.error('-rows %d must be in 1..1024' % args.rows)
+    if not args.speakers:
+        parser.error('-audio_list needs -speakers')
+    if not args.restore_path:
+        parser.error('-audio_list needs -restore')
+    if args.mode not in ('sample', 'greedy'):
+        raise NotImplementedError('decode mode %s not implemented' % args.mode)
+    if not os.path.isfile(args.audio_list):
+        parser.error('-audio_list %s: no such file' % args.audio_list)
+    paths = read_list(args.audio_list, args.data_root)
+    if not paths:
+        parser.error('-audio_list %s names no utterance' % args.audio_list)
+    wavs = []
+    for p in paths:
+        if not os.path.isfile(p):
+            parser.error('-audio_list: %s: no such file' % p)
+        wav = read_wav(p)
+        if len(wav) == 0:
+            parser.error('-audio_list: %s is shorter than 512 samples' % p)
+        wavs.append(wav)
+
+    pkg = importlib.import_module('vq-vae-wavenet_amd')
+    try:        # every row gets the same settings; checked before anything is loaded or built
+        pkg.generator.sampling_settings(1, args.mode, args.temperature, args.top_k, args.top_p)
+    except ValueError as e:
+        parser.error(str(e))
+    world = int(os.environ.get('WORLD_SIZE', '1'))
+    rank = int(os.environ.get('RANK', '0'))
+    local = int(os.environ.get('LOCAL_RANK', '0')) % max(torch.cuda.device_count(), 1)   # no collective: ranks may share a GPU
+    torch.cuda.set_device(local)
+    dev = torch.device('cuda', local)
+    gs = int(args.restore_path.split('-')[-1].split('.')[0])
+    from scipy.io import wavfile
+    num_speakers, ids = speaker_ids(args, pkg)
+    parameters, wavenet_parameters = pkg.model.load_configs(args.parameter_path)
+    model = load_vqvae(args, pkg, parameters, wavenet_parameters, num_speakers, dev)
+    out_dir = args.out_dir or args.restore_path.split('/weights')[0]
+    os.makedirs(out_dir, exist_ok=True)
+
+    ns = len(ids)
+    all_rows = [(u, k) for u in range(len(wavs)) for k in range(ns)]          # list order, then speaker order
+    mine = list(range(rank, len(all_rows), world))                            # rows sharded over ranks: no collective
+    if not mine:
+        return
+    spk_all = torch.tensor(ids, dtype=torch.int64, device=dev)
+    cond, ratio, seen = {}, None, set()
+    for u in sorted({all_rows[r][0] for r in mine}):
+        x = torch.from_numpy(wavs[u]).to(dev).unsqueeze(0).contiguous()
+        enc = model.encode(x, spk_all)                 # this utterance alone with its speakers: what -audio computes
+        r_u = len(wavs[u]) // enc.shape[2]
+        if ratio is None:
+            ratio = r_u
+        assert r_u == ratio and enc.shape[2] * ratio == len(wavs[u])
+        for r in mine:
+            if all_rows[r][0] == u:
+                cond[r] = enc[all_rows[r][1]].clone()
+        if len(wavs[u]) not in seen:                   # the encode workspace is cached by (B, T): a list has many lengths
+            seen.add(len(wavs[u]))
+            model.free_workspaces()
+    lengths = [len(wavs[all_rows[r][0]]) for r in mine]
+    batches, padded = pkg.generator.plan_rows(lengths, args.rows)
+    print('%d rows in %d batches of at most %d; %d of %d row-steps are padding'
+          % (len(mine), len(batches), args.rows, padded, padded + sum(lengths)))
+    gens = {}
+    for batch in batches:
+        nb, n = len(batch), max(lengths[j] for j in batch)
+        Tz = n // ratio
+        enc = torch.empty(nb, model.Cc, Tz, device=dev)
+        for i, j in enumerate(batch):
+            c = cond[mine[j]]
+            enc[i, :, :c.shape[1]] = c
+            enc[i, :, c.shape[1]:] = c[:, -1:]         # padded by repeating the last frame
+        uniforms = None
+        if args.mode == 'sample':
+            uniforms = torch.zeros(nb, n)
+            for i, j in enumerate(batch):
+                uniforms[i, :lengths[j]] = row_uniforms(args.seed, mine[j], lengths[j])
+            uniforms = uniforms.to(dev)
+        if nb not in gens:
+            gens[nb] = pkg.generator.WideGenerator(model, batch=nb)
+        gen = gens[nb]
+        gen.reset()
+        audio, _ = gen.generate(enc, n, mode=args.mode, ratio=ratio, uniforms=uniforms, temperature=args.temperature,
+                                top_k=args.top_k, top_p=args.top_p)
+        audio = audio.cpu().numpy()
+        for i, j in enumerate(batch):
+            u, k = all_rows[mine[j]]
+            s = 'no_speaker' if args.speakers[k] == 'None' else args.speakers[k]
+            name = os.path.join(out_dir, '%d_%s_%s.wav' % (gs, os.path.splitext(os.path.basename(paths[u]))[0], s))
+            wavfile.write(name, 16000, audio[i, :lengths[j]])
+            print('wrote', name)
+    for gen in gens.values():
+        gen.close()
 
 
 def read_wav(path, multiple=512):

@@ -550,6 +550,28 @@ int vqw_ar_decode_destroy(vqw_ar_decoder* h);
  * where it does not run (VQW_AR_PERSISTENT=0, an unsupported shape). */
 int vqw_ar_prior_create(vqw_ar_decoder** out, const vqw_ar_weights* w, int batch, int channels_per_workgroup, int n_codes);
 
+/* ---- The wide generator (csrc/ar_wide.hip): the same generation for 1..1024 rows per handle, for converting many utterances
+ * at once.  Every layer of a step is a GEMM over all rows on the exact-fp32 MFMA, so the weights are read once per step and
+ * not once per row; a step is one linear chain of ordinary launches replayed from a hipGraph (no kernel waits for another).
+ * vqw_ar_decode_* stays the right choice for one to eight rows.
+ * Arguments, layouts (encoding [B][Cc][Tz], uniforms / audio / indices [B][n_steps], probs_last [B][Q]), modes and the
+ * meaning of `sampling` (a HOST array of `batch` entries, or NULL) are those of vqw_ar_decode_run_sampled_async; `audio` is
+ * required.  A run continues from the handle's state; _reset zeroes it; _run_async enqueues on the handle's own stream
+ * behind the work already in `s`, _wait blocks the host until the run is done.  A row's indices, audio and probs_last do
+ * not depend on the batch: not on `batch`, not on the row's position, not on the other rows' inputs or settings; a run cut
+ * into several equals the single run bit for bit.  The condition is projected for a window of 4 frames at a time
+ * (4 * (2 R n_layers + S) * batch floats), refreshed in stream order.  There is no prefill.
+ * Shapes: R, S, Q multiples of 32, Q <= 1024; Cc a multiple of 16; 1 <= pre_k <= 64; 2 <= kernel_size <= VQW_MAX_TAPS;
+ * 1 <= batch <= 1024; anything else is an error that names the value. */
+typedef struct vqw_ar_wide vqw_ar_wide;
+int vqw_ar_wide_create(vqw_ar_wide** out, const vqw_ar_weights* w, int batch);
+int vqw_ar_wide_reset(vqw_ar_wide* h, vqw_stream_t s);
+int vqw_ar_wide_run_async(vqw_ar_wide* h, const float* encoding, int Tz, int ratio, int n_steps, int mode,
+                          const float* uniforms, const vqw_ar_sampling* sampling, float* audio, int32_t* indices,
+                          float* probs_last, vqw_stream_t s);
+int vqw_ar_wide_wait(vqw_ar_wide* h);
+int vqw_ar_wide_destroy(vqw_ar_wide* h);
+
 /* ---- The latent prior's input stage (csrc/prior.hip).  net0[b][:][t] = b_pre + sum_{j<pre_k} w_pre[j][codes[b][t-pre_k+j]][:]
  * (the causal conv of one_hot(shift_right(codes)); codes outside [0, k) contribute nothing); labels (may be NULL) := codes.
  * codes int32 [B][T], w_pre [pre_k][k][R], b_pre [R], net0 [B][R][T]. */

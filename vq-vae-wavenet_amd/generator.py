@@ -78,6 +78,121 @@ def pick_layout(batch, R, cus):
     return rows, (cpb or 0)
 
 
+def plan_rows(lengths, max_rows):
+    """Group rows of the given lengths into batches for WideGenerator: rows sorted by length (ties by index), cut into
+    consecutive batches of at most max_rows.  A batch runs for its longest row, so the steps its shorter rows are carried
+    along for are padding.  Returns (batches, padded): batches a list of lists of row indices, the batches and the rows of
+    each in ascending length; padded the sum over batches of (longest - own) over its rows.  Pure: no GPU, no model."""
+    if isinstance(max_rows, bool) or not isinstance(max_rows, int) or max_rows < 1:
+        raise ValueError('max_rows must be an integer >= 1 (got %r)' % (max_rows,))
+    lengths = [int(n) for n in lengths]
+    if any(n < 0 for n in lengths):
+        raise ValueError('lengths must be >= 0')
+    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
+    batches = [order[i:i + max_rows] for i in range(0, len(order), max_rows)]
+    padded = sum(lengths[b[-1]] - lengths[i] for b in batches for i in b)
+    return batches, padded
+
+
+def _weights_of(model, keep):
+    """vqw_ar_weights over the model's LIVE variables; the ctypes arrays it points to are appended to `keep`."""
+    P = model.P
+    nl, R, S = model.L, model.R, model.S
+    w = L.ArWeights()
+    w.n_layers, w.kernel_size, w.R, w.S, w.Q, w.Cc, w.pre_k = nl, model.ks, R, S, model.Q, model.Cc, model.pre_k
+    dil = (C.c_int32 * nl)(*model.dil)
+    w.dilations = dil
+    f4 = 4  # bytes per float
+
+    def arr(ptrs):
+        a = (C.c_void_p * nl)(*ptrs)
+        return a
+    gw = arr([P['gated_w'][l].data_ptr() for l in range(nl)])
+    gb = arr([P['gated_b'][l].data_ptr() for l in range(nl)])
+    cw = arr([P['cond_w'].data_ptr() + l * 2 * R * f4 for l in range(nl)])
+    ow = arr([P['out_w'][l].data_ptr() for l in range(nl)])
+    ob = arr([P['out_b'][l].data_ptr() for l in range(nl)])
+    keep.extend([dil, gw, gb, cw, ow, ob])
+    w.gated_w, w.gated_b, w.cond_w, w.out_w, w.out_b = gw, gb, cw, ow, ob
+    w.cond_ld, w.out_ld = model.Mall, S + R
+    w.pre_w, w.pre_b = P['pre_w'].data_ptr(), P['pre_b'].data_ptr()
+    w.skip0_w, w.skip0_b = P['skip0_w'].data_ptr(), P['skip0_b'].data_ptr()
+    w.post1_w, w.post1_b = P['post1_w'].data_ptr(), P['post1_b'].data_ptr()
+    w.post1_cond_w, w.post1_cond_ld = P['cond_w'].data_ptr() + nl * 2 * R * f4, model.Mall
+    w.post2_w, w.post2_b = P['post2_w'].data_ptr(), P['post2_b'].data_ptr()
+    return w
+
+
+class WideGenerator:
+    """Generation for many rows at once (1..1024 per handle) on vqw_ar_wide_* (csrc/ar_wide.hip): every layer of a step is
+    a GEMM over all rows on the exact-fp32 MFMA.  Built for throughput: converting a list of utterances (generate.py
+    -audio_list); FastGenerator stays the right choice for one to eight rows.  Uses the model's LIVE variables, like
+    FastGenerator.  A row's indices, audio and probabilities do not depend on the batch it ran in (its size, the row's
+    position, the other rows), and a run cut into several generate() calls equals the single run bit for bit.
+
+    There is no prefill: to continue a prompt, use FastGenerator.prefill + generate."""
+
+    def __init__(self, model, batch):
+        self.model, self.B = model, batch
+        self._keep = []
+        self._w = _weights_of(model, self._keep)
+        self._h = None
+        h = C.c_void_p()
+        L.check(L.lib().vqw_ar_wide_create(C.byref(h), C.byref(self._w), batch))
+        self._h = h
+
+    def reset(self):
+        """sess.run(wavenet.init_ops) (generate.py:105): empty queues, the next sample is step 0."""
+        L.check(L.lib().vqw_ar_wide_reset(self._h, L.stream()))
+
+    def generate(self, encoding, n_steps, mode='greedy', uniforms=None, ratio=None, return_probs=False,
+                 temperature=1.0, top_k=0, top_p=1.0):
+        """encoding [B][Cc][Tz] (model.encode); continues from the current queue state, sample i of the run using condition
+        frame (steps so far + i) // ratio (the last frame beyond it).  temperature / top_k / top_p (mode 'sample' only;
+        scalars or one value per row): see sampling_settings and vqw_ar_sampling in include/vqwave.h.
+        Returns (audio [B][n] float32, indices [B][n] int32[, probs of the last step [B][Q]: the distribution sampled])."""
+        if mode not in ('greedy', 'sample'):
+            raise NotImplementedError('decode mode %s not implemented' % mode)   # utils.py:46
+        settings = sampling_settings(self.B, mode, temperature, top_k, top_p)
+        if (not isinstance(encoding, torch.Tensor) or encoding.dtype != torch.float32 or encoding.dim() != 3
+                or encoding.shape[0] != self.B or encoding.shape[1] != self.model.Cc):
+            raise ValueError('encoding must be a float32 [%d][%d][Tz] tensor' % (self.B, self.model.Cc))
+        B, _, Tz = encoding.shape
+        encoding = encoding.contiguous()
+        L.require_cuda(encoding, uniforms)
+        dev = encoding.device
+        if mode == 'sample':
+            if uniforms is None:
+                uniforms = torch.rand(B, n_steps, device=dev)        # np.random.rand in utils.py:22
+            if uniforms.shape != (B, n_steps) or uniforms.dtype != torch.float32:
+                raise ValueError('uniforms must be float32 [B][n_steps]')
+        audio = torch.empty(B, n_steps, device=dev)
+        idx = torch.empty(B, n_steps, dtype=torch.int32, device=dev)
+        probs = torch.empty(B, self.model.Q, device=dev) if return_probs else None
+        rows = None
+        if settings is not None:
+            rows = (L.ArSampling * B)()
+            for j, (t, k, p) in enumerate(settings):
+                rows[j].temperature, rows[j].top_k, rows[j].top_p = t, min(k, 0x7fffffff), p
+        lib = L.lib()
+        L.check(lib.vqw_ar_wide_run_async(self._h, L.ptr(encoding), Tz, ratio or 64, n_steps, 0 if mode == 'greedy' else 1,
+                                          L.ptr(uniforms) if mode == 'sample' else None, rows, L.ptr(audio), L.ptr(idx),
+                                          L.ptr(probs), L.stream()))
+        L.check(lib.vqw_ar_wide_wait(self._h))
+        return (audio, idx, probs) if return_probs else (audio, idx)
+
+    def close(self):
+        if getattr(self, '_h', None) is not None:
+            L.lib().vqw_ar_wide_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class FastGenerator:
     def __init__(self, model, batch):
         """Uses the model's LIVE variables (call model.use_ema_weights() first to mirror
