@@ -14,6 +14,12 @@ With `-prior <prior.pt> -frames N` no input utterance is needed: N VQ codes per 
 (prior.py, trained by train_prior.py), decoded through the VQ-VAE's codebook (condition_from_codes) and its fast WaveNet
 generator, and written as `<dir>/<step>_<speaker>_prior.wav` (N x 64 samples) plus `prior_codes_<step>_<speaker>.npy`.
 
+`-prior ... -count M` (M > 1) samples a corpus: M takes per speaker, every (speaker k, take m) pair one row i = k M + m of the wide
+generators (generator.WidePriorGenerator for the codes, generator.WideGenerator for the audio), `-rows` (1..1024, default 256)
+rows per batch; writes `<dir>/<step>_<speaker>_prior_<m>.wav` and `prior_codes_<step>_<speaker>_<m>.npy`.  With `-seed` row i
+draws its code uniforms from child 0 of the seed sequence (seed, i) and its audio uniforms from child 1, so a row's codes and
+audio do not depend on `-rows`.  Not with `-prompt_frames` (the wide generators have no prefill).
+
 `-temperature / -top_k / -top_p` temper and truncate the audio sampling, `-prior_temperature / -prior_top_k / -prior_top_p`
 the code sampling of `-prior` (mode sample only; the same values for every speaker; the defaults are plain sampling).
 
@@ -76,12 +82,24 @@ def main():
                         help='with -audio: the decoder\'s one-pass reconstruction given the true past (<step>_<speaker>_teacher.wav)')
     parser.add_argument('-audio_list', dest='audio_list', help='text file of wav paths, one per line: convert every utterance '
                         'to every speaker with the wide generator (<step>_<basename>_<speaker>.wav)')
-    parser.add_argument('-rows', default=256, type=int, help='with -audio_list: (utterance, speaker) rows per batch, 1..1024')
+    parser.add_argument('-rows', default=256, type=int, help='with -audio_list: (utterance, speaker) rows per batch, 1..1024; '
+                        'with -prior -count M: (speaker, take) rows per batch')
+    parser.add_argument('-count', default=1, type=int, help='with -prior: takes per speaker; above 1 both stages run on the wide '
+                        'generators (<step>_<speaker>_prior_<m>.wav, prior_codes_<step>_<speaker>_<m>.npy)')
     parser.add_argument('-data_root', default='', help='with -audio_list: directory the list\'s relative paths start from')
     parser.add_argument('-out_dir', default=None, help='with -audio_list: where the wavs go (default: beside the weights)')
     args = parser.parse_args()
     if args.audio_list is not None:
         return convert_list(args, parser)
+    if args.count < 1:
+        parser.error('-count %d must be >= 1' % args.count)
+    if args.count > 1:
+        if args.prior_path is None:
+            parser.error('-count %d needs -prior: takes are sampled from the latent prior' % args.count)
+        if args.prompt_frames:
+            parser.error('-count %d with -prompt_frames: the wide generators have no prefill' % args.count)
+        if not 1 <= args.rows <= 1024:
+            parser.error('-rows %d must be in 1..1024' % args.rows)
     if args.teacher_forced and (args.prior_path is not None or args.prompt_samples or args.prompt_frames):
         parser.error('-teacher_forced reconstructs -audio in one pass: not with -prior, -prompt_samples or -prompt_frames')
     if args.teacher_forced and args.audio_path is None:
@@ -171,12 +189,16 @@ def read_list(path, data_root):
     return [n if os.path.isabs(n) else os.path.join(data_root, n) for n in names if n and not n.startswith('#')]
 
 
-def row_uniforms(seed, row, n):
+def row_uniforms(seed, row, n, stage=None):
     """The n uniforms of row `row` (list order, then speaker order): seeded by (seed, row) alone, so a row's draw does not
-    depend on -rows, on the batch it lands in or on the sharding; unseeded without -seed."""
+    depend on -rows, on the batch it lands in or on the sharding; unseeded without -seed.  stage (-prior -count: 0 the codes,
+    1 the audio): a row's stages draw from generators of their own, seeded by child `stage` of the row's seed sequence
+    (SeedSequence([seed, row], spawn_key=(stage,)) = .spawn(...)[stage]).  Not SeedSequence([seed, row, stage]): numpy pads
+    the entropy with zeros, so [seed, row, 0] IS [seed, row] and stage 0 would repeat the unstaged draw."""
     if seed is None:
         return torch.rand(n)
-    s = int(np.random.SeedSequence([seed, row]).generate_state(1, np.uint64)[0] >> np.uint64(1))
+    ss = np.random.SeedSequence([seed, row], spawn_key=() if stage is None else (stage,))
+    s = int(ss.generate_state(1, np.uint64)[0] >> np.uint64(1))
     return torch.rand(n, generator=torch.Generator().manual_seed(s))
 
 
@@ -386,6 +408,8 @@ def generate_from_prior(args, pkg, gs, rank, world, dev, parser):
     prior.load_state_dict(torch.load(args.prior_path, map_location='cpu', weights_only=True))
     prior.use_ema_weights()
     save_path = args.restore_path.split('/weights')[0]
+    if args.count > 1:
+        return prior_corpus(args, pkg, gs, rank, world, dev, ids, model, prior, save_path)
     mine = list(range(rank, len(ids), world))
     n, length = args.frames, args.frames * 64
     g = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
@@ -423,6 +447,47 @@ def generate_from_prior(args, pkg, gs, rank, world, dev, parser):
             wavfile.write(save_path + '/%d_%s_prior.wav' % (gs, s), 16000, audio[j])
             np.save(save_path + '/prior_codes_%d_%s.npy' % (gs, s), codes[j])
             print('wrote', save_path + '/%d_%s_prior.wav' % (gs, s))
+
+
+def prior_corpus(args, pkg, gs, rank, world, dev, ids, model, prior, save_path):
+    """-prior -count M: every (speaker k, take m) pair is row i = k M + m of both wide generators.  All rows have the same
+    length, so the rows (sharded over ranks as convert_list shards them) are cut into consecutive batches of at most -rows:
+    WidePriorGenerator draws the codes, condition_from_codes makes the condition, WideGenerator decodes it from reset.  With
+    -seed row i draws its code uniforms from row_uniforms' stage 0 and its audio uniforms from stage 1; with the generators'
+    batch independence a row's codes and audio depend neither on -rows nor on the sharding."""
+    from scipy.io import wavfile
+    M = args.count
+    n, length = args.frames, args.frames * 64
+    all_rows = [(k, m) for k in range(len(ids)) for m in range(M)]            # speaker order, then take
+    mine = list(range(rank, len(all_rows), world))                            # rows sharded over ranks: no collective
+    pgens, gens = {}, {}
+    for b0 in range(0, len(mine), args.rows):
+        batch = mine[b0:b0 + args.rows]
+        nb = len(batch)
+        spk = torch.tensor([ids[all_rows[i][0]] for i in batch], dtype=torch.int64, device=dev)
+        u_codes = u_audio = None
+        if args.mode == 'sample':
+            u_codes = torch.stack([row_uniforms(args.seed, i, n, stage=0) for i in batch]).to(dev)
+            u_audio = torch.stack([row_uniforms(args.seed, i, length, stage=1) for i in batch]).to(dev)
+        if nb not in gens:
+            pgens[nb] = pkg.generator.WidePriorGenerator(prior, batch=nb)
+            gens[nb] = pkg.generator.WideGenerator(model, batch=nb)
+        pgens[nb].reset()
+        codes = pgens[nb].sample(n, spk, mode=args.mode, uniforms=u_codes, temperature=args.prior_temperature,
+                                 top_k=args.prior_top_k, top_p=args.prior_top_p)
+        cond = model.condition_from_codes(codes, spk)
+        gens[nb].reset()
+        audio, _ = gens[nb].generate(cond, length, mode=args.mode, ratio=64, uniforms=u_audio, temperature=args.temperature,
+                                     top_k=args.top_k, top_p=args.top_p)
+        audio, codes = audio.cpu().numpy(), codes.cpu().numpy()
+        for j, i in enumerate(batch):
+            k, m = all_rows[i]
+            s = 'no_speaker' if args.speakers[k] == 'None' else args.speakers[k]
+            wavfile.write(save_path + '/%d_%s_prior_%d.wav' % (gs, s, m), 16000, audio[j])
+            np.save(save_path + '/prior_codes_%d_%s_%d.npy' % (gs, s, m), codes[j])
+            print('wrote', save_path + '/%d_%s_prior_%d.wav' % (gs, s, m))
+    for gen in list(pgens.values()) + list(gens.values()):
+        gen.close()
 
 
 if __name__ == '__main__':

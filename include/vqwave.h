@@ -571,6 +571,19 @@ int vqw_ar_wide_run_async(vqw_ar_wide* h, const float* encoding, int Tz, int rat
                           float* probs_last, vqw_stream_t s);
 int vqw_ar_wide_wait(vqw_ar_wide* h);
 int vqw_ar_wide_destroy(vqw_ar_wide* h);
+/* Code-input mode of the wide generator (the latent prior over VQ codes, prior.py): the same step with a discrete input, for
+ * sampling many code rows at once.  w->Q is the number of codes n_codes (a multiple of 32 in 32..1024, equal to `n_codes`) and
+ * w->pre_w is read as [pre_k][n_codes][R] (prior/preprocess/kernel).  The handle reads the caller's weights IN PLACE, W_pre
+ * included, as every wide handle does: they must stay allocated and unchanged while the handle lives (vqw_ar_prior_create
+ * keeps its own copy of W_pre; this call does not).  The input stage gathers rows of W_pre by the previous codes:
+ *   cur[o] = b_pre[o] + sum_{j < pre_k} W_pre[j][c(t - (pre_k - j))][o], one fp32 add per tap in ascending j, a step before 0
+ * adding nothing (reset = no code yet: a zero one-hot, not code 0); the sampled index is the next input (no mu-law).  With
+ * supplied uniforms u > cdf[n_codes-1] gives n_codes, which is no code: it is clamped to n_codes - 1.
+ * vqw_ar_wide_reset / _run_async / _wait / _destroy serve the handle.  On a code handle `audio` must be NULL and `indices`
+ * (the codes) is required; probs_last is [B][n_codes]; mode, uniforms and sampling mean what they mean above, and so do the
+ * promises about batch independence and chunked runs.  The prior's condition is the speaker tiled over frames of 64 code
+ * steps: encoding [B][Cc][Tz] with ratio = 64.  Errors name the offending value and come before the first device call. */
+int vqw_ar_wide_prior_create(vqw_ar_wide** out, const vqw_ar_weights* w, int batch, int n_codes);
 
 /* ---- The latent prior's input stage (csrc/prior.hip).  net0[b][:][t] = b_pre + sum_{j<pre_k} w_pre[j][codes[b][t-pre_k+j]][:]
  * (the causal conv of one_hot(shift_right(codes)); codes outside [0, k) contribute nothing); labels (may be NULL) := codes.

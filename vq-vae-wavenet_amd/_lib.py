@@ -177,6 +177,7 @@ SIGNATURES = {
     'vqw_ar_decode_destroy': (_i, [_fp]),
     'vqw_ar_prior_create': (_i, [C.POINTER(_fp), C.POINTER(ArWeights), _i, _i, _i]),
     'vqw_ar_wide_create': (_i, [C.POINTER(_fp), C.POINTER(ArWeights), _i]),
+    'vqw_ar_wide_prior_create': (_i, [C.POINTER(_fp), C.POINTER(ArWeights), _i, _i]),
     'vqw_ar_wide_reset': (_i, [_fp, _fp]),
     'vqw_ar_wide_run_async': (_i, [_fp, _fp, _i, _i, _i, _i, _fp, C.POINTER(ArSampling), _fp, _fp, _fp, _fp]),
     'vqw_ar_wide_wait': (_i, [_fp]),

@@ -20,6 +20,11 @@
 // A step is one linear chain of ordinary launches on the handle's private stream, captured once into a hipGraph: no kernel
 // waits for another, nothing spins.  The step counter lives on the device; the last workgroup of the sampling kernel to
 // finish (a ticket, never waited for) advances it.
+//
+// Code-input mode (vqw_ar_wide_prior_create: the latent prior over VQ codes).  The prior is the same stack, so the GEMMs,
+// the rings, the condition window and the step graph are shared; only the two ends of a step differ: arw_pre_code_kernel
+// gathers rows of W_pre by the previous codes where arw_pre_kernel convolves a mu-law sample, and arw_sample_kernel<true>
+// feeds the drawn index itself back as the next input.
 #include <string.h>
 
 #include <vector>
@@ -99,6 +104,60 @@ __global__ __launch_bounds__(256) void arw_pre_kernel(const WideState* st, const
         float acc = pre_b[o];
         for (int j = 0; j < pre_k; ++j) acc = fmaf(pre_w[(size_t)j * R + o], taps[j][tb], acc);
         cur[(size_t)o * B + b] = acc;
+    }
+}
+
+// Code-input mode (the latent prior, prior.py): the input of step t is the code drawn at step t - 1, a one-hot, so the
+// preprocess conv is a gather:  cur[o][b] = b_pre[o] + sum_j W_pre[j][c_j][o],  c_j = row b's code at step t - (pre_k - j),
+// W_pre [pre_k][n_codes][R].  Start from the bias, taps in ascending j, one fp32 add per tap that has a code; a step before
+// 0 has none (a zero one-hot, not code 0) and adds nothing.  xhist / prev hold code + 1 as floats (exact up to 1024), 0 =
+// no code: the persistent kernel's convention, so the zeros of a reset mean "no code yet".  Same block and grid as
+// arw_pre_kernel.  A gathered row segment (32 channels) is 128 contiguous bytes: the gather runs with the lanes along the
+// channel, two rows per wave; cur has b innermost: the store runs with the lanes along b (256-byte segments); the tile is
+// transposed through LDS in between (vqw_prior_input_fwd does the same for the training pass).  Rows of 33 floats (banks are
+// dword address mod 32 per 32-lane half): a half of the gather phase writes one row, 33 r + o with o along the lanes, 32
+// consecutive banks; a half of the store phase reads one column, 33 r + o with r along the lanes, bank (r + o) mod 32, every
+// bank once: neither phase conflicts.  Rows past B - 1 are neither gathered nor stored.
+__global__ __launch_bounds__(256) void arw_pre_code_kernel(const WideState* st, const float* prev, float* xhist, const float* pre_w,
+                                                           const float* pre_b, float* cur, int pre_k, int n_codes, int R, int B) {
+    __shared__ int codes[64][64];       // [tap][row]: the code, or -1 for none
+    __shared__ float tile[64][33];      // [row][channel]
+    const int tb = threadIdx.x & 63, tg = threadIdx.x >> 6;
+    const int b = blockIdx.x * 64 + tb;
+    const int step = st->step;
+    if (b < B) {
+        for (int j = tg; j < pre_k; j += 4) {               // tap j meets the input of step t - (pre_k-1-j)
+            float v;
+            if (j == pre_k - 1) {
+                v = prev[b];                                 // the code drawn at the previous step (+ 1)
+                if (blockIdx.y == 0) xhist[(size_t)(step % pre_k) * B + b] = v;   // the slot of t - pre_k: no tap reads it
+            } else {
+                const int tau = step - (pre_k - 1 - j);
+                v = xhist[(size_t)(((tau % pre_k) + pre_k) % pre_k) * B + b];
+            }
+            const int code = (int)v - 1;
+            codes[j][tb] = code < n_codes ? code : -1;
+        }
+    }
+    __syncthreads();
+    const int o = threadIdx.x & 31, rh = (threadIdx.x >> 5) & 1;
+    const float* wcol = pre_w + blockIdx.y * 32 + o;
+    const float bias = pre_b[blockIdx.y * 32 + o];
+    for (int i = 0; i < 8; ++i) {
+        const int r = 8 * i + 2 * tg + rh;                  // wave tg gathers rows 2 tg, 2 tg + 1 of every group of 8
+        if (blockIdx.x * 64 + r >= B) continue;
+        float acc = bias;
+        for (int j = 0; j < pre_k; ++j) {
+            const int code = codes[j][r];
+            if (code >= 0) acc += wcol[((size_t)j * n_codes + code) * R];
+        }
+        tile[r][o] = acc;
+    }
+    __syncthreads();
+    if (b >= B) return;
+    for (int i = 0; i < 8; ++i) {
+        const int oc = tg * 8 + i;
+        cur[(size_t)(blockIdx.y * 32 + oc) * B + b] = tile[tb][oc];
     }
 }
 
@@ -237,6 +296,10 @@ __global__ void arw_window_kernel(WideState* st, const float* __restrict__ enc, 
 // softmax (wavenet.py:171) + utils.decode (utils.py:30-46) + mu_law_decode_np of ONE row per workgroup; logits [Q][B].
 // A default row: softmax with the maximum subtracted, a sequential fp32 cumsum, searchsorted left; greedy = the lowest index
 // among the maxima.  A row with settings: ar_sample_truncated, by wave 0.
+// CODE (the latent prior's handles): the same decision over Q = n_codes classes; the index itself is the next input
+// (prev = idx + 1, arw_pre_code_kernel), there is no mu-law decode, and audio (NULL on these handles) is skipped.  u above
+// the last cdf value gives Q, which is no code: it is clamped to Q - 1.
+template <bool CODE>
 __global__ __launch_bounds__(256) void arw_sample_kernel(WideState* st, const float* logits, const ArSampleRow* samp, float* prev,
                                                          int B, int Q) {
     __shared__ float sp[1024];
@@ -309,10 +372,17 @@ __global__ __launch_bounds__(256) void arw_sample_kernel(WideState* st, const fl
         }
     }
     if (tid == 0) {
-        const float dec = vqw_mu_decode((float)idx);
-        st->audio[(size_t)b * n_steps + i_out] = dec;
-        if (st->indices) st->indices[(size_t)b * n_steps + i_out] = idx;
-        prev[b] = dec;
+        if constexpr (CODE) {
+            idx = min(idx, Q - 1);
+            if (st->audio) st->audio[(size_t)b * n_steps + i_out] = (float)idx;
+            st->indices[(size_t)b * n_steps + i_out] = idx;
+            prev[b] = (float)(idx + 1);
+        } else {
+            const float dec = vqw_mu_decode((float)idx);
+            st->audio[(size_t)b * n_steps + i_out] = dec;
+            if (st->indices) st->indices[(size_t)b * n_steps + i_out] = idx;
+            prev[b] = dec;
+        }
         // every workgroup read `step` before it took its ticket, so the last one may advance it; nobody waits for this
         if (atomicAdd(&st->ticket, 1) == B - 1) {
             st->ticket = 0;
@@ -328,6 +398,7 @@ struct vqw_ar_wide {
     std::vector<int> dil;
     std::vector<const float*> gated_w, gated_b, cond_w, out_w, out_b;
     int B = 0, Mall = 0;
+    int n_codes = 0;                 // > 0: code-input mode (vqw_ar_wide_prior_create): w.pre_w is [pre_k][n_codes][R], read in place
     long long steps = 0;             // host mirror of the device step counter (reset: 0; a run adds n_steps)
     WideState* st = nullptr;
     ArSampleRow* samp = nullptr;     // device [B]
@@ -368,8 +439,12 @@ void launch_gemm(const WideArgs& a, int rows, int frames, hipStream_t st) {
 int launch_step(vqw_ar_wide* h, hipStream_t st) {
     const vqw_ar_weights& w = h->w;
     const int B = h->B, R = w.R, S = w.S, Q = w.Q, ks = w.kernel_size, L = w.n_layers;
-    hipLaunchKernelGGL(arw_pre_kernel, dim3(vqw_cdiv(B, 64), R / 32), dim3(256), 0, st, h->st, h->prev, h->xhist, w.pre_w, w.pre_b,
-                       h->cur, w.pre_k, R, B);
+    if (h->n_codes)
+        hipLaunchKernelGGL(arw_pre_code_kernel, dim3(vqw_cdiv(B, 64), R / 32), dim3(256), 0, st, h->st, h->prev, h->xhist, w.pre_w,
+                           w.pre_b, h->cur, w.pre_k, h->n_codes, R, B);
+    else
+        hipLaunchKernelGGL(arw_pre_kernel, dim3(vqw_cdiv(B, 64), R / 32), dim3(256), 0, st, h->st, h->prev, h->xhist, w.pre_w, w.pre_b,
+                           h->cur, w.pre_k, R, B);
     // skip = linear(current)  (wavenet.py:127-128)
     WideArgs a = base_args(h);
     a.seg[0] = WideSeg{w.skip0_w, h->cur, 0, 0};
@@ -406,7 +481,10 @@ int launch_step(vqw_ar_wide* h, hipStream_t st) {
     a.seg[0] = WideSeg{w.post2_w, h->h, 0, 0};
     a.nseg = 1; a.K = S; a.ldw = Q; a.N = Q; a.in_relu = 1; a.bias = w.post2_b; a.out = h->logits;
     launch_gemm<MODE_PLAIN>(a, Q, 1, st);
-    hipLaunchKernelGGL(arw_sample_kernel, dim3(B), dim3(256), 0, st, h->st, h->logits, h->samp, h->prev, B, Q);
+    if (h->n_codes)
+        hipLaunchKernelGGL(arw_sample_kernel<true>, dim3(B), dim3(256), 0, st, h->st, h->logits, h->samp, h->prev, B, Q);
+    else
+        hipLaunchKernelGGL(arw_sample_kernel<false>, dim3(B), dim3(256), 0, st, h->st, h->logits, h->samp, h->prev, B, Q);
     VQW_LAUNCH_CHECK("vqw_ar_wide_run(step)");
     return 0;
 }
@@ -442,25 +520,31 @@ void free_all(vqw_ar_wide* h) {
     delete h;
 }
 
-}  // namespace
-
-extern "C" int vqw_ar_wide_create(vqw_ar_wide** out, const vqw_ar_weights* w, int batch) {
-    VQW_CHECK(out && w, "vqw_ar_wide_create: null pointer");
-    VQW_CHECK(batch >= 1 && batch <= WIDE_MAXB, "vqw_ar_wide_create: batch=%d must be in 1..%d", batch, WIDE_MAXB);
-    VQW_CHECK(w->n_layers >= 1, "vqw_ar_wide_create: n_layers=%d must be >= 1", (int)w->n_layers);
-    VQW_CHECK(w->kernel_size >= 2 && w->kernel_size <= VQW_MAX_TAPS, "vqw_ar_wide_create: kernel_size=%d must be in 2..%d",
-              (int)w->kernel_size, VQW_MAX_TAPS);
-    VQW_CHECK(w->R >= 32 && w->R % 32 == 0, "vqw_ar_wide_create: R=%d must be a positive multiple of 32", (int)w->R);
-    VQW_CHECK(w->S >= 32 && w->S % 32 == 0, "vqw_ar_wide_create: S=%d must be a positive multiple of 32", (int)w->S);
-    VQW_CHECK(w->Q >= 32 && w->Q % 32 == 0 && w->Q <= 1024, "vqw_ar_wide_create: Q=%d must be a multiple of 32 in 32..1024", (int)w->Q);
-    VQW_CHECK(w->Cc >= 16 && w->Cc % 16 == 0, "vqw_ar_wide_create: Cc=%d must be a positive multiple of 16", (int)w->Cc);
-    VQW_CHECK(w->pre_k >= 1 && w->pre_k <= 64, "vqw_ar_wide_create: pre_k=%d must be in 1..64", (int)w->pre_k);
-    VQW_CHECK(w->dilations && w->gated_w && w->gated_b && w->cond_w && w->out_w && w->out_b, "vqw_ar_wide_create: null weight table");
+// both kinds of handle; fn names the entry point in the messages.  n_codes > 0: code-input mode.  Every check comes before
+// the first device call.
+int wide_create(const char* fn, vqw_ar_wide** out, const vqw_ar_weights* w, int batch, int n_codes) {
+#define ARW_CHECK(cond, fmt, ...) VQW_CHECK(cond, "%s: " fmt, fn, ##__VA_ARGS__)
+    ARW_CHECK(out && w, "null pointer");
+    ARW_CHECK(batch >= 1 && batch <= WIDE_MAXB, "batch=%d must be in 1..%d", batch, WIDE_MAXB);
+    if (n_codes >= 0) {
+        ARW_CHECK(n_codes >= 32 && n_codes % 32 == 0 && n_codes <= 1024, "n_codes=%d must be a multiple of 32 in 32..1024", n_codes);
+        ARW_CHECK(w->Q == n_codes, "n_codes=%d must equal w->Q=%d", n_codes, (int)w->Q);
+    }
+    ARW_CHECK(w->n_layers >= 1, "n_layers=%d must be >= 1", (int)w->n_layers);
+    ARW_CHECK(w->kernel_size >= 2 && w->kernel_size <= VQW_MAX_TAPS, "kernel_size=%d must be in 2..%d", (int)w->kernel_size, VQW_MAX_TAPS);
+    ARW_CHECK(w->R >= 32 && w->R % 32 == 0, "R=%d must be a positive multiple of 32", (int)w->R);
+    ARW_CHECK(w->S >= 32 && w->S % 32 == 0, "S=%d must be a positive multiple of 32", (int)w->S);
+    ARW_CHECK(w->Q >= 32 && w->Q % 32 == 0 && w->Q <= 1024, "Q=%d must be a multiple of 32 in 32..1024", (int)w->Q);
+    ARW_CHECK(w->Cc >= 16 && w->Cc % 16 == 0, "Cc=%d must be a positive multiple of 16", (int)w->Cc);
+    ARW_CHECK(w->pre_k >= 1 && w->pre_k <= 64, "pre_k=%d must be in 1..64", (int)w->pre_k);
+    ARW_CHECK(w->dilations && w->gated_w && w->gated_b && w->cond_w && w->out_w && w->out_b, "null weight table");
     for (int l = 0; l < w->n_layers; ++l)
-        VQW_CHECK(w->dilations[l] >= 1, "vqw_ar_wide_create: dilation %d of layer %d must be >= 1", (int)w->dilations[l], l);
+        ARW_CHECK(w->dilations[l] >= 1, "dilation %d of layer %d must be >= 1", (int)w->dilations[l], l);
+#undef ARW_CHECK
     vqw_ar_wide* h = new vqw_ar_wide();
     h->w = *w;
     h->B = batch;
+    h->n_codes = n_codes > 0 ? n_codes : 0;
     const int L = w->n_layers;
     h->Mall = L * 2 * w->R + w->S;
     h->dil.assign(w->dilations, w->dilations + L);
@@ -475,7 +559,7 @@ extern "C" int vqw_ar_wide_create(vqw_ar_wide** out, const vqw_ar_weights* w, in
 #define ARW_ALLOC(ptr, bytes)                                                          \
     do {                                                                               \
         hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));                            \
-        if (e_ != hipSuccess) { free_all(h); return vqw_set_error("vqw_ar_wide_create: hipMalloc of %zu bytes failed: %s", (size_t)(bytes), hipGetErrorString(e_)); } \
+        if (e_ != hipSuccess) { free_all(h); return vqw_set_error("%s: hipMalloc of %zu bytes failed: %s", fn, (size_t)(bytes), hipGetErrorString(e_)); } \
     } while (0)
     const size_t B = batch, f4 = sizeof(float);
     ARW_ALLOC(h->st, sizeof(WideState));
@@ -494,13 +578,23 @@ extern "C" int vqw_ar_wide_create(vqw_ar_wide** out, const vqw_ar_weights* w, in
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming) != hipSuccess) {
         free_all(h);
-        return vqw_set_error("vqw_ar_wide_create: stream/event creation failed");
+        return vqw_set_error("%s: stream/event creation failed", fn);
     }
     const int rc = vqw_ar_wide_reset(h, nullptr);
     if (rc) { free_all(h); return rc; }
     HIPC(hipStreamSynchronize(nullptr));
     *out = h;
     return 0;
+}
+
+}  // namespace
+
+extern "C" int vqw_ar_wide_create(vqw_ar_wide** out, const vqw_ar_weights* w, int batch) {
+    return wide_create("vqw_ar_wide_create", out, w, batch, -1);
+}
+
+extern "C" int vqw_ar_wide_prior_create(vqw_ar_wide** out, const vqw_ar_weights* w, int batch, int n_codes) {
+    return wide_create("vqw_ar_wide_prior_create", out, w, batch, n_codes);
 }
 
 extern "C" int vqw_ar_wide_reset(vqw_ar_wide* h, vqw_stream_t s) {
@@ -531,7 +625,13 @@ extern "C" int vqw_ar_wide_wait(vqw_ar_wide* h) {
 extern "C" int vqw_ar_wide_run_async(vqw_ar_wide* h, const float* encoding, int Tz, int ratio, int n_steps, int mode,
                                      const float* uniforms, const vqw_ar_sampling* sampling, float* audio, int32_t* indices,
                                      float* probs_last, vqw_stream_t s) {
-    VQW_CHECK(h && encoding && audio, "vqw_ar_wide_run: null pointer");
+    VQW_CHECK(h && encoding, "vqw_ar_wide_run: null pointer");
+    if (h->n_codes) {
+        VQW_CHECK(!audio, "vqw_ar_wide_run: audio must be NULL on a code handle (vqw_ar_wide_prior_create): it draws codes, not samples");
+        VQW_CHECK(indices, "vqw_ar_wide_run: indices is NULL: a code handle (vqw_ar_wide_prior_create) needs it for the codes");
+    } else {
+        VQW_CHECK(audio, "vqw_ar_wide_run: null pointer");
+    }
     VQW_CHECK(Tz > 0 && ratio > 0 && n_steps > 0, "vqw_ar_wide_run: bad Tz/ratio/n_steps (%d, %d, %d)", Tz, ratio, n_steps);
     VQW_CHECK(mode == 0 || (mode == 1 && uniforms), "vqw_ar_wide_run: mode must be 0 (greedy) or 1 (sample, needs uniforms)");
     VQW_CHECK(h->steps + n_steps <= 0x7fffffffLL, "vqw_ar_wide_run: the step counter would pass 2^31 - 1");

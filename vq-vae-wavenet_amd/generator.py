@@ -193,6 +193,79 @@ class WideGenerator:
             pass
 
 
+class WidePriorGenerator:
+    """Samples VQ codes from a prior.LatentPrior for many rows at once (1..1024 per handle) on the wide generator's code-input
+    mode (vqw_ar_wide_prior_create, csrc/ar_wide.hip): the input stage gathers rows of W_pre by the previous codes, the drawn
+    index is the next input, everything between is WideGenerator's step.  Built for throughput: a corpus sampled from the
+    prior (generate.py -prior -count M); PriorGenerator stays the right choice for one to eight rows.  Uses the prior's LIVE
+    variables, read in place (prior.use_ema_weights() first for the EMA shadows).  A row's codes and probabilities do not
+    depend on the batch it ran in, and a run cut into several sample() calls equals the single run bit for bit.
+
+    There is no prefill: to continue a prompt of codes, use PriorGenerator.prefill + sample."""
+
+    def __init__(self, prior, batch):
+        self.model, self.B = prior, batch
+        self._t = 0
+        self._keep = []
+        self._w = _weights_of(prior, self._keep)
+        self._h = None
+        h = C.c_void_p()
+        L.check(L.lib().vqw_ar_wide_prior_create(C.byref(h), C.byref(self._w), batch, prior.Q))
+        self._h = h
+
+    def reset(self):
+        """Empty history ("no code yet": a zero one-hot, not code 0); the next sample is step 0."""
+        L.check(L.lib().vqw_ar_wide_reset(self._h, L.stream()))
+        self._t = 0
+
+    def sample(self, n_frames, spk, mode='greedy', uniforms=None, return_probs=False, temperature=1.0, top_k=0, top_p=1.0):
+        """n_frames codes per row, continuing from the current state.  spk int64 [B] on the GPU.  mode 'greedy' (argmax) or
+        'sample' (searchsorted(cumsum(p), u) with uniforms [B][n_frames], drawn here when None; u above the cdf's last
+        value gives the last code), tempered / truncated by temperature, top_k, top_p as in WideGenerator.generate.
+        Returns codes int32 [B][n_frames][, probabilities of the last step [B][k]: the distribution sampled]."""
+        if mode not in ('greedy', 'sample'):
+            raise NotImplementedError('decode mode %s not implemented' % mode)
+        settings = sampling_settings(self.B, mode, temperature, top_k, top_p)
+        if spk.numel() != self.B:
+            raise ValueError('%d speaker ids for a batch of %d' % (spk.numel(), self.B))
+        B = self.B
+        ratio = 64                                     # code steps per condition frame (prior.CODES_PER_FRAME)
+        Tz = -(-(self._t + n_frames) // ratio)
+        cond = self.model.speaker_condition(spk.contiguous(), Tz)
+        L.require_cuda(cond, uniforms)
+        dev = cond.device
+        if mode == 'sample':
+            if uniforms is None:
+                uniforms = torch.rand(B, n_frames, device=dev)
+            if uniforms.shape != (B, n_frames) or uniforms.dtype != torch.float32:
+                raise ValueError('uniforms must be float32 [B][n_frames]')
+        idx = torch.empty(B, n_frames, dtype=torch.int32, device=dev)
+        probs = torch.empty(B, self.model.Q, device=dev) if return_probs else None
+        rows = None
+        if settings is not None:
+            rows = (L.ArSampling * B)()
+            for j, (t, k, p) in enumerate(settings):
+                rows[j].temperature, rows[j].top_k, rows[j].top_p = t, min(k, 0x7fffffff), p
+        lib = L.lib()
+        L.check(lib.vqw_ar_wide_run_async(self._h, L.ptr(cond), Tz, ratio, n_frames, 0 if mode == 'greedy' else 1,
+                                          L.ptr(uniforms) if mode == 'sample' else None, rows, None, L.ptr(idx),
+                                          L.ptr(probs), L.stream()))
+        L.check(lib.vqw_ar_wide_wait(self._h))
+        self._t += n_frames
+        return (idx, probs) if return_probs else idx
+
+    def close(self):
+        if getattr(self, '_h', None) is not None:
+            L.lib().vqw_ar_wide_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class FastGenerator:
     def __init__(self, model, batch):
         """Uses the model's LIVE variables (call model.use_ema_weights() first to mirror
