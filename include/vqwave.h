@@ -48,6 +48,15 @@ int vqw_mu_law_decode_f32(const float* idx, float* x, size_t n, vqw_stream_t s);
  * inputs = encode_f32(shift_right(x)); x is [B][T]. Either output may be NULL. */
 int vqw_wavenet_inputs(const float* x, float* inputs, int32_t* labels, int B, int T,
                        vqw_stream_t s);
+/* The same four at `levels` = 256, 512 or 1024 mu-law levels (mu = levels - 1; labels 0..levels-1, idx 0..levels): the
+ * integer labels are compares against the level's own exact threshold table (tools/gen_mu_law_table.py --levels), bit for
+ * bit the fp32 formula for every fp32 input.  levels = 256 runs the kernels of the calls above (the same bits).  Any other
+ * level is an error that names it, before any device call. */
+int vqw_mu_law_encode_f32_levels(const float* x, float* y, size_t n, int levels, vqw_stream_t s);
+int vqw_mu_law_encode_i32_levels(const float* x, int32_t* y, size_t n, int levels, vqw_stream_t s);
+int vqw_mu_law_decode_f32_levels(const float* idx, float* x, size_t n, int levels, vqw_stream_t s);
+int vqw_wavenet_inputs_levels(const float* x, float* inputs, int32_t* labels, int B, int T, int levels,
+                              vqw_stream_t s);
 
 /* ------------------------------------------------------------------------------------
  * Implicit-GEMM convolution engine (fp32 MFMA) -- replaces tf.pad + tf.nn.conv2d + bias
@@ -521,6 +530,16 @@ int vqw_ar_decode_run_group_sampled_async(vqw_ar_decoder* const* hs, int n, cons
 int vqw_softmax_sample(const float* logits, const float* uniforms, const vqw_ar_sampling* rows,
                        const int32_t* t_begin, const int32_t* t_end, int mode, int32_t* idx, float* audio,
                        float* probs, int B, int Q, int T, vqw_stream_t s);
+/* The same with audio decoded at `levels` = 256, 512 or 1024 mu-law levels: with audio given, Q must be that level
+ * (vqw_softmax_sample itself keeps refusing audio with Q != 256). */
+int vqw_softmax_sample_levels(const float* logits, const float* uniforms, const vqw_ar_sampling* rows,
+                              const int32_t* t_begin, const int32_t* t_end, int mode, int32_t* idx, float* audio,
+                              float* probs, int B, int Q, int T, int levels, vqw_stream_t s);
+/* The mu-law level of an audio generator handle.  Every create call makes a 256-level handle whatever w->Q is; these set
+ * the level the handle encodes its input and decodes its draws with (vqw_ar_weights carries no such field).  Refused,
+ * naming the value, before any device call: a level outside {256, 512, 1024}, a level that is not the handle's w->Q, a
+ * code-input handle (vqw_ar_prior_create / vqw_ar_wide_prior_create), a handle with a run pending (wait first). */
+int vqw_ar_decode_set_levels(vqw_ar_decoder* h, int levels);   /* vqw_ar_wide_set_levels: with the wide generator below */
 /* Prefill: leave the handle in the state it would have after vqw_ar_decode_reset and t_end steps teacher-forced on a
  * prompt (the input of step t is the prompt's value at t - 1, not a sampled one); the next run continues at step t_end
  * (sample i of it uses encoding[:, :, (t_end + i) / ratio]).  Sequence: vqw_ar_decode_reset, then
@@ -571,6 +590,8 @@ int vqw_ar_wide_run_async(vqw_ar_wide* h, const float* encoding, int Tz, int rat
                           float* probs_last, vqw_stream_t s);
 int vqw_ar_wide_wait(vqw_ar_wide* h);
 int vqw_ar_wide_destroy(vqw_ar_wide* h);
+/* The mu-law level of an audio wide handle (256 after vqw_ar_wide_create): the rules of vqw_ar_decode_set_levels. */
+int vqw_ar_wide_set_levels(vqw_ar_wide* h, int levels);
 /* Code-input mode of the wide generator (the latent prior over VQ codes, prior.py): the same step with a discrete input, for
  * sampling many code rows at once.  w->Q is the number of codes n_codes (a multiple of 32 in 32..1024, equal to `n_codes`) and
  * w->pre_w is read as [pre_k][n_codes][R] (prior/preprocess/kernel).  The handle reads the caller's weights IN PLACE, W_pre

@@ -116,6 +116,10 @@ SIGNATURES = {
     'vqw_mu_law_encode_i32': (_i, [_fp, _fp, _sz, _fp]),
     'vqw_mu_law_decode_f32': (_i, [_fp, _fp, _sz, _fp]),
     'vqw_wavenet_inputs': (_i, [_fp, _fp, _fp, _i, _i, _fp]),
+    'vqw_mu_law_encode_f32_levels': (_i, [_fp, _fp, _sz, _i, _fp]),
+    'vqw_mu_law_encode_i32_levels': (_i, [_fp, _fp, _sz, _i, _fp]),
+    'vqw_mu_law_decode_f32_levels': (_i, [_fp, _fp, _sz, _i, _fp]),
+    'vqw_wavenet_inputs_levels': (_i, [_fp, _fp, _fp, _i, _i, _i, _fp]),
     'vqw_conv_gemm': (_i, [C.POINTER(ConvDesc), _fp]),
     'vqw_wgrad_gemm': (_i, [C.POINTER(WgradDesc), _fp]),
     'vqw_causal_conv1d_fwd': (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp]),
@@ -150,6 +154,7 @@ SIGNATURES = {
     'vqw_softmax_score': (_i, [_fp] * 9 + [_i64, _i, _i, _i, _fp]),
     'vqw_code_histogram': (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp]),
     'vqw_softmax_sample': (_i, [_fp, _fp, C.POINTER(ArSampling), _fp, _fp, _i, _fp, _fp, _fp, _i, _i, _i, _fp]),
+    'vqw_softmax_sample_levels': (_i, [_fp, _fp, C.POINTER(ArSampling), _fp, _fp, _i, _fp, _fp, _fp, _i, _i, _i, _i, _fp]),
     'vqw_cond_proj_fwd': (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _fp]),
     'vqw_cond_proj_wgrad': (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _fp]),
     'vqw_cond_proj_dgrad': (_i, [_fp, _fp, _fp, _fp, C.c_int64, _i, _i, _i, _i, _fp]),
@@ -162,6 +167,7 @@ SIGNATURES = {
     'vqw_ar_decode_create': (_i, [C.POINTER(_fp), C.POINTER(ArWeights), _i]),
     'vqw_ar_decode_create_ex': (_i, [C.POINTER(_fp), C.POINTER(ArWeights), _i, _i]),
     'vqw_ar_decode_reset': (_i, [_fp, _fp]),
+    'vqw_ar_decode_set_levels': (_i, [_fp, _i]),
     'vqw_ar_decode_run': (_i, [_fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
     'vqw_ar_decode_run_async': (_i, [_fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
     'vqw_ar_decode_wait': (_i, [_fp]),
@@ -179,6 +185,7 @@ SIGNATURES = {
     'vqw_ar_wide_create': (_i, [C.POINTER(_fp), C.POINTER(ArWeights), _i]),
     'vqw_ar_wide_prior_create': (_i, [C.POINTER(_fp), C.POINTER(ArWeights), _i, _i]),
     'vqw_ar_wide_reset': (_i, [_fp, _fp]),
+    'vqw_ar_wide_set_levels': (_i, [_fp, _i]),
     'vqw_ar_wide_run_async': (_i, [_fp, _fp, _i, _i, _i, _i, _fp, C.POINTER(ArSampling), _fp, _fp, _fp, _fp]),
     'vqw_ar_wide_wait': (_i, [_fp]),
     'vqw_ar_wide_destroy': (_i, [_fp]),

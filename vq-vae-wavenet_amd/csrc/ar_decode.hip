@@ -58,12 +58,12 @@ struct GemvArgs {
 
 // wavenet.py:113-124: x = mu_law_encode(input_t); fast_conv1d(k=pre_k, dilation 1, Cin=1).
 __global__ void ar_pre_kernel(const ArState* st, const float* prev, float* xring, const float* pre_w,
-                              const float* pre_b, float* cur, int pre_k, int R) {
+                              const float* pre_b, float* cur, int pre_k, int R, const VqwMu mu) {
     __shared__ float taps[64];
     const int b = blockIdx.x;
     const int step = st->step;
     float* ring = xring + (size_t)b * pre_k;
-    const float x_new = vqw_mu_encode(prev[b]);
+    const float x_new = vqw_mu_encode_m(prev[b], mu);
     if (threadIdx.x < pre_k) {
         const int j = threadIdx.x;                      // tap j multiplies x(t - (pre_k-1-j))
         const int tau = step - (pre_k - 1 - j);
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(const GemvArgs a) {
 
 // softmax (wavenet.py:171) + utils.decode (utils.py:30-46) + mu_law_decode_np; advances the step.
 __global__ __launch_bounds__(256) void ar_sample_kernel(ArState* st, const float* logits, float* probs,
-                                                        float* prev, int B, int Q) {
+                                                        float* prev, int B, int Q, const VqwMu mu) {
     __shared__ float sp[1024];
     __shared__ float redv[4];
     __shared__ int redi[4];
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256) void ar_sample_kernel(ArState* st, const float
                 const int idx = ar_sample_truncated(sp, Q, st->samp[b], st->uniforms[(size_t)b * st->n_steps + i_out],
                                                     st->probs_last ? st->probs_last + (size_t)b * Q : probs + (size_t)b * Q);
                 if (lane == 0) {
-                    const float dec = vqw_mu_decode((float)idx);
+                    const float dec = vqw_mu_decode_m((float)idx, mu);
                     if (st->audio) st->audio[(size_t)b * st->n_steps + i_out] = dec;
                     if (st->indices) st->indices[(size_t)b * st->n_steps + i_out] = idx;
                     prev[b] = dec;
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256) void ar_sample_kernel(ArState* st, const float
                     if (c < u) idx = q + 1;
                 }
             }
-            const float dec = vqw_mu_decode((float)idx);
+            const float dec = vqw_mu_decode_m((float)idx, mu);
             if (st->audio) st->audio[(size_t)b * st->n_steps + i_out] = dec;
             if (st->indices) st->indices[(size_t)b * st->n_steps + i_out] = idx;
             prev[b] = dec;
@@ -336,6 +336,7 @@ struct vqw_ar_decoder {
     bool pending = false;          // a run has been enqueued and not yet waited for
     hipStream_t run_stream = nullptr;   // the stream that run was enqueued on (a group run: the first handle's)
     int n_codes = 0;               // > 0: code-input mode of the latent prior (persistent kernel only, vqw_ar_prior_create)
+    VqwMu mu = {256, 255.0f, 5.5451774444795623f};   // the mu-law level of an audio handle (vqw_ar_decode_set_levels)
 };
 
 namespace {
@@ -350,7 +351,7 @@ int launch_step(vqw_ar_decoder* h, hipStream_t st) {
     const vqw_ar_weights& w = h->w;
     const int B = h->B, R = w.R, S = w.S, Q = w.Q, ks = w.kernel_size;
     hipLaunchKernelGGL(ar_pre_kernel, dim3(B), dim3(256), 0, st, h->st, h->prev, h->xring, w.pre_w, w.pre_b,
-                       h->cur, w.pre_k, R);
+                       h->cur, w.pre_k, R, h->mu);
     GemvArgs a;
     // skip = linear(current)  (wavenet.py:127-128)
     memset(&a, 0, sizeof(a));
@@ -388,7 +389,7 @@ int launch_step(vqw_ar_decoder* h, hipStream_t st) {
     a.seg[0] = GemvSeg{w.post2_w, h->h, S, Q, 0, 0};
     a.nseg = 1; a.B = B; a.N = Q; a.in_relu = 1; a.bias = w.post2_b; a.out = h->logits; a.st = h->st;
     hipLaunchKernelGGL((ar_gemv_kernel<MODE_PLAIN>), dim3(vqw_cdiv(Q, 16)), dim3(256), B * S * sizeof(float) + 4 * MAXB * 16 * sizeof(float), st, a);
-    hipLaunchKernelGGL(ar_sample_kernel, dim3(1), dim3(256), 0, st, h->st, h->logits, h->probs, h->prev, B, Q);
+    hipLaunchKernelGGL(ar_sample_kernel, dim3(1), dim3(256), 0, st, h->st, h->logits, h->probs, h->prev, B, Q, h->mu);
     VQW_LAUNCH_CHECK("vqw_ar_decode_run(step)");
     return 0;
 }
@@ -486,6 +487,23 @@ extern "C" int vqw_ar_prior_create(vqw_ar_decoder** out, const vqw_ar_weights* w
     return ar_create(out, w, batch, channels_per_workgroup, n_codes);
 }
 
+// The mu-law level of an audio handle: 256 after every create call, whatever w->Q is.  Every check comes before any device call.
+extern "C" int vqw_ar_decode_set_levels(vqw_ar_decoder* h, int levels) {
+    VqwMu m;
+    VQW_CHECK(vqw_mu_level(levels, &m), "vqw_ar_decode_set_levels: levels=%d must be 256, 512 or 1024", levels);
+    VQW_CHECK(h, "vqw_ar_decode_set_levels: null handle");
+    VQW_CHECK(h->n_codes == 0, "vqw_ar_decode_set_levels: a code-input handle (n_codes=%d) has no mu-law", h->n_codes);
+    VQW_CHECK(levels == h->w.Q, "vqw_ar_decode_set_levels: levels=%d is not the handle's Q=%d", levels, (int)h->w.Q);
+    VQW_CHECK(!h->pending, "vqw_ar_decode_set_levels: levels=%d refused while a run is pending (vqw_ar_decode_wait first)", levels);
+    if (m.levels == h->mu.levels) return 0;
+    h->mu = m;
+    if (h->persist) arp_set_levels(h->persist, m);
+    // the captured step carries the level as a kernel argument: capture again on the next run
+    if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    return 0;
+}
+
 extern "C" int vqw_ar_decode_reset(vqw_ar_decoder* h, vqw_stream_t s) {
     VQW_CHECK(h, "vqw_ar_decode_reset: null handle");
     if (h->pending) {
@@ -524,11 +542,11 @@ __global__ void ar_prefill_ring_kernel(float* ring, int depth, int BR, const flo
 // last sample and the step counter.  tail[b][j] is a[t_end - pre_k + j]; entries before step 0 keep the reset's zeros.
 // audio_tail NULL (a code-mode handle, whose history lives in the persistent kernel): only the step counter.
 __global__ void ar_prefill_finish_kernel(ArState* st, float* prev, float* xring, int B, int pre_k, int t_end,
-                                         const float* audio_tail) {
+                                         const float* audio_tail, const VqwMu mu) {
     if (audio_tail) {
         for (int i = threadIdx.x; i < B * pre_k; i += blockDim.x) {
             const int b = i / pre_k, s = t_end - pre_k + i % pre_k;
-            if (s >= 0) xring[b * pre_k + (s + 1) % pre_k] = vqw_mu_encode(audio_tail[i]);
+            if (s >= 0) xring[b * pre_k + (s + 1) % pre_k] = vqw_mu_encode_m(audio_tail[i], mu);
         }
         if (t_end > 0)
             for (int b = threadIdx.x; b < B; b += blockDim.x) prev[b] = audio_tail[b * pre_k + pre_k - 1];
@@ -582,7 +600,7 @@ extern "C" int vqw_ar_decode_prefill_finish(vqw_ar_decoder* h, int t_end, const 
         if (rc) return rc;
     }
     hipLaunchKernelGGL(ar_prefill_finish_kernel, dim3(1), dim3(256), 0, st, h->st, h->prev, h->xring, h->B, h->w.pre_k, t_end,
-                       audio_tail);
+                       audio_tail, h->mu);
     VQW_LAUNCH_CHECK("vqw_ar_decode_prefill_finish");
     return 0;
 }

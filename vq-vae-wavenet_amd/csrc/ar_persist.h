@@ -1,6 +1,7 @@
 // Internal interface of the persistent fast-generation kernel (csrc/ar_persist.hip).
 #pragma once
 #include "ar_sampling.h"
+#include "mu_law.h"
 #include "vqw_common.h"
 
 struct ArPersist;
@@ -10,6 +11,7 @@ int arp_create(ArPersist** out, const vqw_ar_weights* w, const int* dil, const f
                int channels_per_workgroup,    // 0 = auto (4 where the chip has R/4 CUs), 4 or 8
                int n_codes);                  // > 0: code-input mode (w->pre_w is [pre_k][n_codes][R]); 0: audio
 int arp_reset(ArPersist* h, hipStream_t st);
+void arp_set_levels(ArPersist* h, const VqwMu& m);   // audio handles: the mu-law level of the decode / re-encode table (256 after create)
 // ONE launch for n handles (1..8, the same kernel instantiation, n * workgroups <= CUs) generating side by side.
 // condenc[i]: L+1 device pointers of handle i ([B][2R][Tz] per layer, then [B][S][Tz] of postprocess1)
 int arp_run(ArPersist* const* hs, int n, const float* const* const* condenc, int Tz, int ratio, int n_steps, int mode,

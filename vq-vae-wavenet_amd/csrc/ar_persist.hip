@@ -71,6 +71,7 @@ struct PArgs {
     u64 *ex_g, *ex_s, *ex_h, *ex_l;  // [2][B][R] (phase parity), [B][S], [B][S], [B][Q]
     float* xhist;                 // [B][pre_k] encoded input history (state across runs); code mode: code + 1, 0 = no code
     int n_codes;                  // > 0: code-input mode (latent prior): the input is the sampled index, no mu-law
+    VqwMu mu;                     // audio mode: the mu-law level (256 unless arp_set_levels; then it is Q)
     const float* prew;            // code mode: [pre_k][n_codes][R] preprocess kernel (the handle's copy)
     float* prev;                  // [B] last decoded sample
     int* state;                   // [0] = step, [1] = error
@@ -395,12 +396,12 @@ __global__ __launch_bounds__(NTHR, 1) void ar_persist_kernel(const PGroup grp) {
     for (int i = tid; i < B * a.pre_k; i += NTHR) xh[i] = a.xhist[i];
     if (tid == 0) *fail = 0;
     for (int i = tid; i <= Q; i += NTHR) {
-        const float dec = vqw_mu_decode((float)i);
+        const float dec = vqw_mu_decode_m((float)i, a.mu);
         lds[cv.dtab + i] = dec;
-        lds[cv.dtab + Q + 1 + i] = vqw_mu_encode(dec);
+        lds[cv.dtab + Q + 1 + i] = vqw_mu_encode_m(dec, a.mu);
     }
     __syncthreads();
-    if (tid < B && !a.n_codes) xh[tid * a.pre_k + (t0 % a.pre_k)] = vqw_mu_encode(a.prev[tid]);   // x_in(t0) = mu_law_encode(previous sample)
+    if (tid < B && !a.n_codes) xh[tid * a.pre_k + (t0 % a.pre_k)] = vqw_mu_encode_m(a.prev[tid], a.mu);   // x_in(t0) = mu_law_encode(previous sample)
     // (code mode: the history saved by the last run already holds the previous code, or 0 = none after a reset)
     __syncthreads();
 
@@ -962,6 +963,7 @@ int arp_create(ArPersist** out, const vqw_ar_weights* w, const int* dil, const f
     PArgs& a = h->args;
     memset(&a, 0, sizeof(a));
     a.L = L; a.R = R; a.S = S; a.Q = Q; a.B = batch; a.nQ = nQ; a.pre_k = w->pre_k;
+    vqw_mu_level(256, &a.mu);
     const int npw = ((ks - 1) * RL * 2 + 3) / 4, ncw = (RL * (5 + nS) + 3) / 4;
     // ---- per-phase weight columns, blocked per compute thread; biases; head
     const size_t pstride = (size_t)nwg * npw * NCT * 4, cstride = (size_t)nwg * ncw * NCT * 4;
@@ -1050,6 +1052,8 @@ int arp_create(ArPersist** out, const vqw_ar_weights* w, const int* dil, const f
     return 0;
 }
 
+void arp_set_levels(ArPersist* h, const VqwMu& m) { h->args.mu = m; }
+
 int arp_reset(ArPersist* h, hipStream_t st) {
     for (auto& z : h->zero_on_reset) PHIPC(hipMemsetAsync(z.first, 0, z.second, st));
     return 0;
@@ -1074,11 +1078,11 @@ __global__ void arp_prefill_layer_kernel(u64* ring, int depth, int BR, const flo
 // tau in (t_end - pre_k, t_end], x_in(tau) = mu_law_encode(a[tau - 1]) (audio) or c[tau - 1] + 1 (codes; 0 = no code).
 // tail[b][j] is prompt entry t_end - pre_k + j; entries before step 0 keep the reset's zeros.
 __global__ void arp_prefill_finish_kernel(float* xhist, float* prev, int* state, int B, int pre_k, int t_end,
-                                          const float* audio_tail, const int32_t* code_tail) {
+                                          const float* audio_tail, const int32_t* code_tail, const VqwMu mu) {
     for (int i = threadIdx.x; i < B * pre_k; i += blockDim.x) {
         const int b = i / pre_k, s = t_end - pre_k + i % pre_k;
         if (s < 0) continue;
-        xhist[b * pre_k + (s + 1) % pre_k] = audio_tail ? vqw_mu_encode(audio_tail[i]) : (float)(code_tail[i] + 1);
+        xhist[b * pre_k + (s + 1) % pre_k] = audio_tail ? vqw_mu_encode_m(audio_tail[i], mu) : (float)(code_tail[i] + 1);
     }
     if (audio_tail && t_end > 0)
         for (int b = threadIdx.x; b < B; b += blockDim.x) prev[b] = audio_tail[b * pre_k + pre_k - 1];
@@ -1100,7 +1104,7 @@ int arp_prefill_layer(ArPersist* h, int l, const float* x, int ld, int t_first, 
 
 int arp_prefill_finish(ArPersist* h, int t_end, const float* audio_tail, const int32_t* code_tail, hipStream_t st) {
     hipLaunchKernelGGL(arp_prefill_finish_kernel, dim3(1), dim3(256), 0, st, h->args.xhist, h->args.prev, h->args.state, h->B,
-                       h->args.pre_k, t_end, audio_tail, code_tail);
+                       h->args.pre_k, t_end, audio_tail, code_tail, h->args.mu);
     VQW_LAUNCH_CHECK("vqw_ar_decode_prefill_finish(persistent)");
     return 0;
 }

@@ -79,7 +79,7 @@ struct WideArgs {
 // wavenet.py:113-124: x = mu_law_encode(input_t); fast_conv1d(k=pre_k, dilation 1, Cin=1), every row in one launch.
 // Block: 64 rows x 32 channels; xhist [pre_k][B], slot tau % pre_k holds the input of step tau.
 __global__ __launch_bounds__(256) void arw_pre_kernel(const WideState* st, const float* prev, float* xhist, const float* pre_w,
-                                                      const float* pre_b, float* cur, int pre_k, int R, int B) {
+                                                      const float* pre_b, float* cur, int pre_k, int R, int B, const VqwMu mu) {
     __shared__ float taps[64][64];
     const int tb = threadIdx.x & 63, tg = threadIdx.x >> 6;
     const int b = blockIdx.x * 64 + tb;
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void arw_pre_kernel(const WideState* st, const
         for (int j = tg; j < pre_k; j += 4) {               // tap j multiplies x(t - (pre_k-1-j))
             float v;
             if (j == pre_k - 1) {
-                v = vqw_mu_encode(prev[b]);
+                v = vqw_mu_encode_m(prev[b], mu);
                 if (blockIdx.y == 0) xhist[(size_t)(step % pre_k) * B + b] = v;   // the slot of t - pre_k: no tap reads it
             } else {
                 const int tau = step - (pre_k - 1 - j);
@@ -301,7 +301,7 @@ __global__ void arw_window_kernel(WideState* st, const float* __restrict__ enc, 
 // the last cdf value gives Q, which is no code: it is clamped to Q - 1.
 template <bool CODE>
 __global__ __launch_bounds__(256) void arw_sample_kernel(WideState* st, const float* logits, const ArSampleRow* samp, float* prev,
-                                                         int B, int Q) {
+                                                         int B, int Q, const VqwMu mu) {
     __shared__ float sp[1024];
     __shared__ float redv[4];
     __shared__ int redi[4];
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256) void arw_sample_kernel(WideState* st, const fl
             st->indices[(size_t)b * n_steps + i_out] = idx;
             prev[b] = (float)(idx + 1);
         } else {
-            const float dec = vqw_mu_decode((float)idx);
+            const float dec = vqw_mu_decode_m((float)idx, mu);
             st->audio[(size_t)b * n_steps + i_out] = dec;
             if (st->indices) st->indices[(size_t)b * n_steps + i_out] = idx;
             prev[b] = dec;
@@ -411,6 +411,7 @@ struct vqw_ar_wide {
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
     bool pending = false;
+    VqwMu mu = {256, 255.0f, 5.5451774444795623f};   // the mu-law level of an audio handle (vqw_ar_wide_set_levels)
 };
 
 namespace {
@@ -444,7 +445,7 @@ int launch_step(vqw_ar_wide* h, hipStream_t st) {
                            w.pre_b, h->cur, w.pre_k, h->n_codes, R, B);
     else
         hipLaunchKernelGGL(arw_pre_kernel, dim3(vqw_cdiv(B, 64), R / 32), dim3(256), 0, st, h->st, h->prev, h->xhist, w.pre_w, w.pre_b,
-                           h->cur, w.pre_k, R, B);
+                           h->cur, w.pre_k, R, B, h->mu);
     // skip = linear(current)  (wavenet.py:127-128)
     WideArgs a = base_args(h);
     a.seg[0] = WideSeg{w.skip0_w, h->cur, 0, 0};
@@ -482,9 +483,9 @@ int launch_step(vqw_ar_wide* h, hipStream_t st) {
     a.nseg = 1; a.K = S; a.ldw = Q; a.N = Q; a.in_relu = 1; a.bias = w.post2_b; a.out = h->logits;
     launch_gemm<MODE_PLAIN>(a, Q, 1, st);
     if (h->n_codes)
-        hipLaunchKernelGGL(arw_sample_kernel<true>, dim3(B), dim3(256), 0, st, h->st, h->logits, h->samp, h->prev, B, Q);
+        hipLaunchKernelGGL(arw_sample_kernel<true>, dim3(B), dim3(256), 0, st, h->st, h->logits, h->samp, h->prev, B, Q, h->mu);
     else
-        hipLaunchKernelGGL(arw_sample_kernel<false>, dim3(B), dim3(256), 0, st, h->st, h->logits, h->samp, h->prev, B, Q);
+        hipLaunchKernelGGL(arw_sample_kernel<false>, dim3(B), dim3(256), 0, st, h->st, h->logits, h->samp, h->prev, B, Q, h->mu);
     VQW_LAUNCH_CHECK("vqw_ar_wide_run(step)");
     return 0;
 }
@@ -595,6 +596,22 @@ extern "C" int vqw_ar_wide_create(vqw_ar_wide** out, const vqw_ar_weights* w, in
 
 extern "C" int vqw_ar_wide_prior_create(vqw_ar_wide** out, const vqw_ar_weights* w, int batch, int n_codes) {
     return wide_create("vqw_ar_wide_prior_create", out, w, batch, n_codes);
+}
+
+// The mu-law level of an audio handle: 256 after vqw_ar_wide_create, whatever w->Q is.  Every check comes before any device call.
+extern "C" int vqw_ar_wide_set_levels(vqw_ar_wide* h, int levels) {
+    VqwMu m;
+    VQW_CHECK(vqw_mu_level(levels, &m), "vqw_ar_wide_set_levels: levels=%d must be 256, 512 or 1024", levels);
+    VQW_CHECK(h, "vqw_ar_wide_set_levels: null handle");
+    VQW_CHECK(h->n_codes == 0, "vqw_ar_wide_set_levels: a code-input handle (n_codes=%d) has no mu-law", h->n_codes);
+    VQW_CHECK(levels == h->w.Q, "vqw_ar_wide_set_levels: levels=%d is not the handle's Q=%d", levels, (int)h->w.Q);
+    VQW_CHECK(!h->pending, "vqw_ar_wide_set_levels: levels=%d refused while a run is pending (vqw_ar_wide_wait first)", levels);
+    if (m.levels == h->mu.levels) return 0;
+    h->mu = m;
+    // the captured step carries the level as a kernel argument: capture again on the next run
+    if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    return 0;
 }
 
 extern "C" int vqw_ar_wide_reset(vqw_ar_wide* h, vqw_stream_t s) {

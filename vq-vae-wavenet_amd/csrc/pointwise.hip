@@ -3,11 +3,15 @@
 // Reference call sites are cited per kernel; numerics follow SURVEY.md Appendix A.
 #include "mu_law.h"
 #include "mu_law_table.h"
+#include "mu_law_table_512.h"
+#include "mu_law_table_1024.h"
 #include "vqw_common.h"
 
 namespace {
 
 __device__ __constant__ unsigned int VQW_MU_LAW_THR_BITS_DEV[255] = VQW_MU_LAW_THR_BITS_LIST;
+__device__ __constant__ unsigned int VQW_MU_LAW_THR_BITS_DEV_512[511] = VQW_MU_LAW_THR_BITS_LIST_512;
+__device__ __constant__ unsigned int VQW_MU_LAW_THR_BITS_DEV_1024[1023] = VQW_MU_LAW_THR_BITS_LIST_1024;
 
 // ----------------------------------------------------------------------------- mu-law (the float forms: mu_law.h)
 // label(x) = #{thr <= clip(x)}: compares only => bit-exact vs the fp32 formula
@@ -59,6 +63,64 @@ __global__ void wavenet_inputs_kernel(const float* __restrict__ x, float* __rest
         const float v = x[i];
         if (labels) labels[i] = mu_encode_i(v, thr);
         if (inputs) inputs[i] = (t == 0) ? 0.0f : vqw_mu_encode(x[i - 1]);
+    }
+}
+
+// ----------------------------------------------------------------------------- mu-law at 512 / 1024 levels
+// The same kernels with the level as a template argument (LV - 1 thresholds in LDS, log2(LV) halvings) and its constants as
+// arguments (mu_law.h).  The 256-level kernels above stay as they are: the _levels entry points launch THEM at 256.
+template <int LV>
+__device__ __forceinline__ int mu_encode_i_lv(float x, const float* thr) {
+    static_assert(LV == 512 || LV == 1024, "levels");
+    x = fminf(fmaxf(x, -1.0f), 1.0f);
+    int lo = 0, hi = LV - 1;
+#pragma unroll
+    for (int it = 0; it < (LV == 512 ? 9 : 10); ++it) {
+        const int mid = (lo + hi) >> 1;
+        const bool ge = (lo < hi) && (thr[mid] <= x);
+        const bool lt = (lo < hi) && !(thr[mid] <= x);
+        lo = ge ? mid + 1 : lo;
+        hi = lt ? mid : hi;
+    }
+    return lo;
+}
+
+template <int LV>
+__device__ __forceinline__ void load_thr_lv(float* thr) {
+    const unsigned int* bits = LV == 512 ? VQW_MU_LAW_THR_BITS_DEV_512 : VQW_MU_LAW_THR_BITS_DEV_1024;
+    for (int i = threadIdx.x; i < LV - 1; i += blockDim.x) thr[i] = __uint_as_float(bits[i]);
+    __syncthreads();
+}
+
+__global__ void mu_encode_f32_lv_kernel(const float* __restrict__ x, float* __restrict__ y, size_t n, float mu, float log1p_mu) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        y[i] = vqw_mu_encode_l(x[i], mu, log1p_mu);
+}
+
+template <int LV>
+__global__ void mu_encode_i32_lv_kernel(const float* __restrict__ x, int32_t* __restrict__ y, size_t n) {
+    __shared__ float thr[LV];
+    load_thr_lv<LV>(thr);
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        y[i] = mu_encode_i_lv<LV>(x[i], thr);
+}
+
+__global__ void mu_decode_f32_lv_kernel(const float* __restrict__ idx, float* __restrict__ x, size_t n, float mu) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        x[i] = vqw_mu_decode_l(idx[i], mu);
+}
+
+template <int LV>
+__global__ void wavenet_inputs_lv_kernel(const float* __restrict__ x, float* __restrict__ inputs, int32_t* __restrict__ labels,
+                                         int B, int T, float mu, float log1p_mu) {
+    __shared__ float thr[LV];
+    load_thr_lv<LV>(thr);
+    const size_t n = (size_t)B * T;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int t = (int)(i % T);
+        const float v = x[i];
+        if (labels) labels[i] = mu_encode_i_lv<LV>(v, thr);
+        if (inputs) inputs[i] = (t == 0) ? 0.0f : vqw_mu_encode_l(x[i - 1], mu, log1p_mu);
     }
 }
 
@@ -613,6 +675,58 @@ extern "C" int vqw_wavenet_inputs(const float* x, float* inputs, int32_t* labels
     VQW_CHECK(B > 0 && T > 0, "vqw_wavenet_inputs: bad shape");
     hipLaunchKernelGGL(wavenet_inputs_kernel, dim3(grid_for((size_t)B * T, 256)), dim3(256), 0, (hipStream_t)s, x, inputs, labels, B, T);
     VQW_LAUNCH_CHECK("vqw_wavenet_inputs");
+    return 0;
+}
+
+// The same four at 256, 512 or 1024 levels.  256 runs the kernels above (the same bits as the entries without a level).
+extern "C" int vqw_mu_law_encode_f32_levels(const float* x, float* y, size_t n, int levels, vqw_stream_t s) {
+    VqwMu m;
+    VQW_CHECK(vqw_mu_level(levels, &m), "vqw_mu_law_encode_f32_levels: levels=%d must be 256, 512 or 1024", levels);
+    if (levels == 256) return vqw_mu_law_encode_f32(x, y, n, s);
+    if (n == 0) return 0;
+    VQW_CHECK(x && y, "vqw_mu_law_encode_f32_levels: null pointer");
+    hipLaunchKernelGGL(mu_encode_f32_lv_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)s, x, y, n, m.mu, m.log1p_mu);
+    VQW_LAUNCH_CHECK("vqw_mu_law_encode_f32_levels");
+    return 0;
+}
+
+extern "C" int vqw_mu_law_encode_i32_levels(const float* x, int32_t* y, size_t n, int levels, vqw_stream_t s) {
+    VqwMu m;
+    VQW_CHECK(vqw_mu_level(levels, &m), "vqw_mu_law_encode_i32_levels: levels=%d must be 256, 512 or 1024", levels);
+    if (levels == 256) return vqw_mu_law_encode_i32(x, y, n, s);
+    if (n == 0) return 0;
+    VQW_CHECK(x && y, "vqw_mu_law_encode_i32_levels: null pointer");
+    if (levels == 512)
+        hipLaunchKernelGGL(mu_encode_i32_lv_kernel<512>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)s, x, y, n);
+    else
+        hipLaunchKernelGGL(mu_encode_i32_lv_kernel<1024>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)s, x, y, n);
+    VQW_LAUNCH_CHECK("vqw_mu_law_encode_i32_levels");
+    return 0;
+}
+
+extern "C" int vqw_mu_law_decode_f32_levels(const float* idx, float* x, size_t n, int levels, vqw_stream_t s) {
+    VqwMu m;
+    VQW_CHECK(vqw_mu_level(levels, &m), "vqw_mu_law_decode_f32_levels: levels=%d must be 256, 512 or 1024", levels);
+    if (levels == 256) return vqw_mu_law_decode_f32(idx, x, n, s);
+    if (n == 0) return 0;
+    VQW_CHECK(idx && x, "vqw_mu_law_decode_f32_levels: null pointer");
+    hipLaunchKernelGGL(mu_decode_f32_lv_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)s, idx, x, n, m.mu);
+    VQW_LAUNCH_CHECK("vqw_mu_law_decode_f32_levels");
+    return 0;
+}
+
+extern "C" int vqw_wavenet_inputs_levels(const float* x, float* inputs, int32_t* labels, int B, int T, int levels, vqw_stream_t s) {
+    VqwMu m;
+    VQW_CHECK(vqw_mu_level(levels, &m), "vqw_wavenet_inputs_levels: levels=%d must be 256, 512 or 1024", levels);
+    if (levels == 256) return vqw_wavenet_inputs(x, inputs, labels, B, T, s);
+    VQW_CHECK(x && (inputs || labels), "vqw_wavenet_inputs_levels: null pointer");
+    VQW_CHECK(B > 0 && T > 0, "vqw_wavenet_inputs_levels: bad shape");
+    const dim3 grid(grid_for((size_t)B * T, 256));
+    if (levels == 512)
+        hipLaunchKernelGGL(wavenet_inputs_lv_kernel<512>, grid, dim3(256), 0, (hipStream_t)s, x, inputs, labels, B, T, m.mu, m.log1p_mu);
+    else
+        hipLaunchKernelGGL(wavenet_inputs_lv_kernel<1024>, grid, dim3(256), 0, (hipStream_t)s, x, inputs, labels, B, T, m.mu, m.log1p_mu);
+    VQW_LAUNCH_CHECK("vqw_wavenet_inputs_levels");
     return 0;
 }
 

@@ -20,7 +20,7 @@ namespace {
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void greedy_kernel(const float* __restrict__ logits, const int32_t* __restrict__ t_begin,
                                                          const int32_t* __restrict__ t_end, int32_t* __restrict__ idx,
-                                                         float* __restrict__ audio, int Q, int T) {
+                                                         float* __restrict__ audio, int Q, int T, const VqwMu mu) {
     __shared__ float sv[NW][64];
     __shared__ int si[NW][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(NW * 64) void greedy_kernel(const float* __restrict
         if (sv[i][lane] > BV) { BV = sv[i][lane]; BI = si[i][lane]; }
     BI = min(BI, Q - 1);                        // nothing compared greater (-inf or NaN everywhere): still a class
     idx[(size_t)b * T + t] = in ? BI : -1;
-    if (audio) audio[(size_t)b * T + t] = in ? vqw_mu_decode((float)BI) : 0.0f;
+    if (audio) audio[(size_t)b * T + t] = in ? vqw_mu_decode_m((float)BI, mu) : 0.0f;
 }
 
 // ----------------------------------------------------------------------------- sample (and greedy with probs)
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_tile_kernel(const float* _
                                                           const SmpRows rows, const int32_t* __restrict__ t_begin,
                                                           const int32_t* __restrict__ t_end, int mode, int32_t* __restrict__ idx,
                                                           float* __restrict__ audio, float* __restrict__ probs, int Q, int T,
-                                                          int nt_shift) {
+                                                          int nt_shift, const VqwMu mu) {
     extern __shared__ float tile[];             // [NT][Q + 1]
     __shared__ int sidx[64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_tile_kernel(const float* _
     if (tid < NT && t0 + tid < T) {
         const int c = sidx[tid];
         idx[(size_t)b * T + t0 + tid] = c;
-        if (audio) audio[(size_t)b * T + t0 + tid] = c >= 0 ? vqw_mu_decode((float)c) : 0.0f;
+        if (audio) audio[(size_t)b * T + t0 + tid] = c >= 0 ? vqw_mu_decode_m((float)c, mu) : 0.0f;
     }
 }
 
@@ -184,35 +184,33 @@ inline int sample_nt_shift(int Q) {
     return sh;
 }
 
-}  // namespace
-
-// ============================================================================ C ABI
-extern "C" int vqw_softmax_sample(const float* logits, const float* uniforms, const vqw_ar_sampling* rows, const int32_t* t_begin,
-                                  const int32_t* t_end, int mode, int32_t* idx, float* audio, float* probs, int B, int Q, int T,
-                                  vqw_stream_t s) {
-    VQW_CHECK(logits && idx, "vqw_softmax_sample: null pointer");
-    VQW_CHECK(B >= 1 && T >= 1, "vqw_softmax_sample: bad shape B=%d T=%d", B, T);
-    VQW_CHECK(Q >= 1 && Q % 4 == 0 && Q <= 1024, "vqw_softmax_sample: Q=%d must be a multiple of 4 and at most 1024", Q);
-    VQW_CHECK(mode == 0 || mode == 1, "vqw_softmax_sample: mode %d must be 0 (greedy) or 1 (sample)", mode);
-    VQW_CHECK(mode == 0 || uniforms, "vqw_softmax_sample: mode 1 (sample) needs uniforms");
-    VQW_CHECK(!audio || Q == 256, "vqw_softmax_sample: audio is the mu-law decode of 256 classes (Q=%d)", Q);
+// both entry points; fn names the caller in the messages, mu is the level audio is decoded at
+int softmax_sample(const char* fn, const float* logits, const float* uniforms, const vqw_ar_sampling* rows, const int32_t* t_begin,
+                   const int32_t* t_end, int mode, int32_t* idx, float* audio, float* probs, int B, int Q, int T, const VqwMu& mu,
+                   vqw_stream_t s) {
+    VQW_CHECK(logits && idx, "%s: null pointer", fn);
+    VQW_CHECK(B >= 1 && T >= 1, "%s: bad shape B=%d T=%d", fn, B, T);
+    VQW_CHECK(Q >= 1 && Q % 4 == 0 && Q <= 1024, "%s: Q=%d must be a multiple of 4 and at most 1024", fn, Q);
+    VQW_CHECK(mode == 0 || mode == 1, "%s: mode %d must be 0 (greedy) or 1 (sample)", fn, mode);
+    VQW_CHECK(mode == 0 || uniforms, "%s: mode 1 (sample) needs uniforms", fn);
+    VQW_CHECK(!audio || Q == mu.levels, "%s: audio is the mu-law decode of %d classes (Q=%d)", fn, mu.levels, Q);
     SmpRows group;
     int any = 0;
     for (int b0 = 0; b0 < B; b0 += SMP_ROWS)    // every row's settings are checked before the first launch
         if (ar_sampling_rows(rows ? rows + b0 : nullptr, std::min(SMP_ROWS, B - b0), Q, mode, group.r, &any)) return 1;
     if (mode == 0 && !probs) {
         const int ntile = vqw_cdiv(T, 64);
-        VQW_CHECK((int64_t)B * ntile < (int64_t)1 << 31, "vqw_softmax_sample: B * ceil(T / 64) must be below 2^31");
+        VQW_CHECK((int64_t)B * ntile < (int64_t)1 << 31, "%s: B * ceil(T / 64) must be below 2^31", fn);
         if (Q % 128 == 0)
-            hipLaunchKernelGGL(greedy_kernel<8>, dim3(B * ntile), dim3(512), 0, (hipStream_t)s, logits, t_begin, t_end, idx, audio, Q, T);
+            hipLaunchKernelGGL(greedy_kernel<8>, dim3(B * ntile), dim3(512), 0, (hipStream_t)s, logits, t_begin, t_end, idx, audio, Q, T, mu);
         else
-            hipLaunchKernelGGL(greedy_kernel<4>, dim3(B * ntile), dim3(256), 0, (hipStream_t)s, logits, t_begin, t_end, idx, audio, Q, T);
+            hipLaunchKernelGGL(greedy_kernel<4>, dim3(B * ntile), dim3(256), 0, (hipStream_t)s, logits, t_begin, t_end, idx, audio, Q, T, mu);
         VQW_LAUNCH_CHECK("vqw_softmax_sample (greedy)");
         return 0;
     }
     const int sh = sample_nt_shift(Q);
     const int ntile = (T + (1 << sh) - 1) >> sh;
-    VQW_CHECK((int64_t)SMP_ROWS * ntile < (int64_t)1 << 31, "vqw_softmax_sample: T too large");
+    VQW_CHECK((int64_t)SMP_ROWS * ntile < (int64_t)1 << 31, "%s: T too large", fn);
     const size_t lds = ((size_t)(Q + 1) << sh) * sizeof(float);
     for (int b0 = 0; b0 < B; b0 += SMP_ROWS) {
         const int nb = std::min(SMP_ROWS, B - b0);
@@ -221,8 +219,28 @@ extern "C" int vqw_softmax_sample(const float* logits, const float* uniforms, co
         const size_t o = (size_t)b0 * T;
         hipLaunchKernelGGL(sample_tile_kernel, dim3(nb * ntile), dim3(SMP_THREADS), lds, (hipStream_t)s, logits + o * Q,
                            uniforms ? uniforms + o : nullptr, group, t_begin ? t_begin + b0 : nullptr, t_end ? t_end + b0 : nullptr, mode,
-                           idx + o, audio ? audio + o : nullptr, probs ? probs + o * Q : nullptr, Q, T, sh);
+                           idx + o, audio ? audio + o : nullptr, probs ? probs + o * Q : nullptr, Q, T, sh, mu);
         VQW_LAUNCH_CHECK("vqw_softmax_sample");
     }
     return 0;
+}
+
+}  // namespace
+
+// ============================================================================ C ABI
+extern "C" int vqw_softmax_sample(const float* logits, const float* uniforms, const vqw_ar_sampling* rows, const int32_t* t_begin,
+                                  const int32_t* t_end, int mode, int32_t* idx, float* audio, float* probs, int B, int Q, int T,
+                                  vqw_stream_t s) {
+    VqwMu mu;
+    vqw_mu_level(256, &mu);
+    return softmax_sample("vqw_softmax_sample", logits, uniforms, rows, t_begin, t_end, mode, idx, audio, probs, B, Q, T, mu, s);
+}
+
+// audio decoded at 256, 512 or 1024 levels (with audio given, Q must be that level)
+extern "C" int vqw_softmax_sample_levels(const float* logits, const float* uniforms, const vqw_ar_sampling* rows,
+                                         const int32_t* t_begin, const int32_t* t_end, int mode, int32_t* idx, float* audio,
+                                         float* probs, int B, int Q, int T, int levels, vqw_stream_t s) {
+    VqwMu mu;
+    VQW_CHECK(vqw_mu_level(levels, &mu), "vqw_softmax_sample_levels: levels=%d must be 256, 512 or 1024", levels);
+    return softmax_sample("vqw_softmax_sample_levels", logits, uniforms, rows, t_begin, t_end, mode, idx, audio, probs, B, Q, T, mu, s);
 }

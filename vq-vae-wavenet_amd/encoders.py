@@ -383,6 +383,10 @@ class EncoderMagenta(Encoder):
         e = lambda *s: A.empty(*s, device=dev)  # noqa: E731
         Tl = [T // (2 ** (i + 1)) for i in range(L)]
         ws['m_Tl'] = Tl
+        # The encoder compands its own input at 256 levels (encoder.py:43) into the decoder's input buffer, which at 256 levels
+        # holds the same values (the decoder's backward and this one both read it again).  A decoder at another level keeps
+        # that buffer and the labels to itself: the encoder's input gets one of its own.
+        ws['m_inputs'] = ws['inputs'] if model.levels == 256 else e(B, T)
         ws['m_en'] = [e(B, F, T)] + [e(B, F, t) for t in Tl]     # en_0 .. en_6
         ws['m_dd'] = [e(B, F, t) for t in Tl]
         ws['m_gated'] = [e(B, F, t) for t in Tl]
@@ -399,9 +403,9 @@ class EncoderMagenta(Encoder):
     def forward(self, model, x, ws, save=True):
         """x [B][T] -> ws['z_e'] [B][D][T/64] (encoder.py:38-63)."""
         P, F, D, k, B, T = model.P, self.FILTERS, self.D, self.KS, ws['B'], ws['T']
-        K.wavenet_inputs(x, ws['inputs'], ws['labels'])                       # shift_right + mu_law_encode
+        K.wavenet_inputs(x, ws['m_inputs'], ws['labels'] if model.levels == 256 else None)   # shift_right + mu_law_encode
         en = ws['m_en']
-        K.conv_cin1_fwd(ws['inputs'], P['mag_pre_w'], P['mag_pre_b'], en[0], k=k, stride=1, offset=-(k - 1))
+        K.conv_cin1_fwd(ws['m_inputs'], P['mag_pre_w'], P['mag_pre_b'], en[0], k=k, stride=1, offset=-(k - 1))
         Tin = T
         for i, d in enumerate(self.DIL):
             To = ws['m_Tl'][i]
@@ -446,7 +450,7 @@ class EncoderMagenta(Encoder):
             den[i].zero_()                                       # odd time steps receive no gradient
             K.conv_gemm(x0=ddd, w=Tt['mag_d_w'][i], out0=den[i], B=B, T_in=To, T_out=To, M=F, C0=F, taps=[0],
                         out_tstride=2, out_toffset=0, T_store=Tin)
-        K.conv_cin1_wgrad(ws['inputs'], den[0], G['mag_pre_w'], k=k, stride=1, offset=-(k - 1))
+        K.conv_cin1_wgrad(ws['m_inputs'], den[0], G['mag_pre_w'], k=k, stride=1, offset=-(k - 1))
         K.rowsum(den[0], total=G['mag_pre_b'])
         if model.grad_sync is not None:
             model.grad_sync.bucket_ready(0, model.seg_off['pre_w'][0])

@@ -140,6 +140,8 @@ class WideGenerator:
         h = C.c_void_p()
         L.check(L.lib().vqw_ar_wide_create(C.byref(h), C.byref(self._w), batch))
         self._h = h
+        if model.levels != 256:          # the model's mu-law level (a created handle compands at 256)
+            L.check(L.lib().vqw_ar_wide_set_levels(h, model.levels))
 
     def reset(self):
         """sess.run(wavenet.init_ops) (generate.py:105): empty queues, the next sample is step 0."""
@@ -323,6 +325,8 @@ class FastGenerator:
 
     def _create(self, h, w, rows, cpb):
         L.check(L.lib().vqw_ar_decode_create_ex(C.byref(h), C.byref(w), rows, cpb))
+        if self.model.levels != 256:     # the model's mu-law level (a created handle compands at 256)
+            L.check(L.lib().vqw_ar_decode_set_levels(h, self.model.levels))
 
     def reset(self):
         """sess.run(wavenet.init_ops) (generate.py:105)."""

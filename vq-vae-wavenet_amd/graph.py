@@ -263,8 +263,9 @@ class Wavenet:
     def build(self, inputs, local_condition=None, global_condition=None):
         """inputs [b, t, 1] raw audio -> (logits [b*t, 256], labels int32 [b*t])  (wavenet.py:24-100)."""
         a = self.args
-        self.labels = O.mu_law_encode(inputs, to_int=True).reshape(-1)
-        net = O.mu_law_encode(O.shift_right(inputs))
+        levels = O.mu_law_levels(a['quantization_channels'])
+        self.labels = O.mu_law_encode(inputs, levels, to_int=True).reshape(-1)
+        net = O.mu_law_encode(O.shift_right(inputs), levels)
         with variable_scope('preprocess'):
             net = conv1d_v2(net, a['preprocess']['filters'], a['preprocess']['kernel_size'])
         with variable_scope('skip'):
@@ -293,7 +294,7 @@ class Wavenet:
         a = self.args
         init_ops, push_ops = [], []
         with variable_scope('preprocess'):
-            current, i_, p_ = fast_conv1d(O.mu_law_encode(input_t), a['preprocess']['filters'], a['preprocess']['kernel_size'],
+            current, i_, p_ = fast_conv1d(O.mu_law_encode(input_t, O.mu_law_levels(a['quantization_channels'])), a['preprocess']['filters'], a['preprocess']['kernel_size'],
                                           1, batch_size)
             init_ops += i_; push_ops += p_
         with variable_scope('skip'):

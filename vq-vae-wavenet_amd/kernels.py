@@ -112,32 +112,45 @@ def wgrad_gemm(*, p, q0, dw, B, T_q, T_p, Cp, Q0, taps, q1=None, Q1=0, p_stride=
     L.check(L.lib().vqw_wgrad_gemm(C.byref(d), L.stream()))
 
 
-def mu_law_encode_f32(x, out=None):
+def mu_law_encode_f32(x, out=None, levels=256):
+    """levels: 256, 512 or 1024 mu-law levels; 256 calls the entry without a level (every wrapper below likewise)."""
     L.require_cuda(x)
     out = torch.empty_like(x) if out is None else out
-    L.check(L.lib().vqw_mu_law_encode_f32(L.ptr(x), L.ptr(out), x.numel(), L.stream()))
+    if levels == 256:
+        L.check(L.lib().vqw_mu_law_encode_f32(L.ptr(x), L.ptr(out), x.numel(), L.stream()))
+    else:
+        L.check(L.lib().vqw_mu_law_encode_f32_levels(L.ptr(x), L.ptr(out), x.numel(), int(levels), L.stream()))
     return out
 
 
-def mu_law_encode_i32(x, out=None):
+def mu_law_encode_i32(x, out=None, levels=256):
     L.require_cuda(x)
     out = torch.empty(x.shape, dtype=torch.int32, device=x.device) if out is None else out
-    L.check(L.lib().vqw_mu_law_encode_i32(L.ptr(x), L.ptr(out), x.numel(), L.stream()))
+    if levels == 256:
+        L.check(L.lib().vqw_mu_law_encode_i32(L.ptr(x), L.ptr(out), x.numel(), L.stream()))
+    else:
+        L.check(L.lib().vqw_mu_law_encode_i32_levels(L.ptr(x), L.ptr(out), x.numel(), int(levels), L.stream()))
     return out
 
 
-def mu_law_decode_f32(idx, out=None):
+def mu_law_decode_f32(idx, out=None, levels=256):
     L.require_cuda(idx)
     out = torch.empty_like(idx) if out is None else out
-    L.check(L.lib().vqw_mu_law_decode_f32(L.ptr(idx), L.ptr(out), idx.numel(), L.stream()))
+    if levels == 256:
+        L.check(L.lib().vqw_mu_law_decode_f32(L.ptr(idx), L.ptr(out), idx.numel(), L.stream()))
+    else:
+        L.check(L.lib().vqw_mu_law_decode_f32_levels(L.ptr(idx), L.ptr(out), idx.numel(), int(levels), L.stream()))
     return out
 
 
-def wavenet_inputs(x, inputs, labels):
+def wavenet_inputs(x, inputs, labels, levels=256):
     """x [B][T] -> inputs f32 [B][T] (mu-law of shift_right), labels int32 [B][T]."""
     B, T = x.shape
     L.require_cuda(x, inputs, labels)
-    L.check(L.lib().vqw_wavenet_inputs(L.ptr(x), L.ptr(inputs), L.ptr(labels), B, T, L.stream()))
+    if levels == 256:
+        L.check(L.lib().vqw_wavenet_inputs(L.ptr(x), L.ptr(inputs), L.ptr(labels), B, T, L.stream()))
+    else:
+        L.check(L.lib().vqw_wavenet_inputs_levels(L.ptr(x), L.ptr(inputs), L.ptr(labels), B, T, int(levels), L.stream()))
 
 
 def conv_cin1_fwd(x, w, bias, out, *, k, stride, offset, relu=False, scale=None, shift=None, save_r=None):
@@ -787,13 +800,13 @@ def softmax_score(logits, labels, *, t_begin=None, t_end=None, nll=None, entropy
 
 
 def softmax_sample(logits, *, mode='sample', uniforms=None, temperature=1.0, top_k=0, top_p=1.0, t_begin=None, t_end=None,
-                   idx=None, audio=None, probs=None):
+                   idx=None, audio=None, probs=None, levels=256):
     """vqw_softmax_sample: one class for every position of logits fp32 [B][Q][T] over t_begin[b] <= t < t_end[b] (device
     int32 [B]; None: the whole row).  mode 'greedy': the lowest index among the maxima; 'sample': the generators' tempered /
     truncated sampling with uniforms fp32 [B][T] in [0, 1] and temperature / top_k / top_p (scalars or one value per row,
     generator.sampling_settings).  Returns idx int32 [B][T] (-1 outside the range).  audio: optional fp32 [B][T] output, the
-    mu-law decode of idx (Q = 256; 0 outside); probs: optional fp32 [B][T][Q] output, the distribution drawn from (softmax
-    in greedy mode; 0 outside)."""
+    mu-law decode of idx at `levels` levels (Q = levels; 0 outside); probs: optional fp32 [B][T][Q] output, the distribution
+    drawn from (softmax in greedy mode; 0 outside).  levels 256 calls vqw_softmax_sample, 512 / 1024 its _levels form."""
     from .generator import sampling_settings
     if mode not in ('sample', 'greedy'):
         raise ValueError("softmax_sample: mode must be 'sample' or 'greedy' (got %r)" % (mode,))
@@ -818,8 +831,12 @@ def softmax_sample(logits, *, mode='sample', uniforms=None, temperature=1.0, top
     rows = None
     if settings is not None:
         rows = (L.ArSampling * B)(*[L.ArSampling(t, k, p) for t, k, p in settings])
-    L.check(L.lib().vqw_softmax_sample(L.ptr(logits), L.ptr(uniforms) if mode == 'sample' else None, rows, L.ptr(t_begin), L.ptr(t_end),
-                                       1 if mode == 'sample' else 0, L.ptr(idx), L.ptr(audio), L.ptr(probs), B, Q, T, L.stream()))
+    args = (L.ptr(logits), L.ptr(uniforms) if mode == 'sample' else None, rows, L.ptr(t_begin), L.ptr(t_end),
+            1 if mode == 'sample' else 0, L.ptr(idx), L.ptr(audio), L.ptr(probs), B, Q, T)
+    if levels == 256:
+        L.check(L.lib().vqw_softmax_sample(*args, L.stream()))
+    else:
+        L.check(L.lib().vqw_softmax_sample_levels(*args, int(levels), L.stream()))
     return idx
 
 

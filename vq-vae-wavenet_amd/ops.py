@@ -25,24 +25,30 @@ def _btc(x):
     return x.transpose(1, 2).contiguous()
 
 
+MU_LAW_LEVELS = (256, 512, 1024)
+
+
+from .utils import mu_law_levels  # noqa: E402,F401
+
+
 def mu_law_encode(x, quantization_channels=256, to_int=False, one_hot=False):
     """mu_law_ops.py:5-15."""
-    if quantization_channels != 256:
-        raise NotImplementedError('quantization_channels must be 256 (threshold table)')
+    if quantization_channels not in MU_LAW_LEVELS:
+        raise NotImplementedError('quantization_channels must be 256, 512 or 1024 (one threshold table each), got %r' % (quantization_channels,))
     x = x.contiguous()
     if to_int or one_hot:
-        y = K.mu_law_encode_i32(x)
+        y = K.mu_law_encode_i32(x, levels=quantization_channels)
         if one_hot:
             return torch.nn.functional.one_hot(y.long(), quantization_channels).float().squeeze(-2)
         return y
-    return K.mu_law_encode_f32(x)
+    return K.mu_law_encode_f32(x, levels=quantization_channels)
 
 
 def mu_law_decode(y, quantization_channels=256):
     """mu_law_ops.py:18-31 (TF and numpy twins)."""
-    if quantization_channels != 256:
-        raise NotImplementedError('quantization_channels must be 256')
-    return K.mu_law_decode_f32(y.float().contiguous())
+    if quantization_channels not in MU_LAW_LEVELS:
+        raise NotImplementedError('quantization_channels must be 256, 512 or 1024, got %r' % (quantization_channels,))
+    return K.mu_law_decode_f32(y.float().contiguous(), levels=quantization_channels)
 
 
 mu_law_decode_np = mu_law_decode

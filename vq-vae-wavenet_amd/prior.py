@@ -64,6 +64,7 @@ class LatentPrior(WaveNet):
         if n_codes is not None and int(n_codes) != int(cfg['quantization_channels']):
             raise ValueError('prior quantization_channels %d != codebook size %d' % (cfg['quantization_channels'], n_codes))
         super().__init__(cfg, cfg, num_speakers, device=device, seed=seed)
+        self.levels = 256      # the classes are VQ codes: there is no mu-law here, whatever their number
 
     # ------------------------------------------------------------------ hooks of WaveNet
     def _setup_front(self, cfg, num_speakers):

@@ -9,6 +9,12 @@ import numpy as np
 _MU_LEVELS = {}
 
 
+def mu_law_levels(quantization_channels):
+    """The mu-law level a decoder with this many output classes compands with: the class count itself at 512 and 1024,
+    otherwise 256 (the reference's only level; any other class count runs as it always has)."""
+    return int(quantization_channels) if int(quantization_channels) in (512, 1024) else 256
+
+
 def _decode_table(quantization_channels):
     """All decode levels at once: index i -> sign(y) ((1 + mu)^|y| - 1) / mu with y = 2 i / mu - 1, in numpy fp32
     (mu_law_ops.py:26-31); one extra entry for the index `quantization_channels` that sampling can return when

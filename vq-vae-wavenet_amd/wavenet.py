@@ -22,6 +22,7 @@ import torch
 
 from . import _alloc as A
 from . import kernels as K
+from .utils import mu_law_levels
 
 DEFAULT_ENGINE = 'f16x3'
 
@@ -140,6 +141,9 @@ class WaveNet:
         self.L = len(self.dil)
         self.ks = w['kernel_size']
         self.R, self.S, self.Q = w['residual_filters'], w['skip_filters'], w['quantization_channels']
+        # the mu-law level of labels, decoder input and generated audio: Q at 512 and 1024, otherwise 256 (which leaves every
+        # other Q exactly as it has always run; only 256, 512 and 1024 are mu-law models).  LatentPrior has no mu-law.
+        self.levels = mu_law_levels(self.Q)
         if w['dilation_filters'] != self.R or w['preprocess']['filters'] != self.R:
             raise NotImplementedError('dilation_filters / preprocess filters must equal residual_filters '
                                       '(the reference adds them: wavenet.py:73)')
@@ -443,7 +447,8 @@ class WaveNet:
         if self.skip_f16x3:
             ws['wskip'], ws['wres'] = h(2 * L * R * S), h(L, 2 * R * R)
             if self._head_on_engine():
-                ws['hp'], ws['hp2'] = h(2 * B * S * T), h(2 * B * S * T)   # relu(skip) / d postprocess1, relu(postprocess1) / d logits
+                # relu(skip) / d postprocess1 (S channels); relu(postprocess1) (S) / d logits (Q channels: more than S at 1024 levels)
+                ws['hp'], ws['hp2'] = h(2 * B * S * T), h(2 * B * max(S, Q) * T)
                 for name, n_ in (('wskip0', R * S), ('wpost1', S * S), ('wpost2', S * Q)):
                     for sfx in (('', 't') if train else ('',)):      # (+ 't': the transposed kernel of the input gradient)
                         ws[name + sfx] = h(2 * n_)
@@ -615,7 +620,8 @@ class WaveNet:
 
     def _decode_input(self, x, ws):
         """The input stage: labels and net[0] = the preprocess conv of the shifted input (hook)."""
-        K.wavenet_inputs(x, ws['inputs'], ws['labels'])                                   # wavenet.py:33-37
+        lv = {} if self.levels == 256 else {'levels': self.levels}     # (256: the call as it has always been)
+        K.wavenet_inputs(x, ws['inputs'], ws['labels'], **lv)                             # wavenet.py:33-37
         K.conv_cin1_fwd(ws['inputs'], self.P['pre_w'], self.P['pre_b'], ws['net'][0], k=self.pre_k, stride=1,
                         offset=-(self.pre_k - 1))                                         # wavenet.py:42-44
 
@@ -868,7 +874,8 @@ class WaveNet:
             out_audio = torch.empty(B, T, device=self.dev) if audio else None
             probs = torch.empty(B, T, Q, device=self.dev) if return_probs else None
             idx = K.softmax_sample(ws['logits'], mode=mode, uniforms=u, temperature=temperature, top_k=top_k, top_p=top_p,
-                                   t_end=t_end, audio=out_audio, probs=probs)
+                                   t_end=t_end, audio=out_audio, probs=probs,
+                                   **({} if self.levels == 256 else {'levels': self.levels}))
             torch.cuda.synchronize(self.dev)
             out = ((out_audio,) if audio else ()) + (idx,) + ((probs,) if return_probs else ())
             return out if len(out) > 1 else out[0]
