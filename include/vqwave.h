@@ -346,6 +346,25 @@ int vqw_code_histogram(const int64_t* idx, const int32_t* f_end, int32_t* counts
                        vqw_stream_t s);
 
 /* ------------------------------------------------------------------------------------
+ * Dynamic time warping between cepstral sequences (mel-cepstral distortion; scoring.mcd).
+ * a [P][C][Ta], b [P][C][Tb]: the layout vqw_mfcc writes, frames innermost.  Pair p compares frames 0 .. na[p]-1 of a with
+ * frames 0 .. nb[p]-1 of b on the channels d0 .. d0+D-1 (d0 = 1, D = 12 leaves out the energy coefficient c0).  na / nb:
+ * device int32 [P], either may be NULL: Ta / Tb; a length is CLAMPED to [1, Ta] / [1, Tb].  Every operation is ONE correctly
+ * rounded fp32 operation, no fused multiply-add:
+ *   c(i,j)   = sqrt(sum_d sq_d),  sq_d = x * x,  x = a[d][i] - b[d][j];  the sum ascends in d from +0.0f, one add per term
+ *   Dp(0,0)  = c(0,0),  n(0,0) = 1
+ *   Dp(i,j)  = c(i,j) + Dp(pred),  n(i,j) = n(pred) + 1,  pred chosen among the neighbours that exist in the order
+ *              (i-1,j-1), (i-1,j), (i,j-1): a later one replaces an earlier one only if its Dp is STRICTLY smaller
+ *              (the symmetric step pattern, no slope weights, no band)
+ *   cost[p]  = Dp(na-1, nb-1) (fp32),  steps[p] = n(na-1, nb-1) (int32): the number of cells on the chosen path
+ * Nothing at or past frame na[p] / nb[p] is read; no atomics; a pair's result depends on that pair alone (not on P or its
+ * position).  Non-finite input is not special-cased (the values are then unspecified, the reads stay in range).
+ * P >= 1; D >= 1, d0 >= 0, d0 + D <= C; 1 <= Ta, Tb <= 4096 (three anti-diagonals of (cost, steps) in LDS).  One workgroup
+ * per pair, one barrier per anti-diagonal: na + nb - 1 of them.                                                        */
+int vqw_cepstral_dtw(const float* a, const float* b, const int32_t* na, const int32_t* nb, float* cost, int32_t* steps,
+                     int P, int C, int d0, int D, int Ta, int Tb, vqw_stream_t s);
+
+/* ------------------------------------------------------------------------------------
  * The decoder's local-condition projections -- add_condition, wavenet_ops.py:93-101: a 1x1 conv1d_v2 of the condition
  * per gated_cnn and for postprocess1 (wavenet.py:58-100).  All L + 1 kernels side by side are one matrix
  * w[Cc][Mall] (Mall = L * 2R + S); cond [B][Cc][Tz], out / dce [B][Mall][Tz], dcond [B][Cc][Tz].

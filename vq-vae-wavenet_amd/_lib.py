@@ -153,6 +153,7 @@ SIGNATURES = {
     'vqw_softmax_xent_bwd': (_i, [_fp, _fp, _fp, _f, _i, _i, _i, _fp]),
     'vqw_softmax_score': (_i, [_fp] * 9 + [_i64, _i, _i, _i, _fp]),
     'vqw_code_histogram': (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp]),
+    'vqw_cepstral_dtw': (_i, [_fp] * 6 + [_i, _i, _i, _i, _i, _i, _fp]),
     'vqw_softmax_sample': (_i, [_fp, _fp, C.POINTER(ArSampling), _fp, _fp, _i, _fp, _fp, _fp, _i, _i, _i, _fp]),
     'vqw_softmax_sample_levels': (_i, [_fp, _fp, C.POINTER(ArSampling), _fp, _fp, _i, _fp, _fp, _fp, _i, _i, _i, _i, _fp]),
     'vqw_cond_proj_fwd': (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _fp]),

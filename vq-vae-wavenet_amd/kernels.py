@@ -853,6 +853,33 @@ def code_histogram(idx, counts, flag, *, f_end=None):
     L.check(L.lib().vqw_code_histogram(L.ptr(idx), L.ptr(f_end), L.ptr(counts), L.ptr(flag), B, Tz, counts.numel(), L.stream()))
 
 
+def cepstral_dtw(a, b, *, na=None, nb=None, d0=1, D=12, cost=None, steps=None):
+    """vqw_cepstral_dtw: the DTW cost and path length of every pair of a fp32 [P][C][Ta] and b fp32 [P][C][Tb] (mfcc's output
+    layout) on channels d0 .. d0+D-1, over frames 0 .. na[p]-1 / 0 .. nb[p]-1 (device int32 [P]; None: all; clamped to
+    [1, Ta] / [1, Tb]).  Returns (cost fp32 [P], steps int32 [P]).  The shape limits (D, d0, C, Ta, Tb <= 4096) are the
+    library's to refuse; here only what the pointers must cover is checked."""
+    if a is None or b is None:
+        raise ValueError('a and b are required')
+    if a.dim() != 3 or b.dim() != 3 or a.shape[:2] != b.shape[:2]:
+        raise ValueError('a must be [P][C][Ta] and b [P][C][Tb] with the same P and C (got %s and %s)' % (tuple(a.shape), tuple(b.shape)))
+    P, Cn, Ta = a.shape
+    Tb = b.shape[2]
+    dev = a.device
+    if cost is None:
+        cost = torch.empty(P, dtype=torch.float32, device=dev)
+    if steps is None:
+        steps = torch.empty(P, dtype=torch.int32, device=dev)
+    L.require_cuda(a, b, na, nb, cost, steps)
+    _need(a, P * Cn * Ta, 'a')
+    _need(b, P * Cn * Tb, 'b')
+    _need(cost, P, 'cost')
+    for t, nm in ((na, 'na'), (nb, 'nb'), (steps, 'steps')):
+        _need_i32(t, P, nm)
+    L.check(L.lib().vqw_cepstral_dtw(L.ptr(a), L.ptr(b), L.ptr(na), L.ptr(nb), L.ptr(cost), L.ptr(steps), P, Cn, int(d0), int(D),
+                                     Ta, Tb, L.stream()))
+    return cost, steps
+
+
 def cond_proj_fwd(cond, w, out, *, B, Cc, Mall, Tz):
     """out[b][m][t] = sum_c w[c][m] cond[b][c][t]: every add_condition projection of the decoder in one launch (wavenet_ops.py:93-101)."""
     _need(cond, B * Cc * Tz, 'cond')

@@ -256,6 +256,19 @@ def mfcc(audio, mel=None):
     return _btc(out)
 
 
+def dtw(a, b, na=None, nb=None, d0=1, D=12):
+    """Dynamic time warping of cepstra a [P, Ta, C] against b [P, Tb, C] (what `mfcc` returns) on the coefficients
+    d0 .. d0+D-1 (the default leaves out c0), over the first na[p] / nb[p] frames (lists or int tensors of P; None: all).
+    Returns (cost fp32 [P], steps int32 [P]): the accumulated Euclidean frame distance along the optimal symmetric-step path
+    and the number of cells on it, one vqw_cepstral_dtw launch (include/vqwave.h has the arithmetic).  No counterpart in the
+    reference; scoring.mcd calls the kernel on mfcc's own [P, C, T] layout and skips the two transposes made here."""
+    dev = a.device
+
+    def lengths(n):
+        return None if n is None else torch.as_tensor(n).to(device=dev, dtype=torch.int32).contiguous()
+    return K.cepstral_dtw(_bct(a), _bct(b), na=lengths(na), nb=lengths(nb), d0=d0, D=D)
+
+
 def concat(net, global_condition):
     """decoder_ops.py:39-43."""
     return torch.cat([net, global_condition.expand(-1, net.shape[1], -1)], dim=-1)

@@ -4,10 +4,82 @@ Pure Python over small host arrays (no GPU needed):
     bits(nll_sum, count)   = nll_sum / (count * ln 2)            bits per scored position
     perplexity(counts)     = exp(-sum p ln p),  p = counts / counts.sum(), zeros ignored, float64
     used(counts)           = number of codes that occur at all
+
+Conversion scoring (mcd, on the GPU): mel-cepstral distortion between a converted utterance x and the target speaker's own
+recording y of the same sentence, in dB:
+
+    MCD(x, y) = (10 sqrt(2) / ln 10) * (1 / N) * sum over the DTW path (i, j) of  sqrt(sum_{d=1..12} (cx[d][i] - cy[d][j])^2)
+
+with N the number of cells on the path.  The path is the symmetric-step DTW alignment (no slope weights, no band) that
+minimises the summed frame distance; c0 (energy) is left out.  The cepstra cx, cy are the 13 MFCCs of vqw_mfcc / ops.mfcc
+(frame 400, step 160 at 16 kHz: 100 frames per second; 80 mel bins, log, DCT-II): NOT the mel-generalised cepstra (MGC, e.g.
+SPTK mcep order 24) that published MCD figures usually rest on, so the number compares systems scored HERE with one
+another and is not comparable with figures from papers.
 """
+import collections
 import math
 
 import numpy as np
+
+FRAME_STEP = 160                                           # vqw_mfcc: samples per cepstral frame
+MAX_FRAMES = 4096                                          # vqw_cepstral_dtw's bound (41 s)
+MCD_K = 10.0 * math.sqrt(2.0) / math.log(10.0)             # 6.1418...: Euclidean cepstral distance -> dB
+
+MCD = collections.namedtuple('MCD', 'mcd cost steps frames_x frames_y')
+_mel = {}
+
+
+def frames_of(n):
+    """Cepstral frames of an utterance of n samples: ceil(n / 160) (stft with pad_end)."""
+    return -(-int(n) // FRAME_STEP)
+
+
+def mcd(x, y, nx=None, ny=None):
+    """Mel-cepstral distortion of every pair (x[p], y[p]).  x fp32 [P][Tx], y fp32 [P][Ty]: audio on the GPU, each row ZERO
+    beyond its nx[p] / ny[p] samples (lists of P; None: whole rows).  Per pair: the MFCCs of both sides (ops.mfcc's kernel,
+    written as [P][13][frames], which is the layout vqw_cepstral_dtw reads), frames = ceil(n / 160), then the DTW over
+    coefficients 1..12.  Two mfcc launches and one dtw launch per call; the cost and path length come back to the host and
+    mcd = MCD_K * cost / steps is formed there in float64.  Returns MCD(mcd float64 [P], cost float32 [P], steps int32 [P],
+    frames_x int32 [P], frames_y int32 [P]) as numpy arrays.  A pair's numbers do not depend on the rest of the batch."""
+    import torch
+    from . import kernels as K
+    from .encoders import mel_weight_matrix
+    if x.dim() != 2 or y.dim() != 2 or x.shape[0] != y.shape[0]:
+        raise ValueError('mcd: x must be [P][Tx] and y [P][Ty] with the same P (got %s and %s)' % (tuple(x.shape), tuple(y.shape)))
+    if x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise ValueError('mcd: audio must be float32 (got %s and %s)' % (x.dtype, y.dtype))
+    P = x.shape[0]
+    frames = []
+    for n, t, what in ((nx, x, 'nx'), (ny, y, 'ny')):
+        n = [t.shape[1]] * P if n is None else [int(v) for v in n]
+        if len(n) != P or min(n) < 1 or max(n) > t.shape[1]:
+            raise ValueError('mcd: %s must hold %d sample counts in 1..%d (got %s)' % (what, P, t.shape[1], n[:8]))
+        frames.append(np.array([frames_of(v) for v in n], dtype=np.int32))
+    dev = x.device
+    if dev not in _mel:
+        _mel[dev] = mel_weight_matrix().to(dev).contiguous()
+    cep = []
+    for t in (x, y):
+        c = torch.empty(P, 13, frames_of(t.shape[1]), device=dev)
+        K.mfcc(t.contiguous(), _mel[dev], c, n_keep=13)
+        cep.append(c)
+    na, nb = (torch.from_numpy(f).to(dev) for f in frames)
+    cost, steps = K.cepstral_dtw(cep[0], cep[1], na=na, nb=nb, d0=1, D=12)
+    cost, steps = cost.cpu().numpy(), steps.cpu().numpy()
+    return MCD(MCD_K * cost.astype(np.float64) / steps.astype(np.float64), cost, steps, frames[0], frames[1])
+
+
+def mcd_report(results, missing=0):
+    """The report of score_conversion.py from a list of MCD results (one per batch): pairs, missing, the mean MCD per pair,
+    the frame-weighted mean sum(MCD_K * cost) / sum(steps), min, max and the total frames of both sides.  float64 sums in
+    list order."""
+    m = np.concatenate([r.mcd for r in results])
+    cost = np.concatenate([r.cost for r in results]).astype(np.float64)
+    steps = np.concatenate([r.steps for r in results]).astype(np.int64)
+    frames = int(sum(int(r.frames_x.sum()) + int(r.frames_y.sum()) for r in results))
+    return {'pairs': int(m.size), 'missing': int(missing), 'mcd_mean': float(m.mean()),
+            'mcd_frame_weighted': float(MCD_K * cost.sum() / steps.sum()), 'mcd_min': float(m.min()), 'mcd_max': float(m.max()),
+            'frames': frames, 'path_steps': int(steps.sum())}
 
 
 def bits(nll_sum, count):
