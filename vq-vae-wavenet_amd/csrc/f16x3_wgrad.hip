@@ -1,6 +1,7 @@
 // fp16x3 engine: weight gradients.  Two kernels over one work decomposition (WgArgs, wg_decode) and one slab reduction:
 //   wgrad_f16x3_kernel<ODD, BF, S2, QP, PP>  the register loop: at least one operand is read as fp32 and converted on the way to LDS
-//   wgrad_f16x3_dma_kernel<BF>               both operands as planes: global -> LDS by LDS-DMA, nothing passes through registers
+//   wgrad_f16x3_dma_kernel<BF>               both operands as planes: global -> LDS by LDS-DMA, nothing passes through registers;
+//                                            2 x 2 wave tiling, q sums only in the blocks that use them
 // wg_kernel() maps a launch to one of the 13 instantiations and its LDS bytes.
 #include <string.h>
 
@@ -487,16 +488,35 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_kernel(const WgArgs a) {
 // go global -> LDS by LDS-DMA (x3_dma16) into a ring of WG_DMA_NSTG 16-step stages, as in the conv main loop (f16x3_mainloop): no
 // rgp / rgq, no ds_write, no commit.  A DMA writes lane-linear 1-KiB pieces, which rules the padded rows out: the image is the
 // XOR-permuted one of f16x3_wgrad_layout.h (8 KiB per plane and stage, no padding).  A tap's shift is a row offset of p's planes.
+// The four waves tile the block 2 x 2 (128 rows x 128 columns each, acc[4][4]: 8 A + 8 B fragments per step where 256 rows x 64
+// columns took 16 + 4), and the q sums are formed only where they are used: the loop body is chosen in front of the loop.
 template <bool BF> struct WgDmaStage {
     static constexpr int BOFF = (BF ? 1 : 2) * wgl::PLANE, BYTES = 2 * BOFF, STAGES = WG_DMA_NSTG;      // q image behind the p image
 };
+// 12 MFMAs (bf16: 4): row tile i x the wave's 4 column tiles, the three terms outermost (small first): two MFMAs into the same
+// accumulator are three independent ones apart, and every accumulator sees its terms in wg_mfma_rows' order
+template <bool BF>
+__device__ __forceinline__ void wg_mfma_row4(f32x16 (&acc)[4][4], const uint4 (&fa)[4][2], const uint4 (&b)[4][2], int i) {
+    if constexpr (BF) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[i][0]), __builtin_bit_cast(bf16x8, b[j][0]), acc[i][j], 0, 0, 0);
+    } else {
+#pragma unroll
+        for (int term = 0; term < 3; ++term)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int pa = term == 1 ? 1 : 0, pb = term == 0 ? 1 : 0;
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[i][pa]), __builtin_bit_cast(f16x8, b[j][pb]), acc[i][j], 0, 0, 0);
+            }
+    }
+}
+
 template <bool BF>
 __global__ __launch_bounds__(256, 1) void wgrad_f16x3_dma_kernel(const WgArgs a) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     constexpr int STGB = WgDmaStage<BF>::BYTES, BOFF = WgDmaStage<BF>::BOFF, NPL = BF ? 1 : 2;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
-    // (the register kernel's prologue without its fp32 sources and per-plane resources; statement by statement in its order -- the
-    // second planes' offsets where it forms them -- or the kernel compiles to other code)
     const WgItem it = wg_decode(vqw_xcd_remap(blockIdx.x, gridDim.x), a);
     const WgProblem& pr = a.pr[it.prob];
     const int split = it.split, tap = it.tap, c0 = it.rtl * 256;
@@ -515,10 +535,16 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_dma_kernel(const WgArgs a)
     const size_t pl1p = !BF ? (size_t)pr.p_KC * NBq * 16 : 0;
     float* const q_total = pr.q_total;
     float* const q_seg = pr.q_seg;
-    // q sums, from the B fragments: lane (channel l31, k half lhi) of the thread's two column tiles
+    const int wvu = __builtin_amdgcn_readfirstlane(wv);
+    // 2 x 2 wave tiling (f16x3_wgrad_layout.h): wave (wr, wc) owns row tiles 4 wr + i, column tiles 4 wc + j
+    const int wr = wvu >> 1, wc = wvu & 1;
+    // q sums, from the B fragments: lane (channel l31, k half lhi) of column tiles j = 2 wr, 2 wr + 1 of the wave's four
     const bool do_sum = it.rtl == 0 && tap == 0 && (q_seg != nullptr || (q_total != nullptr && o0 < a.total_o1 && o0 + 256 > a.total_o0));
     float qs_pair[2] = {0.f, 0.f}, qs_tot[2] = {0.f, 0.f};
     const float inv_scq = __builtin_amdgcn_rcpf(scq);
+    const int sum_row0 = o0 + (4 * wc + 2 * wr) * 32 + l31;
+    static_assert(wgl::wave_b_tile(0, wgl::wave_sum_j(0, 0)) == 0 && wgl::wave_b_tile(1, wgl::wave_sum_j(1, 0)) == 4 &&
+                  wgl::wave_b_tile(2, wgl::wave_sum_j(2, 0)) == 2 && wgl::wave_b_tile(3, wgl::wave_sum_j(3, 0)) == 6, "first summed column tile: 4 wc + 2 wr");
     auto sum_frag = [&](const uint4 (&b)[2][2]) { wg_sum_frag<BF>(qs_pair, b, inv_scq); };
     auto flush_pair = [&](int s) {         // pair s is complete in qs_pair: add it to its condition frame, fold it into the totals
 #pragma unroll
@@ -528,27 +554,26 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_dma_kernel(const WgArgs a)
             qs_pair[h] = 0.f;
             if (q_seg && lhi == 0) {
                 const int b = s / a.pairs_row, t0 = (s - b * a.pairs_row) * 32;
-                const int row = o0 + (wv * 2 + h) * 32 + l31;
+                const int row = sum_row0 + h * 32;
                 unsafeAtomicAdd(q_seg + (size_t)b * a.seg_bstride + (size_t)row * a.seg_T + t0 / a.seg_ratio, both);
             }
         }
     };
-    uint4 fa[8][2], fb[2][2];                        // A fragments (both planes) of 8 row tiles, B fragments of this wave's 2 column tiles
-    f32x16 acc[8][2];
+    uint4 fa[4][2], fb[4][2];                        // A fragments (both planes) of the wave's 4 row tiles, B fragments of its 4 column tiles
+    f32x16 acc[4][4];
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     const int npairs = s_end - s_begin;
-    // One step = one 16-step stage: pair s of the K range is steps 2 (s - s_begin), 2 (s - s_begin) + 1, so the stages -- and with
-    // them the fragments and the order of the MFMAs -- are those of the register kernel and dW is the same bit for bit.
+    // One step = one 16-step stage, as in the register kernel: per accumulator the stages and the three terms come in its order,
+    // so dW is the same bit for bit (only the order ACROSS accumulators differs).
     constexpr int P = 4 * NPL;             // 1-KiB pieces a wave requests per stage: 2 operands x NPL planes x 8 pieces over 4 waves
-    const int wvu = __builtin_amdgcn_readfirstlane(wv);
     // Piece w = wvu * P + k of a stage, in image order: operand (p, q), plane, time half, chunk group.  Two planes: wave 0 / 1 move
     // p's plane 0 / 1, wave 2 / 3 q's; one plane (bf16): wave 0 / 1 move p's time half 0 / 1, wave 2 / 3 q's.  A wave therefore
-    // requests from ONE resource with ONE shift (q: none).
+    // requests from ONE resource with ONE shift (q: none).  (Which wave MOVES a piece has nothing to do with which waves read it.)
     const bool w_is_p = wvu < 2;
     const int w_plane = BF ? 0 : (wvu & 1), w_shift = w_is_p ? shift : 0;
     // (requests past the block's last stage, rows outside the batch row and steps behind T carry the offset 2^31, outside every
@@ -584,24 +609,21 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_dma_kernel(const WgArgs a)
         rq_row += wrap ? T * 16 : 0;
     };
     const int trl = wgl::tr_lane(lane);
-    auto read_a = [&](int i, int stage) {
-        const char* st = smem + (stage % WG_DMA_NSTG) * STGB + wgl::piece_off(0, 0, i >> 1) + (trl ^ ((i & 1) * 64));
+    const int a_off = wr * wgl::wave_a_off(2), b_off = BOFF + wc * wgl::wave_b_off(1);
+    static_assert(wgl::wave_a_off(0) == 0 && wgl::wave_a_off(1) == 0 && wgl::wave_a_off(3) == wgl::wave_a_off(2) &&
+                  wgl::wave_b_off(0) == 0 && wgl::wave_b_off(2) == 0 && wgl::wave_b_off(3) == wgl::wave_b_off(1), "wave terms of the read maps");
+    auto read_frag = [&](uint4 (&f)[4][2], int k, int base, int stage) {     // wgl::wave_addr_split
+        const char* st = smem + (stage % WG_DMA_NSTG) * STGB + base + wgl::piece_off(0, 0, k >> 1) + (trl ^ ((k & 1) * 64));
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl) {
             const uint2 k0 = wg_tr_read(st + pl * wgl::PLANE), k1 = wg_tr_read(st + pl * wgl::PLANE + 4 * wgl::SLOTS * 16);
-            fa[i][pl] = make_uint4(k0.x, k0.y, k1.x, k1.y);
+            f[k][pl] = make_uint4(k0.x, k0.y, k1.x, k1.y);
         }
     };
-    auto read_b = [&](uint4 (&b)[2][2], int stage) {
-        const char* st = smem + (stage % WG_DMA_NSTG) * STGB + BOFF + wv * wgl::PIECE;
+    auto read_a = [&](int i, int stage) { read_frag(fa, i, a_off, stage); };
+    auto read_b = [&](uint4 (&b)[4][2], int stage) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) {
-                const char* sj = st + (trl ^ (j * 64)) + pl * wgl::PLANE;
-                const uint2 k0 = wg_tr_read(sj), k1 = wg_tr_read(sj + 4 * wgl::SLOTS * 16);
-                b[j][pl] = make_uint4(k0.x, k0.y, k1.x, k1.y);
-            }
+        for (int j = 0; j < 4; ++j) read_frag(b, j, b_off, stage);
     };
     // The compiler does not count the requests (x3_dma16): every wait for them is written here.  Never __syncthreads() while one
     // is in flight -- its fence would drain the ring.
@@ -611,42 +633,64 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_dma_kernel(const WgArgs a)
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(N) : "memory");
     };
     if (npairs > 0) {
-        uint4 fbn[2][2];
+        uint4 fbn[4][2];
 #pragma unroll
         for (int s = 0; s < WG_DMA_NSTG; ++s) { request(0, P); advance(); }
         wait_barrier(std::integral_constant<int, (WG_DMA_NSTG - 1) * P>{});
 #pragma unroll
-        for (int i = 0; i < 8; ++i) read_a(i, 0);
+        for (int i = 0; i < 4; ++i) read_a(i, 0);
         read_b(fb, 0);
         // Step s (one barrier): the wait retires this wave's pieces of stage s + 1 (DEPTH newer stages stay in flight) and its
         // fragment reads of stage s; behind the barrier stage s + 1 is complete and slot s % NSTG is free, so stage s + NSTG is
-        // requested into it, in four even parts behind the fragment reads of stage s + 1, all in the shadow of stage s's MFMAs.
-        // No conditionals in the body; the last step re-reads its own stage (never used).
-        auto step = [&](const uint4 (&bc)[2][2], uint4 (&bn)[2][2], int s) {
-            wait_barrier(std::integral_constant<int, WG_DMA_DEPTH * P>{});
-            const int sn = s + 1 < nsteps ? s + 1 : s;
-            sum_frag(bc);
-            read_b(bn, sn);
+        // requested into it, in four even parts, each behind a row tile's MFMAs and the refill of its A fragments from stage
+        // s + 1 -- all in the shadow of stage s's MFMAs.  No conditionals in the body; the last step re-reads its own stage
+        // (never used).
+        // The body exists three times, chosen once in front of the loop (do_sum is block-uniform, wr wave-uniform; the waves of a
+        // block meet at the barriers whichever body they run): SUMS = 0 without q sums -- two thirds of the gate batches' blocks
+        // and every block of the skip halves, where the sums were formed and dropped --, SUMS = 1 / 2 with the sums of column
+        // tiles 0, 1 / 2, 3 of the wave's four.
+        // (flush_on is do_sum again, hidden from the compiler: with the flush behind a branch the summing body is the loop it was
+        // before the bodies were split -- packed adds, 204 vector ALU instructions per pair; with the flush inline the six-layer
+        // batch, whose summing blocks finish last, took 731-734 instead of 718-726 us.)
+        int flush_on = __builtin_amdgcn_readfirstlane((int)do_sum);
+        asm volatile("" : "+s"(flush_on));
+        auto loop = [&](auto sums_c) {
+            constexpr int SUMS = decltype(sums_c)::value;
+            auto step = [&](const uint4 (&bc)[4][2], uint4 (&bn)[4][2], int s) {
+                wait_barrier(std::integral_constant<int, WG_DMA_DEPTH * P>{});
+                const int sn = s + 1 < nsteps ? s + 1 : s;
+                if constexpr (SUMS != 0) {
+                    constexpr int j0 = wgl::wave_sum_j(2 * (SUMS - 1), 0);
+                    static_assert(wgl::wave_sum_j(2 * (SUMS - 1), 1) == j0 + 1 && wgl::wave_sum_j(2 * (SUMS - 1) + 1, 0) == j0, "the wave's summed column tiles");
+                    const uint4 bs[2][2] = {{bc[j0][0], bc[j0][1]}, {bc[j0 + 1][0], bc[j0 + 1][1]}};
+                    sum_frag(bs);
+                }
+                read_b(bn, sn);
 #pragma unroll
-            for (int i = 0; i < 8; i += 2) {
-                wg_mfma_rows<BF>(acc, fa, bc, i);
-                read_a(i, sn);
-                read_a(i + 1, sn);
-                request(P * (i / 2) / 4, P * (i / 2 + 1) / 4);
-            }
-            advance();
+                for (int i = 0; i < 4; ++i) {
+                    wg_mfma_row4<BF>(acc, fa, bc, i);
+                    read_a(i, sn);
+                    request(P * i / 4, P * (i + 1) / 4);
+                }
+                advance();
 #pragma unroll
-            for (int k_ = 0; k_ < (BF ? 2 : 6) * 8; ++k_) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100 | 0x200 | 0x020, BF ? 2 : VQW_WG_DMA_PAT_MEM, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002 | 0x004, VQW_WG_DMA_PAT_ALU, 0);
+                for (int k_ = 0; k_ < (BF ? 2 : 6) * 8; ++k_) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100 | 0x200 | 0x020, BF ? 2 : VQW_WG_DMA_PAT_MEM, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002 | 0x004, VQW_WG_DMA_PAT_ALU, 0);
+                }
+            };
+            for (int s = 0; s < nsteps; s += 2) {
+                step(fb, fbn, s);
+                step(fbn, fb, s + 1);
+                if constexpr (SUMS != 0) {
+                    if (flush_on) flush_pair(s_begin + (s >> 1));     // both stages of the pair are in qs_pair
+                }
             }
         };
-        for (int s = 0; s < nsteps; s += 2) {
-            step(fb, fbn, s);
-            step(fbn, fb, s + 1);
-            if (do_sum) flush_pair(s_begin + (s >> 1));     // both stages of the pair are in qs_pair
-        }
+        if (!do_sum) loop(std::integral_constant<int, 0>{});
+        else if (wr == 0) loop(std::integral_constant<int, 1>{});
+        else loop(std::integral_constant<int, 2>{});
         // the requests past the last stage: nothing of the loop may be in flight when the slab stores start
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -654,22 +698,22 @@ __global__ __launch_bounds__(256, 1) void wgrad_f16x3_dma_kernel(const WgArgs a)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const float both = qs_tot[h] + __shfl_xor(qs_tot[h], 32, 64);
-            const int row = o0 + (wv * 2 + h) * 32 + l31;
+            const int row = sum_row0 + h * 32;
             if (lhi == 0 && row >= a.total_o0 && row < a.total_o1) unsafeAtomicAdd(q_total + row, both);
         }
     }
-    // ---- partial tile -> slab, as in wgrad_f16x3_kernel
+    // ---- partial tile -> slab [tile][split][256][256], rows c, columns o (32 lanes = 128 contiguous bytes): the wave's quadrant
     const float inv = __builtin_amdgcn_rcpf(scp * scq);
-    float* out = a.slab + ((size_t)it.gtile * a.nsplit + split) * 65536;
+    float* out = a.slab + ((size_t)it.gtile * a.nsplit + split) * 65536 + (128 * wr) * 256 + 128 * wc;
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int v4 = 0; v4 < 4; ++v4)
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    out[(32 * i + 8 * v4 + 4 * lhi + e) * 256 + 64 * wv + 32 * j + l31] = acc[i][j][v4 * 4 + e] * inv;
+                for (int j = 0; j < 4; ++j)
+                    out[(32 * i + 8 * v4 + 4 * lhi + e) * 256 + 32 * j + l31] = acc[i][j][v4 * 4 + e] * inv;
 }
 
 // dW[tap][c][o] += sum over splits (fixed order) of the slab tiles; grid (64, tiles of all problems)

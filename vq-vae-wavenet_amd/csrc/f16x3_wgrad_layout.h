@@ -38,6 +38,20 @@ constexpr int tr_addr_split(int lane, int tile, int khalf) {
     return piece_off(0, 0, tile >> 1) + (tr_lane(lane) ^ ((tile & 1) * 64)) + khalf * 4 * (SLOTS * 16);
 }
 
+// 2 x 2 wave tiling of the 256 x 256 output tile: wave (wr, wc) = (wave >> 1, wave & 1) owns rows 128 wr .. and columns 128 wc ..,
+// i.e. row tiles 4 wr + i of p and column tiles 4 wc + j of q (i, j = 0..3): 8 A + 8 B fragments per step instead of 16 + 4.
+constexpr int WAVES = 4, WTILES = 4;
+constexpr int wave_a_tile(int wave, int i) { return WTILES * (wave >> 1) + i; }
+constexpr int wave_b_tile(int wave, int j) { return WTILES * (wave & 1) + j; }
+// the q sums of a column tile are formed by one of the two waves that read it: wave (wr, wc) sums j = 2 wr + h (h = 0, 1) of its four
+constexpr int wave_sum_j(int wave, int h) { return 2 * (wave >> 1) + h; }
+// The kernel forms a fragment's address from a wave term (per operand), the lane term, an XOR for odd tiles and constants:
+constexpr int wave_a_off(int wave) { return piece_off(0, 0, 2 * (wave >> 1)); }
+constexpr int wave_b_off(int wave) { return piece_off(0, 0, 2 * (wave & 1)); }
+constexpr int wave_addr_split(int wave_off, int lane, int k, int khalf) {      // k: the wave's own tile index i or j
+    return wave_off + piece_off(0, 0, k >> 1) + (tr_lane(lane) ^ ((k & 1) * 64)) + khalf * 4 * (SLOTS * 16);
+}
+
 // ---- compile-time checks
 // what the DMA puts at byte `a` of a plane's image: (time step of the stage) * 256 + channel
 constexpr int dma_content(int a) {
@@ -102,7 +116,44 @@ constexpr bool check_banks() {
             }
     return true;
 }
+// (d) the 2 x 2 wave tiling: the kernel's address of every (wave, own tile, k half) is the checked read map (b, c) at the tile the
+// wave owns -- so every fragment element is its (channel, time step) and no two lanes of a half share a bank, in every plane (a
+// plane is an offset of PLANE: the same banks) --, the 4 x 16 (row tile, column tile) pairs of the waves are the tile's 64, each
+// once, and every column tile is summed by exactly one wave, from a fragment that wave reads.
+constexpr bool check_wave_tiling() {
+    int owners[8][8] = {}, summed[8] = {};
+    for (int wave = 0; wave < WAVES; ++wave) {
+        for (int k = 0; k < WTILES; ++k)
+            for (int kh = 0; kh < 2; ++kh)
+                for (int lane = 0; lane < 64; ++lane) {
+                    if (wave_addr_split(wave_a_off(wave), lane, k, kh) != tr_addr(lane, wave_a_tile(wave, k), kh)) return false;
+                    if (wave_addr_split(wave_b_off(wave), lane, k, kh) != tr_addr(lane, wave_b_tile(wave, k), kh)) return false;
+                    for (int q = 0; q < 4; ++q) {
+                        const int src = (lane & ~15) + 4 * q + ((lane & 15) >> 2);
+                        const int want_t = 8 * (lane >> 5) + 4 * kh + q;
+                        if (dma_content(wave_addr_split(wave_a_off(wave), src, k, kh) + 2 * (lane & 3)) != want_t * 256 + 32 * wave_a_tile(wave, k) + (lane & 31)) return false;
+                        if (dma_content(wave_addr_split(wave_b_off(wave), src, k, kh) + 2 * (lane & 3)) != want_t * 256 + 32 * wave_b_tile(wave, k) + (lane & 31)) return false;
+                    }
+                }
+        for (int i = 0; i < WTILES; ++i)
+            for (int j = 0; j < WTILES; ++j) {
+                if (wave_a_tile(wave, i) < 0 || wave_a_tile(wave, i) >= 8 || wave_b_tile(wave, j) < 0 || wave_b_tile(wave, j) >= 8) return false;
+                ++owners[wave_a_tile(wave, i)][wave_b_tile(wave, j)];
+            }
+        for (int h = 0; h < 2; ++h) {
+            if (wave_sum_j(wave, h) < 0 || wave_sum_j(wave, h) >= WTILES) return false;
+            ++summed[wave_b_tile(wave, wave_sum_j(wave, h))];
+        }
+    }
+    for (int i = 0; i < 8; ++i) {
+        if (summed[i] != 1) return false;
+        for (int j = 0; j < 8; ++j)
+            if (owners[i][j] != 1) return false;
+    }
+    return true;
+}
 static_assert(check_involution(), "wgrad LDS image: source permutation and read permutation differ");
+static_assert(check_wave_tiling(), "wgrad LDS image: the 2 x 2 wave tiling reads a fragment that is not its tile's, or leaves a tile out");
 static_assert(check_fragments(), "wgrad LDS image: a fragment element is not its (channel, time step)");
 static_assert(check_banks(), "wgrad LDS image: bank conflict in a transposed read");
 
