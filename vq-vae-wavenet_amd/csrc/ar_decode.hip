@@ -12,11 +12,8 @@
 // first step) with 16-byte loads, 16 output columns per workgroup.
 #include <string.h>
 
-#include <vector>
-
+#include "ar_host.h"
 #include "ar_persist.h"
-#include "mu_law.h"
-#include "vqw_common.h"
 
 namespace {
 
@@ -235,7 +232,7 @@ __global__ __launch_bounds__(256) void ar_sample_kernel(ArState* st, const float
     for (int b = 0; b < B; ++b) {
         const float* lg = logits + (size_t)b * Q;
         if (st->samp[b].on) {              // block-uniform; wave 0 samples the row (ar_sampling.h), the others wait
-            if (wv == 0) {
+            if (wv == 0) {                 // (sp is this wave's alone: thread 0, the last reader of the row before, is in it)
                 for (int q = lane; q < Q; q += 64) sp[q] = lg[q];
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // lanes read each other's LDS writes (same wave)
                 const int idx = ar_sample_truncated(sp, Q, st->samp[b], st->uniforms[(size_t)b * st->n_steps + i_out],
@@ -250,75 +247,23 @@ __global__ __launch_bounds__(256) void ar_sample_kernel(ArState* st, const float
             __syncthreads();
             continue;
         }
-        float m = -INFINITY;
-        int mi = 0x7fffffff;
-        for (int q = tid; q < Q; q += 256) {
-            const float v = lg[q];
-            if (v > m) { m = v; mi = q; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float om = __shfl_xor(m, o);
-            const int oi = __shfl_xor(mi, o);
-            if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-        }
-        __syncthreads();
-        if (lane == 0) { redv[wv] = m; redi[wv] = mi; }
-        __syncthreads();
-        m = redv[0]; mi = redi[0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w)
-            if (redv[w] > m || (redv[w] == m && redi[w] < mi)) { m = redv[w]; mi = redi[w]; }
-        float s = 0.0f;
-        for (int q = tid; q < Q; q += 256) {
-            const float e = __expf(lg[q] - m);
-            sp[q] = e;
-            s += e;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        __syncthreads();
-        if (lane == 0) redv[wv] = s;
-        __syncthreads();
-        s = (redv[0] + redv[1]) + (redv[2] + redv[3]);
-        const float inv = 1.0f / s;
-        for (int q = tid; q < Q; q += 256) {
-            const float p = sp[q] * inv;
-            sp[q] = p;
-            probs[(size_t)b * Q + q] = p;
-            if (st->probs_last) st->probs_last[(size_t)b * Q + q] = p;
-        }
-        __syncthreads();
+        // a default row (ar_sample_default); p goes to probs every step, and to probs_last whenever that is set
+        const int mode = st->mode;
+        const int idx = ar_sample_default(lg, 1, sp, redv, redi, Q, mode, mode ? st->uniforms + (size_t)b * st->n_steps + i_out : nullptr,
+                                          probs + (size_t)b * Q, st->probs_last ? st->probs_last + (size_t)b * Q : nullptr);
         if (tid == 0) {
-            int idx;
-            if (st->mode == 0) {
-                idx = mi;  // greedy: np.argmax (first maximum)
-            } else {
-                // utils.py:20-25: cdf = cumsum(pdf) (sequential fp32), searchsorted(cdf, u, 'left')
-                const float u = st->uniforms[(size_t)b * st->n_steps + i_out];
-                float c = 0.0f;
-                idx = 0;
-                for (int q = 0; q < Q; ++q) {
-                    c += sp[q];
-                    if (c < u) idx = q + 1;
-                }
-            }
             const float dec = vqw_mu_decode_m((float)idx, mu);
             if (st->audio) st->audio[(size_t)b * st->n_steps + i_out] = dec;
             if (st->indices) st->indices[(size_t)b * st->n_steps + i_out] = idx;
             prev[b] = dec;
         }
-        __syncthreads();
     }
     if (tid == 0) st->step = step + 1;
 }
 
 }  // namespace
 
-struct vqw_ar_decoder {
-    vqw_ar_weights w;
-    std::vector<int> dil;
-    std::vector<const float*> gated_w, gated_b, cond_w, out_w, out_b;
+struct vqw_ar_decoder : ArTables {
     int B = 0;
     // device state
     ArState* st = nullptr;
@@ -329,8 +274,7 @@ struct vqw_ar_decoder {
     int cond_Tz_cap = 0;
     hipStream_t stream = nullptr;  // private stream (graph capture is illegal on the null stream)
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t gexec = nullptr;
+    ArGraph step;                  // launch_step, captured
     bool use_graph = true;
     ArPersist* persist = nullptr;  // persistent single-launch generator (default model shapes)
     bool pending = false;          // a run has been enqueued and not yet waited for
@@ -340,12 +284,6 @@ struct vqw_ar_decoder {
 };
 
 namespace {
-
-#define HIPC(x)                                                                       \
-    do {                                                                              \
-        hipError_t e_ = (x);                                                          \
-        if (e_ != hipSuccess) return vqw_set_error("%s failed: %s", #x, hipGetErrorString(e_)); \
-    } while (0)
 
 int launch_step(vqw_ar_decoder* h, hipStream_t st) {
     const vqw_ar_weights& w = h->w;
@@ -397,8 +335,7 @@ int launch_step(vqw_ar_decoder* h, hipStream_t st) {
 void free_all(vqw_ar_decoder* h) {
     if (!h) return;
     if (h->persist) arp_destroy(h->persist);
-    if (h->gexec) (void)hipGraphExecDestroy(h->gexec);
-    if (h->graph) (void)hipGraphDestroy(h->graph);
+    h->step.drop();
     for (float* p : h->rings) (void)hipFree(p);
     for (float* p : h->condenc) (void)hipFree(p);
     float* bufs[] = {reinterpret_cast<float*>(h->st), h->prev, h->xring, h->cur, h->gated, h->skip, h->h, h->logits, h->probs};
@@ -427,17 +364,9 @@ static int ar_create(vqw_ar_decoder** out, const vqw_ar_weights* w, int batch, i
     VQW_CHECK(w->Q <= 1024 && w->pre_k <= 64, "vqw_ar_decode_create: Q must be <= 1024 and pre_k <= 64");
     VQW_CHECK(w->pre_k >= 1 && w->dilations && w->gated_w && w->gated_b && w->cond_w && w->out_w && w->out_b, "vqw_ar_decode_create: null weight table");
     vqw_ar_decoder* h = new vqw_ar_decoder();
-    h->w = *w;
+    h->assign(w);
     h->B = batch;
     const int L = w->n_layers;
-    h->dil.assign(w->dilations, w->dilations + L);
-    h->gated_w.assign(w->gated_w, w->gated_w + L);
-    h->gated_b.assign(w->gated_b, w->gated_b + L);
-    h->cond_w.assign(w->cond_w, w->cond_w + L);
-    h->out_w.assign(w->out_w, w->out_w + L);
-    h->out_b.assign(w->out_b, w->out_b + L);
-    h->w.dilations = nullptr; h->w.gated_w = nullptr; h->w.gated_b = nullptr; h->w.cond_w = nullptr;
-    h->w.out_w = nullptr; h->w.out_b = nullptr;
     const char* env = getenv("VQW_AR_GRAPH");
     h->use_graph = !(env && env[0] == '0');
 #define AR_ALLOC(ptr, n)                                                               \
@@ -456,7 +385,7 @@ static int ar_create(vqw_ar_decoder** out, const vqw_ar_weights* w, int batch, i
     AR_ALLOC(h->logits, B * w->Q);
     AR_ALLOC(h->probs, B * w->Q);
     h->rings.assign(L, nullptr);
-    for (int l = 0; l < L; ++l) AR_ALLOC(h->rings[l], (size_t)(w->kernel_size - 1) * h->dil[l] * B * w->R);
+    for (int l = 0; l < L; ++l) AR_ALLOC(h->rings[l], h->ring_floats(l, batch));
     h->condenc.assign(L + 1, nullptr);
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming) != hipSuccess ||
@@ -490,17 +419,12 @@ extern "C" int vqw_ar_prior_create(vqw_ar_decoder** out, const vqw_ar_weights* w
 // The mu-law level of an audio handle: 256 after every create call, whatever w->Q is.  Every check comes before any device call.
 extern "C" int vqw_ar_decode_set_levels(vqw_ar_decoder* h, int levels) {
     VqwMu m;
-    VQW_CHECK(vqw_mu_level(levels, &m), "vqw_ar_decode_set_levels: levels=%d must be 256, 512 or 1024", levels);
-    VQW_CHECK(h, "vqw_ar_decode_set_levels: null handle");
-    VQW_CHECK(h->n_codes == 0, "vqw_ar_decode_set_levels: a code-input handle (n_codes=%d) has no mu-law", h->n_codes);
-    VQW_CHECK(levels == h->w.Q, "vqw_ar_decode_set_levels: levels=%d is not the handle's Q=%d", levels, (int)h->w.Q);
-    VQW_CHECK(!h->pending, "vqw_ar_decode_set_levels: levels=%d refused while a run is pending (vqw_ar_decode_wait first)", levels);
+    const int rc = ar_levels_check("vqw_ar_decode", h, levels, &m);
+    if (rc) return rc;
     if (m.levels == h->mu.levels) return 0;
     h->mu = m;
     if (h->persist) arp_set_levels(h->persist, m);
-    // the captured step carries the level as a kernel argument: capture again on the next run
-    if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    h->step.drop();   // the captured step carries the level as a kernel argument
     return 0;
 }
 
@@ -520,7 +444,7 @@ extern "C" int vqw_ar_decode_reset(vqw_ar_decoder* h, vqw_stream_t s) {
     HIPC(hipMemsetAsync(h->prev, 0, B * sizeof(float), st));       // audio = zeros (generate.py:103)
     HIPC(hipMemsetAsync(h->xring, 0, B * h->w.pre_k * sizeof(float), st));
     for (int l = 0; l < h->w.n_layers; ++l)
-        HIPC(hipMemsetAsync(h->rings[l], 0, (size_t)(h->w.kernel_size - 1) * h->dil[l] * B * h->w.R * sizeof(float), st));
+        HIPC(hipMemsetAsync(h->rings[l], 0, h->ring_floats(l, h->B) * sizeof(float), st));
     return 0;
 }
 
@@ -646,8 +570,7 @@ int project_condition(vqw_ar_decoder* h, const float* encoding, int Tz, hipStrea
             HIPC(hipMalloc((void**)&h->condenc[l], n * sizeof(float)));
         }
         h->cond_Tz_cap = Tz;
-        if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-        if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+        h->step.drop();   // the captured step carries the condition buffers as kernel arguments
     }
     for (int l = 0; l <= L; ++l) {
         vqw_conv_desc d;
@@ -711,19 +634,13 @@ static int run_single(vqw_ar_decoder* h, const float* encoding, int Tz, int rati
     HIPC(hipMemcpyAsync(&h->st->run_base, &h->st->step, sizeof(int), hipMemcpyDeviceToDevice, st));
     HIPC(hipStreamSynchronize(st));  // `hs` is a stack object; also orders the capture below
 
-    if (h->use_graph && !h->gexec) {
-        HIPC(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        const int rc = launch_step(h, st);
-        hipGraph_t g = nullptr;
-        hipError_t e = hipStreamEndCapture(st, &g);
+    if (h->use_graph && !h->step.exec) {
+        const int rc = h->step.capture(st, [&] { return launch_step(h, st); }, "vqw_ar_decode_run");
         if (rc) return rc;
-        if (e != hipSuccess) return vqw_set_error("vqw_ar_decode_run: graph capture failed: %s", hipGetErrorString(e));
-        h->graph = g;
-        HIPC(hipGraphInstantiate(&h->gexec, h->graph, nullptr, nullptr, 0));
     }
     for (int i = 0; i < n_steps; ++i) {
-        if (h->gexec) {
-            HIPC(hipGraphLaunch(h->gexec, st));
+        if (h->step.exec) {
+            HIPC(hipGraphLaunch(h->step.exec, st));
         } else {
             const int rc = launch_step(h, st);
             if (rc) return rc;

@@ -1,6 +1,10 @@
-// Temperature, top-k and nucleus (top-p) sampling of one batch row by ONE wave, shared by the persistent generator
-// (ar_persist.hip decode_rows) and the launch-per-phase path (ar_decode.hip ar_sample_kernel).  Rows at their defaults
-// (temperature 1, top_k off, top_p 1) never come here: they keep the plain softmax + serial cdf of utils.py:13-46 bit for bit.
+// The generators' sampling of one batch row.
+//
+// ar_sample_truncated: temperature, top-k and nucleus (top-p) sampling by ONE wave, shared by the persistent generator
+// (ar_persist.hip decode_rows), the launch-per-phase path (ar_decode.hip ar_sample_kernel), the wide generator (ar_wide.hip
+// arw_sample_kernel) and the all-positions pass (sample.hip).  Rows at their defaults (temperature 1, top_k off, top_p 1)
+// never come there: they keep the plain softmax + serial cdf of utils.py:13-46 bit for bit, which for a 256-thread block is
+// ar_sample_default (ar_sample_kernel, arw_sample_kernel; the persistent kernel has its own in decode_rows).
 //
 // Semantics (include/vqwave.h, vqw_ar_sampling):  p = softmax(z / T) (max subtracted first);  top-k keeps the first K classes
 // in the order (p descending, index ascending);  top-p keeps, in the same order, the shortest prefix of the kept set whose
@@ -178,6 +182,67 @@ __device__ __forceinline__ int ar_sample_truncated(float* row, int Q, const ArSa
     const unsigned long long kl = __ballot(keep != 0);   // u above the last cdf value: the largest kept index
     const int l1 = 63 - __clzll((long long)kl);
     return l1 * nj + __shfl(last_kept, l1);
+}
+
+// A row at its defaults, by a block of 256 threads (all of them call): softmax with the maximum subtracted (wavenet.py:171),
+// then utils.decode (utils.py:30-46): mode 0 the lowest index among the maxima (np.argmax), mode 1 a sequential fp32 cumsum
+// and searchsorted left, which gives Q when *u lies above the last cdf value.  The index is returned in thread 0 only.
+// logits: the row's Q <= 1024 logits in global memory, `stride` floats apart; sp [Q], redv [4], redi [4]: LDS scratch of the
+// block, sp is left holding p; u: the row's uniform of this step, read by thread 0 in mode 1 only; p0, p1 (either may be
+// null): global copies of p.  May be called row after row on the same scratch: the barrier at the top ends the last call's
+// reads of it (thread 0's of sp among them); until the last barrier a thread touches only the sp[q] it wrote itself.
+__device__ __forceinline__ int ar_sample_default(const float* logits, size_t stride, float* sp, float* redv, int* redi, int Q,
+                                                 int mode, const float* u, float* p0, float* p1) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __syncthreads();
+    float m = -INFINITY;
+    int mi = 0x7fffffff;
+    for (int q = tid; q < Q; q += 256) {
+        const float v = logits[q * stride];
+        sp[q] = v;
+        if (v > m) { m = v; mi = q; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(m, o);
+        const int oi = __shfl_xor(mi, o);
+        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+    }
+    if (lane == 0) { redv[wv] = m; redi[wv] = mi; }
+    __syncthreads();
+    m = redv[0]; mi = redi[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+        if (redv[w] > m || (redv[w] == m && redi[w] < mi)) { m = redv[w]; mi = redi[w]; }
+    float s = 0.0f;
+    for (int q = tid; q < Q; q += 256) {
+        const float e = __expf(sp[q] - m);
+        sp[q] = e;
+        s += e;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    __syncthreads();                           // every wave has read the maxima
+    if (lane == 0) redv[wv] = s;
+    __syncthreads();
+    s = (redv[0] + redv[1]) + (redv[2] + redv[3]);
+    const float inv = 1.0f / s;
+    for (int q = tid; q < Q; q += 256) {
+        const float p = sp[q] * inv;
+        sp[q] = p;
+        if (p0) p0[q] = p;
+        if (p1) p1[q] = p;
+    }
+    __syncthreads();
+    if (tid != 0 || mode == 0) return mi;
+    const float uu = *u;
+    float cs = 0.0f;
+    int idx = 0;
+    for (int q = 0; q < Q; ++q) {
+        cs += sp[q];
+        if (cs < uu) idx = q + 1;
+    }
+    return idx;
 }
 
 // host: validate the per-row settings of one handle (NULL = all defaults) and turn them into ArSampleRow; `any` is set when

@@ -27,12 +27,9 @@
 // feeds the drawn index itself back as the next input.
 #include <string.h>
 
-#include <vector>
-
+#include "ar_host.h"
 #include "ar_sampling.h"
 #include "ar_wide_plan.h"
-#include "mu_law.h"
-#include "vqw_common.h"
 
 namespace {
 
@@ -294,8 +291,9 @@ __global__ void arw_window_kernel(WideState* st, const float* __restrict__ enc, 
 }
 
 // softmax (wavenet.py:171) + utils.decode (utils.py:30-46) + mu_law_decode_np of ONE row per workgroup; logits [Q][B].
-// A default row: softmax with the maximum subtracted, a sequential fp32 cumsum, searchsorted left; greedy = the lowest index
-// among the maxima.  A row with settings: ar_sample_truncated, by wave 0.
+// A default row: ar_sample_default (softmax with the maximum subtracted, a sequential fp32 cumsum, searchsorted left; greedy =
+// the lowest index among the maxima); p is written on the last step of a run only.  A row with settings:
+// ar_sample_truncated, by wave 0.
 // CODE (the latent prior's handles): the same decision over Q = n_codes classes; the index itself is the next input
 // (prev = idx + 1, arw_pre_code_kernel), there is no mu-law decode, and audio (NULL on these handles) is skipped.  u above
 // the last cdf value gives Q, which is no code: it is clamped to Q - 1.
@@ -305,71 +303,26 @@ __global__ __launch_bounds__(256) void arw_sample_kernel(WideState* st, const fl
     __shared__ float sp[1024];
     __shared__ float redv[4];
     __shared__ int redi[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const int b = blockIdx.x;
     const int step = st->step;
     const int n_steps = st->n_steps;
     const int i_out = step - st->run_base;
     const bool last = i_out == n_steps - 1;
     float* const pl = (last && st->probs_last) ? st->probs_last + (size_t)b * Q : nullptr;
-    for (int q = tid; q < Q; q += 256) sp[q] = logits[(size_t)q * B + b];
-    __syncthreads();
     int idx = 0;
     const ArSampleRow row = samp[b];
     if (row.on) {                          // block-uniform; wave 0 samples the row (ar_sampling.h)
-        if (wv != 0) return;
+        for (int q = tid; q < Q; q += 256) sp[q] = logits[(size_t)q * B + b];
+        __syncthreads();
+        if (tid >= 64) return;
         idx = ar_sample_truncated(sp, Q, row, st->uniforms[(size_t)b * n_steps + i_out], pl);
     } else {
-        float m = -INFINITY;
-        int mi = 0x7fffffff;
-        for (int q = tid; q < Q; q += 256) {
-            const float v = sp[q];
-            if (v > m) { m = v; mi = q; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float om = __shfl_xor(m, o);
-            const int oi = __shfl_xor(mi, o);
-            if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-        }
-        if (lane == 0) { redv[wv] = m; redi[wv] = mi; }
-        __syncthreads();
-        m = redv[0]; mi = redi[0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w)
-            if (redv[w] > m || (redv[w] == m && redi[w] < mi)) { m = redv[w]; mi = redi[w]; }
-        float s = 0.0f;
-        for (int q = tid; q < Q; q += 256) {
-            const float e = __expf(sp[q] - m);
-            sp[q] = e;
-            s += e;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        __syncthreads();
-        if (lane == 0) redv[wv] = s;
-        __syncthreads();
-        s = (redv[0] + redv[1]) + (redv[2] + redv[3]);
-        const float inv = 1.0f / s;
-        for (int q = tid; q < Q; q += 256) {
-            const float p = sp[q] * inv;
-            sp[q] = p;
-            if (pl) pl[q] = p;
-        }
-        __syncthreads();
+        const int mode = st->mode;
+        idx = ar_sample_default(logits + b, B, sp, redv, redi, Q, mode, mode ? st->uniforms + (size_t)b * n_steps + i_out : nullptr,
+                                pl, nullptr);
         if (tid != 0) return;
-        if (st->mode == 0) {
-            idx = mi;                      // greedy: np.argmax (first maximum)
-        } else {
-            // utils.py:20-25: cdf = cumsum(pdf) (sequential fp32), searchsorted(cdf, u, 'left')
-            const float u = st->uniforms[(size_t)b * n_steps + i_out];
-            float cs = 0.0f;
-            for (int q = 0; q < Q; ++q) {
-                cs += sp[q];
-                if (cs < u) idx = q + 1;
-            }
-            idx = min(idx, Q - 1);
-        }
+        if (mode != 0) idx = min(idx, Q - 1);
     }
     if (tid == 0) {
         if constexpr (CODE) {
@@ -393,10 +346,7 @@ __global__ __launch_bounds__(256) void arw_sample_kernel(WideState* st, const fl
 
 }  // namespace
 
-struct vqw_ar_wide {
-    vqw_ar_weights w;
-    std::vector<int> dil;
-    std::vector<const float*> gated_w, gated_b, cond_w, out_w, out_b;
+struct vqw_ar_wide : ArTables {
     int B = 0, Mall = 0;
     int n_codes = 0;                 // > 0: code-input mode (vqw_ar_wide_prior_create): w.pre_w is [pre_k][n_codes][R], read in place
     long long steps = 0;             // host mirror of the device step counter (reset: 0; a run adds n_steps)
@@ -408,19 +358,12 @@ struct vqw_ar_wide {
     std::vector<float*> rings;       // per layer [depth][R][B]
     hipStream_t stream = nullptr;    // private stream (graph capture is illegal on the null stream)
     hipEvent_t ev_in = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t gexec = nullptr;
+    ArGraph step;                    // launch_step, captured
     bool pending = false;
     VqwMu mu = {256, 255.0f, 5.5451774444795623f};   // the mu-law level of an audio handle (vqw_ar_wide_set_levels)
 };
 
 namespace {
-
-#define HIPC(x)                                                                       \
-    do {                                                                              \
-        hipError_t e_ = (x);                                                          \
-        if (e_ != hipSuccess) return vqw_set_error("%s failed: %s", #x, hipGetErrorString(e_)); \
-    } while (0)
 
 WideArgs base_args(const vqw_ar_wide* h) {
     WideArgs a;
@@ -511,8 +454,7 @@ int refresh_window(vqw_ar_wide* h, const float* encoding, int Tz, const ArWideWi
 
 void free_all(vqw_ar_wide* h) {
     if (!h) return;
-    if (h->gexec) (void)hipGraphExecDestroy(h->gexec);
-    if (h->graph) (void)hipGraphDestroy(h->graph);
+    h->step.drop();
     for (float* p : h->rings) (void)hipFree(p);
     void* bufs[] = {h->st, h->samp, h->prev, h->xhist, h->cur, h->gated, h->skip, h->h, h->logits, h->enct, h->condwin};
     for (void* p : bufs) (void)hipFree(p);
@@ -543,19 +485,11 @@ int wide_create(const char* fn, vqw_ar_wide** out, const vqw_ar_weights* w, int 
         ARW_CHECK(w->dilations[l] >= 1, "dilation %d of layer %d must be >= 1", (int)w->dilations[l], l);
 #undef ARW_CHECK
     vqw_ar_wide* h = new vqw_ar_wide();
-    h->w = *w;
+    h->assign(w);
     h->B = batch;
     h->n_codes = n_codes > 0 ? n_codes : 0;
     const int L = w->n_layers;
     h->Mall = L * 2 * w->R + w->S;
-    h->dil.assign(w->dilations, w->dilations + L);
-    h->gated_w.assign(w->gated_w, w->gated_w + L);
-    h->gated_b.assign(w->gated_b, w->gated_b + L);
-    h->cond_w.assign(w->cond_w, w->cond_w + L);
-    h->out_w.assign(w->out_w, w->out_w + L);
-    h->out_b.assign(w->out_b, w->out_b + L);
-    h->w.dilations = nullptr; h->w.gated_w = nullptr; h->w.gated_b = nullptr; h->w.cond_w = nullptr;
-    h->w.out_w = nullptr; h->w.out_b = nullptr;
     h->samp_host.assign(batch, ArSampleRow{1.0f, 0, 1.0f, 0});
 #define ARW_ALLOC(ptr, bytes)                                                          \
     do {                                                                               \
@@ -575,7 +509,7 @@ int wide_create(const char* fn, vqw_ar_wide** out, const vqw_ar_weights* w, int 
     ARW_ALLOC(h->enct, (size_t)AR_WIDE_WINDOW * w->Cc * B * f4);
     ARW_ALLOC(h->condwin, (size_t)AR_WIDE_WINDOW * h->Mall * B * f4);
     h->rings.assign(L, nullptr);
-    for (int l = 0; l < L; ++l) ARW_ALLOC(h->rings[l], (size_t)(w->kernel_size - 1) * h->dil[l] * B * w->R * f4);
+    for (int l = 0; l < L; ++l) ARW_ALLOC(h->rings[l], h->ring_floats(l, batch) * f4);
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming) != hipSuccess) {
         free_all(h);
@@ -601,16 +535,11 @@ extern "C" int vqw_ar_wide_prior_create(vqw_ar_wide** out, const vqw_ar_weights*
 // The mu-law level of an audio handle: 256 after vqw_ar_wide_create, whatever w->Q is.  Every check comes before any device call.
 extern "C" int vqw_ar_wide_set_levels(vqw_ar_wide* h, int levels) {
     VqwMu m;
-    VQW_CHECK(vqw_mu_level(levels, &m), "vqw_ar_wide_set_levels: levels=%d must be 256, 512 or 1024", levels);
-    VQW_CHECK(h, "vqw_ar_wide_set_levels: null handle");
-    VQW_CHECK(h->n_codes == 0, "vqw_ar_wide_set_levels: a code-input handle (n_codes=%d) has no mu-law", h->n_codes);
-    VQW_CHECK(levels == h->w.Q, "vqw_ar_wide_set_levels: levels=%d is not the handle's Q=%d", levels, (int)h->w.Q);
-    VQW_CHECK(!h->pending, "vqw_ar_wide_set_levels: levels=%d refused while a run is pending (vqw_ar_wide_wait first)", levels);
+    const int rc = ar_levels_check("vqw_ar_wide", h, levels, &m);
+    if (rc) return rc;
     if (m.levels == h->mu.levels) return 0;
     h->mu = m;
-    // the captured step carries the level as a kernel argument: capture again on the next run
-    if (h->gexec) { (void)hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    h->step.drop();   // the captured step carries the level as a kernel argument
     return 0;
 }
 
@@ -626,7 +555,7 @@ extern "C" int vqw_ar_wide_reset(vqw_ar_wide* h, vqw_stream_t s) {
     HIPC(hipMemsetAsync(h->prev, 0, B * sizeof(float), st));       // audio = zeros (generate.py:103)
     HIPC(hipMemsetAsync(h->xhist, 0, B * h->w.pre_k * sizeof(float), st));
     for (int l = 0; l < h->w.n_layers; ++l)
-        HIPC(hipMemsetAsync(h->rings[l], 0, (size_t)(h->w.kernel_size - 1) * h->dil[l] * B * h->w.R * sizeof(float), st));
+        HIPC(hipMemsetAsync(h->rings[l], 0, h->ring_floats(l, h->B) * sizeof(float), st));
     h->steps = 0;
     return 0;
 }
@@ -675,15 +604,9 @@ extern "C" int vqw_ar_wide_run_async(vqw_ar_wide* h, const float* encoding, int 
     HIPC(hipMemcpyAsync(&h->st->run_base, &h->st->step, sizeof(int), hipMemcpyDeviceToDevice, st));
     HIPC(hipStreamSynchronize(st));  // `hs` is a stack object; also orders the capture below
 
-    if (!h->gexec) {
-        HIPC(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        const int rc = launch_step(h, st);
-        hipGraph_t g = nullptr;
-        hipError_t e = hipStreamEndCapture(st, &g);
+    if (!h->step.exec) {
+        const int rc = h->step.capture(st, [&] { return launch_step(h, st); }, "vqw_ar_wide_run");
         if (rc) return rc;
-        if (e != hipSuccess) return vqw_set_error("vqw_ar_wide_run: graph capture failed: %s", hipGetErrorString(e));
-        h->graph = g;
-        HIPC(hipGraphInstantiate(&h->gexec, h->graph, nullptr, nullptr, 0));
     }
     // every run projects its own windows: the encoding may be another one than the last run's
     ArWideWindow win;
@@ -696,7 +619,7 @@ extern "C" int vqw_ar_wide_run_async(vqw_ar_wide* h, const float* encoding, int 
             if (rc) return rc;
         }
         const long long n = arw_steps_in_window(win, t, left, ratio, Tz);
-        for (long long i = 0; i < n; ++i) HIPC(hipGraphLaunch(h->gexec, st));
+        for (long long i = 0; i < n; ++i) HIPC(hipGraphLaunch(h->step.exec, st));
         t += n;
         left -= n;
         h->steps = t;

@@ -1,7 +1,14 @@
 """Fast autoregressive generation: host-side mirror of Wavenet.build_generator
 (wavenet.py:103-172) + the sampling loop of generate.py:103-113, running entirely on the GPU
-through vqw_ar_decode_* (ring buffers instead of FIFO queues, on-device sampling)."""
+through vqw_ar_decode_* / vqw_ar_wide_* (ring buffers instead of FIFO queues, on-device sampling).
+
+FastGenerator (audio) and PriorGenerator (VQ codes) cut 1..8 rows into handles of the persistent kernel (or of the
+launch-per-phase path) and share FastGenerator._run; WideGenerator and WidePriorGenerator run up to 1024 rows on one
+vqw_ar_wide handle and share _WideBase._run.  What all four do alike (weight table, argument checks, uniforms, per-row sampling
+settings) is in the helpers in front of the classes.  Every public method refuses in the order mode, sampling settings,
+tensor arguments, before anything touches the model or the device."""
 import ctypes as C
+import functools
 
 import torch
 
@@ -9,7 +16,7 @@ from . import _lib as L
 
 
 MAX_ROWS = 4    # batch rows of one persistent handle (its LDS budget); larger batches run as several handles
-MAX_GROUP = 8   # handles of one launch (vqw_ar_decode_run_group_async)
+MAX_GROUP = 8   # handles of one launch (vqw_ar_decode_run_group_sampled_async)
 CU_MARGIN = 8   # CUs left free when handles share a launch: a workgroup of a persistent grid that finds no free CU
 #                 keeps its siblings spinning until their timeout (not applied to the whole-chip layout below, which is
 #                 chosen only when it fits exactly and is what BASELINE.json configs[3] on one GPU asks for)
@@ -20,7 +27,7 @@ def sampling_settings(batch, mode, temperature=1.0, top_k=0, top_p=1.0):
     (temperature, top_k, top_p) per row.  Each keyword is a scalar (every row) or a sequence of `batch` values.
     temperature: finite, > 0 (1 = off); top_k: integer >= 0 (0 = off, >= the class count = off); top_p: in (0, 1] (1 = off).
     They apply to mode 'sample' only: a non-default setting with mode 'greedy' is refused.  Returns None when every row is
-    at its defaults (the plain entry points then run, bit for bit today's sampling), else a list of `batch` tuples."""
+    at its defaults (the library is then handed no settings: the plain sampling, bit for bit), else a list of `batch` tuples."""
     import math
 
     def rows(name, v):
@@ -123,7 +130,99 @@ def _weights_of(model, keep):
     return w
 
 
-class WideGenerator:
+def _sampling_rows(settings):
+    """vqw_ar_sampling[len(settings)] of sampling_settings' tuples; None (NULL: every row at its defaults) for None."""
+    if settings is None:
+        return None
+    rows = (L.ArSampling * len(settings))()
+    for j, (t, k, p) in enumerate(settings):
+        rows[j].temperature, rows[j].top_k, rows[j].top_p = t, min(k, 0x7fffffff), p
+    return rows
+
+
+def _check_mode(mode):
+    if mode not in ('greedy', 'sample'):
+        raise NotImplementedError('decode mode %s not implemented' % mode)   # utils.py:46
+
+
+def _check_encoding(encoding, B, Cc):
+    if (not isinstance(encoding, torch.Tensor) or encoding.dtype != torch.float32 or encoding.dim() != 3
+            or encoding.shape[0] != B or encoding.shape[1] != Cc):
+        raise ValueError('encoding must be a float32 [%d][%d][Tz] tensor' % (B, Cc))
+
+
+def _check_speakers(spk, B):
+    if spk.numel() != B:
+        raise ValueError('%d speaker ids for a batch of %d' % (spk.numel(), B))
+
+
+def _uniforms_of(uniforms, mode, B, n, dev, n_name):
+    """The float32 [B][n] uniforms of mode 'sample', drawn here when None (np.random.rand in utils.py:22); None for 'greedy'."""
+    if mode != 'sample':
+        return None
+    if uniforms is None:
+        uniforms = torch.rand(B, n, device=dev)
+    if uniforms.shape != (B, n) or uniforms.dtype != torch.float32:
+        raise ValueError('uniforms must be float32 [B][%s]' % n_name)
+    return uniforms
+
+
+@functools.lru_cache(maxsize=None)
+def _row_slices(parts):
+    """parts: the rows of each handle (a tuple) -> the slice of the batch each handle owns."""
+    starts = [sum(parts[:i]) for i in range(len(parts))]
+    return tuple(slice(b0, b0 + nb) for b0, nb in zip(starts, parts))
+
+
+PRIOR_RATIO = 64    # code steps per condition frame (prior.CODES_PER_FRAME)
+
+
+class _Closes:
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _WideBase(_Closes):
+    """One vqw_ar_wide handle (csrc/ar_wide.hip) over the model's LIVE variables, and one run of it.  A subclass says how its
+    handle is created (_create) and what its public method hands to _run."""
+    _n_name = 'n_steps'          # the step count's name in the subclass's public method (for the messages)
+
+    def __init__(self, model, batch):
+        self.model, self.B = model, batch
+        self._keep = []
+        self._w = _weights_of(model, self._keep)
+        self._h = None
+        h = C.c_void_p()
+        self._create(h, self._w)
+        self._h = h
+
+    def reset(self):
+        """sess.run(wavenet.init_ops) (generate.py:105): empty queues, the next sample is step 0."""
+        L.check(L.lib().vqw_ar_wide_reset(self._h, L.stream()))
+
+    def _run(self, cond, Tz, ratio, n, mode, uniforms, settings, audio, return_probs):
+        """n steps of every row on condition cond [B][Cc][Tz]; audio [B][n] or None (code mode).  Returns (indices, probs of
+        the last step or None)."""
+        L.require_cuda(cond, uniforms)
+        uniforms = _uniforms_of(uniforms, mode, self.B, n, cond.device, self._n_name)
+        idx = torch.empty(self.B, n, dtype=torch.int32, device=cond.device)
+        probs = torch.empty(self.B, self.model.Q, device=cond.device) if return_probs else None
+        lib = L.lib()
+        L.check(lib.vqw_ar_wide_run_async(self._h, L.ptr(cond), Tz, ratio, n, 0 if mode == 'greedy' else 1, L.ptr(uniforms),
+                                          _sampling_rows(settings), L.ptr(audio), L.ptr(idx), L.ptr(probs), L.stream()))
+        L.check(lib.vqw_ar_wide_wait(self._h))
+        return idx, probs
+
+    def close(self):
+        if getattr(self, '_h', None) is not None:
+            L.lib().vqw_ar_wide_destroy(self._h)
+            self._h = None
+
+
+class WideGenerator(_WideBase):
     """Generation for many rows at once (1..1024 per handle) on vqw_ar_wide_* (csrc/ar_wide.hip): every layer of a step is
     a GEMM over all rows on the exact-fp32 MFMA.  Built for throughput: converting a list of utterances (generate.py
     -audio_list); FastGenerator stays the right choice for one to eight rows.  Uses the model's LIVE variables, like
@@ -132,20 +231,10 @@ class WideGenerator:
 
     There is no prefill: to continue a prompt, use FastGenerator.prefill + generate."""
 
-    def __init__(self, model, batch):
-        self.model, self.B = model, batch
-        self._keep = []
-        self._w = _weights_of(model, self._keep)
-        self._h = None
-        h = C.c_void_p()
-        L.check(L.lib().vqw_ar_wide_create(C.byref(h), C.byref(self._w), batch))
-        self._h = h
-        if model.levels != 256:          # the model's mu-law level (a created handle compands at 256)
-            L.check(L.lib().vqw_ar_wide_set_levels(h, model.levels))
-
-    def reset(self):
-        """sess.run(wavenet.init_ops) (generate.py:105): empty queues, the next sample is step 0."""
-        L.check(L.lib().vqw_ar_wide_reset(self._h, L.stream()))
+    def _create(self, h, w):
+        L.check(L.lib().vqw_ar_wide_create(C.byref(h), C.byref(w), self.B))
+        if self.model.levels != 256:     # the model's mu-law level (a created handle compands at 256)
+            L.check(L.lib().vqw_ar_wide_set_levels(h, self.model.levels))
 
     def generate(self, encoding, n_steps, mode='greedy', uniforms=None, ratio=None, return_probs=False,
                  temperature=1.0, top_k=0, top_p=1.0):
@@ -153,49 +242,16 @@ class WideGenerator:
         frame (steps so far + i) // ratio (the last frame beyond it).  temperature / top_k / top_p (mode 'sample' only;
         scalars or one value per row): see sampling_settings and vqw_ar_sampling in include/vqwave.h.
         Returns (audio [B][n] float32, indices [B][n] int32[, probs of the last step [B][Q]: the distribution sampled])."""
-        if mode not in ('greedy', 'sample'):
-            raise NotImplementedError('decode mode %s not implemented' % mode)   # utils.py:46
+        _check_mode(mode)
         settings = sampling_settings(self.B, mode, temperature, top_k, top_p)
-        if (not isinstance(encoding, torch.Tensor) or encoding.dtype != torch.float32 or encoding.dim() != 3
-                or encoding.shape[0] != self.B or encoding.shape[1] != self.model.Cc):
-            raise ValueError('encoding must be a float32 [%d][%d][Tz] tensor' % (self.B, self.model.Cc))
-        B, _, Tz = encoding.shape
+        _check_encoding(encoding, self.B, self.model.Cc)
         encoding = encoding.contiguous()
-        L.require_cuda(encoding, uniforms)
-        dev = encoding.device
-        if mode == 'sample':
-            if uniforms is None:
-                uniforms = torch.rand(B, n_steps, device=dev)        # np.random.rand in utils.py:22
-            if uniforms.shape != (B, n_steps) or uniforms.dtype != torch.float32:
-                raise ValueError('uniforms must be float32 [B][n_steps]')
-        audio = torch.empty(B, n_steps, device=dev)
-        idx = torch.empty(B, n_steps, dtype=torch.int32, device=dev)
-        probs = torch.empty(B, self.model.Q, device=dev) if return_probs else None
-        rows = None
-        if settings is not None:
-            rows = (L.ArSampling * B)()
-            for j, (t, k, p) in enumerate(settings):
-                rows[j].temperature, rows[j].top_k, rows[j].top_p = t, min(k, 0x7fffffff), p
-        lib = L.lib()
-        L.check(lib.vqw_ar_wide_run_async(self._h, L.ptr(encoding), Tz, ratio or 64, n_steps, 0 if mode == 'greedy' else 1,
-                                          L.ptr(uniforms) if mode == 'sample' else None, rows, L.ptr(audio), L.ptr(idx),
-                                          L.ptr(probs), L.stream()))
-        L.check(lib.vqw_ar_wide_wait(self._h))
+        audio = torch.empty(self.B, n_steps, device=encoding.device)
+        idx, probs = self._run(encoding, encoding.shape[2], ratio or 64, n_steps, mode, uniforms, settings, audio, return_probs)
         return (audio, idx, probs) if return_probs else (audio, idx)
 
-    def close(self):
-        if getattr(self, '_h', None) is not None:
-            L.lib().vqw_ar_wide_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class WidePriorGenerator:
+class WidePriorGenerator(_WideBase):
     """Samples VQ codes from a prior.LatentPrior for many rows at once (1..1024 per handle) on the wide generator's code-input
     mode (vqw_ar_wide_prior_create, csrc/ar_wide.hip): the input stage gathers rows of W_pre by the previous codes, the drawn
     index is the next input, everything between is WideGenerator's step.  Built for throughput: a corpus sampled from the
@@ -204,20 +260,18 @@ class WidePriorGenerator:
     depend on the batch it ran in, and a run cut into several sample() calls equals the single run bit for bit.
 
     There is no prefill: to continue a prompt of codes, use PriorGenerator.prefill + sample."""
+    _n_name = 'n_frames'
 
     def __init__(self, prior, batch):
-        self.model, self.B = prior, batch
         self._t = 0
-        self._keep = []
-        self._w = _weights_of(prior, self._keep)
-        self._h = None
-        h = C.c_void_p()
-        L.check(L.lib().vqw_ar_wide_prior_create(C.byref(h), C.byref(self._w), batch, prior.Q))
-        self._h = h
+        super().__init__(prior, batch)
+
+    def _create(self, h, w):
+        L.check(L.lib().vqw_ar_wide_prior_create(C.byref(h), C.byref(w), self.B, self.model.Q))
 
     def reset(self):
         """Empty history ("no code yet": a zero one-hot, not code 0); the next sample is step 0."""
-        L.check(L.lib().vqw_ar_wide_reset(self._h, L.stream()))
+        super().reset()
         self._t = 0
 
     def sample(self, n_frames, spk, mode='greedy', uniforms=None, return_probs=False, temperature=1.0, top_k=0, top_p=1.0):
@@ -225,50 +279,17 @@ class WidePriorGenerator:
         'sample' (searchsorted(cumsum(p), u) with uniforms [B][n_frames], drawn here when None; u above the cdf's last
         value gives the last code), tempered / truncated by temperature, top_k, top_p as in WideGenerator.generate.
         Returns codes int32 [B][n_frames][, probabilities of the last step [B][k]: the distribution sampled]."""
-        if mode not in ('greedy', 'sample'):
-            raise NotImplementedError('decode mode %s not implemented' % mode)
+        _check_mode(mode)
         settings = sampling_settings(self.B, mode, temperature, top_k, top_p)
-        if spk.numel() != self.B:
-            raise ValueError('%d speaker ids for a batch of %d' % (spk.numel(), self.B))
-        B = self.B
-        ratio = 64                                     # code steps per condition frame (prior.CODES_PER_FRAME)
-        Tz = -(-(self._t + n_frames) // ratio)
+        _check_speakers(spk, self.B)
+        Tz = -(-(self._t + n_frames) // PRIOR_RATIO)
         cond = self.model.speaker_condition(spk.contiguous(), Tz)
-        L.require_cuda(cond, uniforms)
-        dev = cond.device
-        if mode == 'sample':
-            if uniforms is None:
-                uniforms = torch.rand(B, n_frames, device=dev)
-            if uniforms.shape != (B, n_frames) or uniforms.dtype != torch.float32:
-                raise ValueError('uniforms must be float32 [B][n_frames]')
-        idx = torch.empty(B, n_frames, dtype=torch.int32, device=dev)
-        probs = torch.empty(B, self.model.Q, device=dev) if return_probs else None
-        rows = None
-        if settings is not None:
-            rows = (L.ArSampling * B)()
-            for j, (t, k, p) in enumerate(settings):
-                rows[j].temperature, rows[j].top_k, rows[j].top_p = t, min(k, 0x7fffffff), p
-        lib = L.lib()
-        L.check(lib.vqw_ar_wide_run_async(self._h, L.ptr(cond), Tz, ratio, n_frames, 0 if mode == 'greedy' else 1,
-                                          L.ptr(uniforms) if mode == 'sample' else None, rows, None, L.ptr(idx),
-                                          L.ptr(probs), L.stream()))
-        L.check(lib.vqw_ar_wide_wait(self._h))
+        idx, probs = self._run(cond, Tz, PRIOR_RATIO, n_frames, mode, uniforms, settings, None, return_probs)
         self._t += n_frames
         return (idx, probs) if return_probs else idx
 
-    def close(self):
-        if getattr(self, '_h', None) is not None:
-            L.lib().vqw_ar_wide_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class FastGenerator:
+class FastGenerator(_Closes):
     def __init__(self, model, batch):
         """Uses the model's LIVE variables (call model.use_ema_weights() first to mirror
         generate.py:88-90, which restores the EMA shadows).  Rows of the batch never interact
@@ -279,34 +300,12 @@ class FastGenerator:
         cus = torch.cuda.get_device_properties(model.dev).multi_processor_count
         rows, cpb = pick_layout(batch, model.R, cus)
         self._parts = [rows] * (batch // rows) + ([batch % rows] if batch % rows else [])
-        P = model.P
-        nl, R, S = model.L, model.R, model.S
-        w = L.ArWeights()
-        w.n_layers, w.kernel_size, w.R, w.S, w.Q, w.Cc, w.pre_k = nl, model.ks, R, S, model.Q, model.Cc, model.pre_k
-        self._dil = (C.c_int32 * nl)(*model.dil)
-        w.dilations = self._dil
-        f4 = 4  # bytes per float
-
-        def arr(ptrs):
-            a = (C.c_void_p * nl)(*ptrs)
-            return a
-        self._gw = arr([P['gated_w'][l].data_ptr() for l in range(nl)])
-        self._gb = arr([P['gated_b'][l].data_ptr() for l in range(nl)])
-        self._cw = arr([P['cond_w'].data_ptr() + l * 2 * R * f4 for l in range(nl)])
-        self._ow = arr([P['out_w'][l].data_ptr() for l in range(nl)])
-        self._ob = arr([P['out_b'][l].data_ptr() for l in range(nl)])
-        w.gated_w, w.gated_b, w.cond_w, w.out_w, w.out_b = self._gw, self._gb, self._cw, self._ow, self._ob
-        w.cond_ld, w.out_ld = model.Mall, S + R
-        w.pre_w, w.pre_b = P['pre_w'].data_ptr(), P['pre_b'].data_ptr()
-        w.skip0_w, w.skip0_b = P['skip0_w'].data_ptr(), P['skip0_b'].data_ptr()
-        w.post1_w, w.post1_b = P['post1_w'].data_ptr(), P['post1_b'].data_ptr()
-        w.post1_cond_w, w.post1_cond_ld = P['cond_w'].data_ptr() + nl * 2 * R * f4, model.Mall
-        w.post2_w, w.post2_b = P['post2_w'].data_ptr(), P['post2_b'].data_ptr()
-        self._w = w
+        self._keep = []
+        self._w = _weights_of(model, self._keep)
         self._hs = []
         for nb in self._parts:
             h = C.c_void_p()
-            self._create(h, w, nb, cpb)
+            self._create(h, self._w, nb, cpb)
             self._hs.append(h)
         # waves of handles that are co-resident by construction: floor((CUs - margin) / workgroups), at most MAX_GROUP
         # (no margin where the whole batch fits the chip exactly: the one-utterance-per-XCD layout)
@@ -342,9 +341,7 @@ class FastGenerator:
         ratio = ratio or 64
         if not isinstance(prompt, torch.Tensor) or prompt.dtype != torch.float32 or prompt.dim() != 2 or prompt.shape[0] != self.B:
             raise ValueError('prompt must be a float32 [%d][T] tensor' % self.B)
-        if (not isinstance(encoding, torch.Tensor) or encoding.dtype != torch.float32 or encoding.dim() != 3
-                or encoding.shape[0] != self.B or encoding.shape[1] != self.model.Cc):
-            raise ValueError('encoding must be a float32 [%d][%d][Tz] tensor' % (self.B, self.model.Cc))
+        _check_encoding(encoding, self.B, self.model.Cc)
         T = prompt.shape[1]
         if T > encoding.shape[2] * ratio:
             raise ValueError('a prompt of %d samples is longer than the encoding (%d frames x %d)' % (T, encoding.shape[2], ratio))
@@ -357,8 +354,7 @@ class FastGenerator:
         lib, st = L.lib(), L.stream()
         for h in self._hs:
             L.check(lib.vqw_ar_decode_reset(h, st))
-        starts = [sum(self._parts[:i]) for i in range(len(self._parts))]
-        rows = [slice(b0, b0 + nb) for b0, nb in zip(starts, self._parts)]
+        rows = _row_slices(tuple(self._parts))
         if T == 0:
             return
         x = x.contiguous()
@@ -379,75 +375,45 @@ class FastGenerator:
         """encoding [B][Cc][Tz] (model.encode); continues from the current queue state.  temperature / top_k / top_p
         (mode 'sample' only; scalars or one value per row): see sampling_settings and vqw_ar_sampling in include/vqwave.h.
         Returns (audio [B][n] float32, indices [B][n] int32[, probs of the last step [B][Q]: the distribution sampled])."""
-        if mode not in ('greedy', 'sample'):
-            raise NotImplementedError('decode mode %s not implemented' % mode)   # utils.py:46
+        _check_mode(mode)
         settings = sampling_settings(self.B, mode, temperature, top_k, top_p)
-        B = encoding.shape[0]
-        audio = torch.empty(B, n_steps, device=encoding.device)
+        audio = torch.empty(self.B, n_steps, device=encoding.device)
         idx, probs = self._run(encoding, n_steps, mode, uniforms, ratio or 64, audio, return_probs, settings)
         return (audio, idx, probs) if return_probs else (audio, idx)
 
     def _run(self, encoding, n_steps, mode, uniforms, ratio, audio, return_probs, settings=None):
         """One run of every handle over its rows; audio may be None (code mode).  settings: sampling_settings' per-row list,
-        or None (every row at its defaults: the plain entry points).  Returns (indices, probs of the last step)."""
-        B, Cc, Tz = encoding.shape
-        if B != self.B or Cc != self.model.Cc:
-            raise ValueError('encoding must be [%d][%d][Tz]' % (self.B, self.model.Cc))
+        or None (every row at its defaults).  Returns (indices, probs of the last step)."""
+        _check_encoding(encoding, self.B, self.model.Cc)
         L.require_cuda(encoding, uniforms)
+        B, _, Tz = encoding.shape
         dev = encoding.device
         idx = torch.empty(B, n_steps, dtype=torch.int32, device=dev)
         probs = torch.empty(B, self.model.Q, device=dev) if return_probs else None
-        if mode == 'sample':
-            if uniforms is None:
-                uniforms = torch.rand(B, n_steps, device=dev)        # np.random.rand in utils.py:22
-            if uniforms.shape != (B, n_steps) or uniforms.dtype != torch.float32:
-                raise ValueError('uniforms must be float32 [B][n_steps]')
-        encoding = encoding.contiguous()
-        starts = [sum(self._parts[:i]) for i in range(len(self._parts))]
-        rows = [slice(b0, b0 + nb) for b0, nb in zip(starts, self._parts)]
-        vp = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])  # noqa: E731
-        if settings is not None:
-            return self._run_sampled(encoding, Tz, n_steps, uniforms, ratio, audio, idx, probs, settings, rows, vp)
-        for wave in self._waves:                 # one launch per wave; the waves follow each other
-            hs = (C.c_void_p * len(wave))(*[self._hs[i].value for i in wave])
-            L.check(L.lib().vqw_ar_decode_run_group_async(
-                hs, len(wave), vp([encoding[rows[i]] for i in wave]), Tz, ratio, n_steps, 0 if mode == 'greedy' else 1,
-                vp([uniforms[rows[i]] for i in wave]) if uniforms is not None else None,
-                vp([audio[rows[i]] for i in wave]) if audio is not None else None, vp([idx[rows[i]] for i in wave]),
-                vp([probs[rows[i]] for i in wave]) if probs is not None else None, L.stream())
-                if L.lib().vqw_ar_decode_workgroups(self._hs[wave[0]]) > 0 else
-                L.lib().vqw_ar_decode_run_async(
-                    self._hs[wave[0]], L.ptr(encoding[rows[wave[0]]]), Tz, ratio, n_steps, 0 if mode == 'greedy' else 1,
-                    L.ptr(uniforms[rows[wave[0]]]) if uniforms is not None else None, L.ptr(audio[rows[wave[0]]]),
-                    L.ptr(idx[rows[wave[0]]]), L.ptr(probs[rows[wave[0]]]) if probs is not None else None, L.stream()))
-            for i in wave:
-                L.check(L.lib().vqw_ar_decode_wait(self._hs[i]))
-        return idx, probs
+        uniforms = _uniforms_of(uniforms, mode, B, n_steps, dev, 'n_steps')
+        rows = _row_slices(tuple(self._parts))
+        per = [_sampling_rows(settings and settings[r]) for r in rows]     # each handle its slice of the rows
 
-    def _run_sampled(self, encoding, Tz, n_steps, uniforms, ratio, audio, idx, probs, settings, rows, vp):
-        """_run with per-row sampling settings (mode 'sample'): each handle gets its slice of the rows."""
-        lib = L.lib()
-        per = []
-        for r in rows:
-            a = (L.ArSampling * (r.stop - r.start))()
-            for j, (t, k, p) in enumerate(settings[r]):
-                a[j].temperature, a[j].top_k, a[j].top_p = t, min(k, 0x7fffffff), p
-            per.append(a)
-        for wave in self._waves:
+        def part(t, i):
+            return None if t is None else L.ptr(t[rows[i]])
+
+        def parts(t, wave):
+            return None if t is None else (C.c_void_p * len(wave))(*[t[rows[i]].data_ptr() for i in wave])
+        lib, m = L.lib(), 0 if mode == 'greedy' else 1
+        for wave in self._waves:                 # one launch per wave; the waves follow each other
             if lib.vqw_ar_decode_workgroups(self._hs[wave[0]]) > 0:
                 hs = (C.c_void_p * len(wave))(*[self._hs[i].value for i in wave])
-                sp = (C.POINTER(L.ArSampling) * len(wave))(*[C.cast(per[i], C.POINTER(L.ArSampling)) for i in wave])
+                sp = None
+                if settings is not None:
+                    sp = (C.POINTER(L.ArSampling) * len(wave))(*[C.cast(per[i], C.POINTER(L.ArSampling)) for i in wave])
                 L.check(lib.vqw_ar_decode_run_group_sampled_async(
-                    hs, len(wave), vp([encoding[rows[i]] for i in wave]), Tz, ratio, n_steps, 1,
-                    vp([uniforms[rows[i]] for i in wave]), sp,
-                    vp([audio[rows[i]] for i in wave]) if audio is not None else None, vp([idx[rows[i]] for i in wave]),
-                    vp([probs[rows[i]] for i in wave]) if probs is not None else None, L.stream()))
-            else:
+                    hs, len(wave), parts(encoding, wave), Tz, ratio, n_steps, m, parts(uniforms, wave), sp, parts(audio, wave),
+                    parts(idx, wave), parts(probs, wave), L.stream()))
+            else:                                # launch-per-phase path: one handle
                 i = wave[0]
                 L.check(lib.vqw_ar_decode_run_sampled_async(
-                    self._hs[i], L.ptr(encoding[rows[i]]), Tz, ratio, n_steps, 1, L.ptr(uniforms[rows[i]]), per[i],
-                    L.ptr(audio[rows[i]]) if audio is not None else None, L.ptr(idx[rows[i]]),
-                    L.ptr(probs[rows[i]]) if probs is not None else None, L.stream()))
+                    self._hs[i], part(encoding, i), Tz, ratio, n_steps, m, part(uniforms, i), per[i], part(audio, i),
+                    part(idx, i), part(probs, i), L.stream()))
             for i in wave:
                 L.check(lib.vqw_ar_decode_wait(self._hs[i]))
         return idx, probs
@@ -456,12 +422,6 @@ class FastGenerator:
         for h in getattr(self, '_hs', []):
             L.lib().vqw_ar_decode_destroy(h)
         self._hs = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class PriorGenerator(FastGenerator):
@@ -493,14 +453,12 @@ class PriorGenerator(FastGenerator):
         if (not isinstance(codes, torch.Tensor) or codes.dtype != torch.int32 or codes.dim() != 2 or codes.shape[0] != self.B
                 or not codes.is_cuda):
             raise ValueError('codes must be an int32 [%d][T] tensor on the GPU' % self.B)
-        if spk.numel() != self.B:
-            raise ValueError('%d speaker ids for a batch of %d' % (spk.numel(), self.B))
+        _check_speakers(spk, self.B)
         T = codes.shape[1]
         if T and (int(codes.min()) < 0 or int(codes.max()) >= self.model.Q):
             raise ValueError('codes must lie in [0, %d)' % self.model.Q)
-        ratio = 64                                     # code steps per condition frame (prior.CODES_PER_FRAME)
-        cond = self.model.speaker_condition(spk.contiguous(), max(1, -(-T // ratio)))
-        self._prefill(codes.contiguous(), cond, T, ratio, audio=False)
+        cond = self.model.speaker_condition(spk.contiguous(), max(1, -(-T // PRIOR_RATIO)))
+        self._prefill(codes.contiguous(), cond, T, PRIOR_RATIO, audio=False)
         self._t = T
 
     def sample(self, n_frames, spk, mode='greedy', uniforms=None, return_probs=False, temperature=1.0, top_k=0, top_p=1.0):
@@ -508,14 +466,11 @@ class PriorGenerator(FastGenerator):
         'sample' (searchsorted(cumsum(p), u) with uniforms [B][n_frames], drawn here when None; u above the cdf's last
         value gives the last code), tempered / truncated by temperature, top_k, top_p as in FastGenerator.generate.
         Returns codes int32 [B][n_frames][, probabilities of the last step [B][k]: the distribution sampled]."""
-        if mode not in ('greedy', 'sample'):
-            raise NotImplementedError('decode mode %s not implemented' % mode)
+        _check_mode(mode)
         settings = sampling_settings(self.B, mode, temperature, top_k, top_p)
-        if spk.numel() != self.B:
-            raise ValueError('%d speaker ids for a batch of %d' % (spk.numel(), self.B))
-        ratio = 64                                     # code steps per condition frame (prior.CODES_PER_FRAME)
-        Tz = -(-(self._t + n_frames) // ratio)
+        _check_speakers(spk, self.B)
+        Tz = -(-(self._t + n_frames) // PRIOR_RATIO)
         cond = self.model.speaker_condition(spk.contiguous(), Tz)
-        idx, probs = self._run(cond, n_frames, mode, uniforms, ratio, None, return_probs, settings)
+        idx, probs = self._run(cond, n_frames, mode, uniforms, PRIOR_RATIO, None, return_probs, settings)
         self._t += n_frames
         return (idx, probs) if return_probs else idx
