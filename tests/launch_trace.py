@@ -9,7 +9,8 @@ too.  Nothing is computed; the tensors hold whatever torch.empty left in them.
 
 `CASES` are the shapes and switches under which Encoder_64 takes each of its branches (plus the two other encoders), the decoder's
 own branches (bf16, the development ladder, the weight-gradient, head and condition switches, a length the plane engine refuses),
-the latent prior, train_step around the passes and the forward-only passes (score, decoder_states, encode); `LAYOUTS` the
+the latent prior, train_step around the passes, the forward-only passes (score, decoder_states, encode) and the backward stack at 8
+layers (`DEEP`: the chain runs ahead of per-layer weight gradients, batches flush inside the loop); `LAYOUTS` the
 configurations whose flat-buffer layout, state_dict and reference names are pinned.  tests/golden/launch_trace.json holds the
 SHA-256 of every case's JSON-serialised trace, its call names (for a readable failure; DIGEST_ONLY cases: their number) and the
 layout facts (the prior's: their digest).
@@ -41,7 +42,11 @@ SPEAKERS = 109
 
 PRIOR = dict(WAVENET, quantization_channels=512, speaker_embedding=64, learning_rate_schedule={'0': 1e-4})
 
-# model: keys laid over MODEL (kind 'prior': over PRIOR); env: VQW_* switches (every other VQW_* variable is unset); active:
+# the deep stack: 8 layers in 2 cycles, where the chain runs two layers ahead of the per-layer weight gradients (the ring wait) and a
+# weight-gradient batch fills and flushes inside the loop -- what 2 layers never reach
+DEEP = dict(num_cycles=2, num_cycle_layers=4, dilation_rates=[1, 2, 4, 8, 1, 2, 4, 8])
+
+# model: keys laid over MODEL (kind 'prior': over PRIOR); wavenet: keys laid over WAVENET (kind 'prior': over PRIOR, under `model`); env: VQW_* switches (every other VQW_* variable is unset); active:
 # model._x3_active; grad_sync: with the recording stub; kind: 'prior' = prior.LatentPrior over int32 codes instead of a VQVAE;
 # run: what is recorded instead of forward() + backward() -- '_encode': _encode(save=False) on a train=False workspace,
 # 'train_step': one immediate train_step, 'score': _score_pass on the score workspace, 'states': decoder_states of a 700-step
@@ -94,6 +99,26 @@ DIGEST_ONLY = {
     # the deferred range flag: two steps and their resolution; with the void flag preset, the whole replay path
     'train-step-deferred': dict(run='deferred'),
     'train-step-deferred-flagged': dict(run='deferred', void=True),
+    # the backward stack at 8 layers (DEEP), under every switch that changes its route, buffers or weight-gradient schedule
+    'deep': dict(wavenet=DEEP),
+    'deep-wg-batches-2-3': dict(wavenet=DEEP, env={'VQW_WG_GATE_BATCH': '2', 'VQW_WG_RES_BATCH': '3'}),     # batches flush inside the loop
+    'deep-wgrad-batch-0': dict(wavenet=DEEP, env={'VQW_WGRAD_BATCH': '0'}),                                # per layer: the rings and their waits
+    'deep-wgrad-batch-0-overlap-0': dict(wavenet=DEEP, env={'VQW_WGRAD_BATCH': '0', 'VQW_OVERLAP': '0'}),
+    'deep-overlap-0': dict(wavenet=DEEP, env={'VQW_OVERLAP': '0'}),
+    'deep-wgrad-x3-0': dict(wavenet=DEEP, env={'VQW_WGRAD_X3': '0'}),
+    'deep-wgrad-qp-0': dict(wavenet=DEEP, env={'VQW_WGRAD_QP': '0'}),
+    'deep-wgrad-pp-0': dict(wavenet=DEEP, env={'VQW_WGRAD_PP': '0'}),
+    'deep-engine-fp32': dict(wavenet=DEEP, env={'VQW_ENGINE': 'fp32'}),
+    'deep-fp32-repeat': dict(wavenet=DEEP, active=False),
+    'deep-bf16': dict(wavenet=DEEP, env={'VQW_DTYPE': 'bf16'}),
+    'deep-ladder-4': dict(wavenet=DEEP, env={'VQW_GATE_F16X3': '4'}),
+    'deep-ladder-5': dict(wavenet=DEEP, env={'VQW_GATE_F16X3': '5'}),
+    'deep-save-tanh-1': dict(wavenet=DEEP, env={'VQW_SAVE_TANH': '1'}),
+    'deep-save-gated-1': dict(wavenet=DEEP, env={'VQW_SAVE_GATED': '1'}),
+    'deep-head-x3-0': dict(wavenet=DEEP, env={'VQW_HEAD_X3': '0'}),
+    'deep-grad-sync': dict(wavenet=DEEP, grad_sync=True),
+    'deep-prior': dict(wavenet=DEEP, kind='prior'),
+    'deep-refused-length': dict(wavenet=DEEP, T=1088),
 }
 CASES.update(DIGEST_ONLY)
 LAYOUTS = {'%s-vq%d-spk%d' % (enc, vq, spk): {'encoder': enc, 'use_vq': bool(vq), 'speaker_embedding': spk}
@@ -218,11 +243,11 @@ def set_switches(monkeypatch, env):
         monkeypatch.setenv(k, v)
 
 
-def make_model(pkg, kind, keys):
-    """A fresh model on the CPU: a VQVAE of MODEL / WAVENET, or (kind 'prior') a LatentPrior of PRIOR, with `keys` laid over."""
+def make_model(pkg, kind, keys, wavenet=None):
+    """A fresh model on the CPU: a VQVAE of MODEL / WAVENET, or (kind 'prior') a LatentPrior of PRIOR, with `keys` (and `wavenet`) laid over."""
     if kind == 'prior':
-        return pkg.prior.LatentPrior(dict(PRIOR, **keys), SPEAKERS, device='cpu')
-    return pkg.model.VQVAE(dict(MODEL, **keys), dict(WAVENET), SPEAKERS, device='cpu', seed=0)
+        return pkg.prior.LatentPrior(dict(PRIOR, **dict(wavenet or {}, **keys)), SPEAKERS, device='cpu')
+    return pkg.model.VQVAE(dict(MODEL, **keys), dict(WAVENET, **(wavenet or {})), SPEAKERS, device='cpu', seed=0)
 
 
 def run_case(monkeypatch, pkg, name):
@@ -231,7 +256,7 @@ def run_case(monkeypatch, pkg, name):
     set_switches(monkeypatch, case.get('env', {}))
     rec = install(monkeypatch, pkg)
     prior, run = case.get('kind') == 'prior', case.get('run')
-    model = make_model(pkg, case.get('kind'), case.get('model', {}))
+    model = make_model(pkg, case.get('kind'), case.get('model', {}), case.get('wavenet'))
     model._x3_active = case.get('active', True)
     if case.get('grad_sync'):
         model.grad_sync = GradSyncStub(rec)

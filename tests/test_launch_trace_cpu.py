@@ -2,7 +2,8 @@
 streams, event edges and grad_sync ranges, recorded on the CPU (tests/launch_trace.py) and held to the digests in
 tests/golden/launch_trace.json -- for the three encoders and for every branch of Encoder_64's passes (fp16x3 layers, split-K and
 unsplit short layers, plane or register weight gradients, one or two streams, a pass that saves nothing), for the decoder's own
-branches, the latent prior, train_step and the forward-only passes.  Next to it the facts
+branches (at 2 layers, and at 8 where the backward stack's rings and weight-gradient batches come into play), the latent prior,
+train_step and the forward-only passes.  Next to it the facts
 checkpoints and the data-parallel bucket ranges rest on: flat-buffer segments and offsets, state_dict keys, reference names."""
 import json
 import os
@@ -30,7 +31,8 @@ def test_launches_are_the_golden_ones(pkg, name):
     assert LT.digest(trace) == want['sha256'], 'same calls, other arguments / buffers / streams: python tests/launch_trace.py --dump %s' % name
 
 
-@pytest.mark.parametrize('name', ['enc64', 'magenta', '2019', 'enc64-grad-sync', 'train-step-deferred', 'train-step-deferred-flagged'])
+@pytest.mark.parametrize('name', ['enc64', 'magenta', '2019', 'enc64-grad-sync', 'train-step-deferred', 'train-step-deferred-flagged', 'deep',
+                                  'deep-wgrad-batch-0'])
 def test_a_second_run_gives_the_same_trace(pkg, name):
     digests = []
     for _ in range(2):
@@ -84,6 +86,30 @@ def test_the_cases_reach_the_branches_they_are_named_for(pkg):
     refused = {e[0] for e in traced('dec-refused-length') if e[0].startswith('f16x3_')}
     assert 'f16x3_strided_conv' in refused and not refused & {'f16x3_gate_conv', 'f16x3_out_conv', 'f16x3_pack_gate_weights', 'f16x3_wgrad_batch'}
     assert not any(n.startswith('f16x3_') for n in names(traced('dec-refused-length-enc-x3-0')))
+    # the deep stack: what 2 layers never reach.  Per-layer weight gradients on a side stream: the chain waits for the rings ...
+    waits = lambda t: sum(1 for e in t if e[0] == 'wait_event' and e[1] == 'main')      # noqa: E731
+    deep = {name: traced(name) for name in LT.CASES if name.startswith('deep')}
+    for name in ('deep-wgrad-batch-0', 'deep-engine-fp32', 'deep-wgrad-x3-0'):
+        assert waits(deep[name]) == 6, name                                # layers 5..0 of 8: two layers ahead, then one wait per layer
+    assert not any(waits(traced(name)) for name in LT.CASES if name not in deep)
+    assert waits(deep['deep']) == 0 and not waits(deep['deep-wgrad-batch-0-overlap-0'])
+    # ... batches that fill and flush inside the loop, on both tap-alignment classes (dilations 1, 2 / 4, 8)
+    batches = lambda t: [e for e in t if e[0] == 'f16x3_wgrad_batch']                  # noqa: E731
+    assert len(batches(deep['deep'])) == 4 and len(batches(deep['deep-wg-batches-2-3'])) == 8
+    gate_taps = {tuple(p['taps']) for e in batches(deep['deep-wg-batches-2-3']) for p in e[3]['problems'] if 'taps' in p}
+    assert {taps for taps in gate_taps if any(s % 4 for s in taps)} and {taps for taps in gate_taps if not any(s % 4 for s in taps)}
+    assert names(deep['deep-wgrad-batch-0']).count('f16x3_wgrad') == 20
+    assert names(deep['deep-engine-fp32']).count('wgrad_gemm') == 25
+    # ... one stream: no event, nothing on a side stream
+    for name in ('deep-wgrad-batch-0-overlap-0', 'deep-overlap-0'):
+        assert {e[1] for e in deep[name]} == {'main'} and 'record' not in names(deep[name]), name
+    assert batches(deep['deep-overlap-0']) and not batches(deep['deep-wgrad-batch-0-overlap-0'])
+    # ... the gate kernels' q operand: the planes gate backward wrote (qp), or fp32 dpre
+    gate_probs = lambda t: [p for e in batches(t) if e[2]['Q0'] == 512 and 'seg_T' in e[2] for p in e[3]['problems']]     # noqa: E731
+    assert len(gate_probs(deep['deep'])) == 8 and all('q_planes' in p and 'q0' not in p for p in gate_probs(deep['deep']))
+    assert len(gate_probs(deep['deep-wgrad-qp-0'])) == 8 and all('q0' in p and 'q_planes' not in p for p in gate_probs(deep['deep-wgrad-qp-0']))
+    assert names(deep['deep-fp32-repeat']).count('f16x3_amax') > names(deep['deep-engine-fp32']).count('f16x3_amax') + 8      # (the calibrating repeat: per layer)
+    assert len({LT.digest(t) for t in deep.values()}) == len(deep)
 
 
 @pytest.mark.parametrize('name', list(LT.LAYOUTS))

@@ -45,6 +45,15 @@ class record:
         _recording = self.prev
 
 
+def scratch(ws, key, make):
+    """ws[key], made by make() at first use: the buffers of a workspace that only some passes need.  What make() obtains
+    through `empty()` joins ws['_poison'], the buffers refilled at the start of every step."""
+    if key not in ws:
+        with record(ws['_poison']):
+            ws[key] = make()
+    return ws[key]
+
+
 def repoison(tensors):
     if POISON:
         for t in tensors:

@@ -157,12 +157,9 @@ class Encoder64(Encoder):
         of one launch (at most two rounds of 128-row blocks) and the tiles' ticket counters, which every launch leaves at zero."""
         if not model.sw.sconv_split:
             return {}
-        if 'sslab' not in ws:
-            cus = torch.cuda.get_device_properties(model.dev).multi_processor_count
-            ws['sslab'] = A.empty(cus * 65536, device=model.dev)
-            ws['_poison'].append(ws['sslab'])
-            ws['scount'] = torch.zeros(1024, dtype=torch.int32, device=model.dev)
-        return {'split_slab': ws['sslab'], 'split_counters': ws['scount']}
+        slab = lambda: A.empty(torch.cuda.get_device_properties(model.dev).multi_processor_count * 65536, device=model.dev)    # noqa: E731
+        return {'split_slab': A.scratch(ws, 'sslab', slab),
+                'split_counters': A.scratch(ws, 'scount', lambda: torch.zeros(1024, dtype=torch.int32, device=model.dev))}
 
     @staticmethod
     def _short_layer_split(M, T_out, B, cus=256):

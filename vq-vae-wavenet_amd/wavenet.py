@@ -117,6 +117,144 @@ def layer_scope(i, num_cycle_layers, scope='decoder'):
     return '%s/cycle_%d/layer_%d' % (scope, 1 + i // num_cycle_layers, 1 + i % num_cycle_layers)
 
 
+class _WgradSchedule:
+    """The residual stack's weight gradients, bias sums and share of the condition gradient, beside the backward chain
+    (WaveNet._backward_stack): where the chain writes per layer, and when the launches go out.  The chain calls
+        buffers(l) -> (dpre, dplanes, dnet_next)    before layer l: where its gate backward and input gradient write
+        layer(l, dnet, dpre, ready)                 behind layer l's two launches (dnet: d loss / d net[l + 1], None at the top
+                                                    layer; ready: the mark on main behind gate backward, side_mark)
+        finish()                                    behind layer 0
+    Nothing downstream waits for what a schedule launches: it forks to the side stream (main itself without VQW_OVERLAP), which
+    the chain joins after finish()."""
+
+    def __init__(self, model, ws, dskip, main, side):
+        self.m, self.ws, self.dskip, self.main, self.side = model, ws, dskip, main, side
+        self.plan, self.sc = ws['plan'], model._guards(ws['plan'])[0]
+
+
+class _PerLayerWgrads(_WgradSchedule):
+    """A layer's launches as soon as its dpre is ready: the plane engine's two kernels (VQW_WGRAD_BATCH=0), or the fp32 engine's
+    with their row sums.  Two streams: the chain stays on main and these run on the side stream, so one kernel's thin last round
+    is filled by the other's blocks.  dnet / dpre are rings (3 / 2 buffers): the chain may run two layers ahead of the side stream
+    before it has to wait for it."""
+
+    def __init__(self, model, ws, dskip, main, side):
+        super().__init__(model, ws, dskip, main, side)
+        self.done = {}       # layer -> the event behind its launches on the side stream
+        self.seg = None if self.plan.wg_x3 else A.empty(ws['B'], 2 * model.R, ws['Tz'], device=model.dev)
+
+    def buffers(self, l):
+        if (l + 2) in self.done:
+            self.main.wait_event(self.done[l + 2])            # dpre[l % 2] and dnet[(l - 1) % 3] are free again
+        return self.ws['dpre_ring'][l % 2], self.ws.get('dp'), self.ws['dnet_ring'][(l - 1) % 3]
+
+    def layer(self, l, dnet, dpre, ready):
+        m, ws, sc, dskip = self.m, self.ws, self.sc, self.dskip
+        G, R, S, B, T, Tz, dce = m.G, m.R, m.S, ws['B'], ws['T'], ws['Tz'], ws['dcondenc']
+        top, taps, md = dnet is None, causal_taps(m.ks, m.dil[l]), m.x3_mode_bwd
+        with side_after(self.side, ready):
+            if self.plan.wg_x3:    # weight gradients on the fp16 pipe too: operands split in registers with the planes' guard scales;
+                # the bias sums and the condition gradient (sums of dpre per condition frame) come out of the same kernels
+                K.f16x3_wgrad(p=ws['gated'][l], q0=dskip, q1=dnet, dw=G['out_w'][l], slab=ws['wslab'], B=B,
+                              T=T, Cp=R, Q0=S, Q1=0 if top else R, lddw=S + R, taps=[0], q0_scale=sc('G'), q1_scale=sc('G'),
+                              q_total=None if top else G['out_b'][l], total_cols=(S, S + R), mode=md)
+                K.f16x3_wgrad(p=ws['net'][l], q0=dpre, dw=G['gated_w'][l], slab=ws['wslab'], B=B, T=T, Cp=R, Q0=2 * R,
+                              taps=taps, p_scale=sc('X', l), q0_scale=sc('DP', l),
+                              q_seg=dce.view(-1)[l * 2 * R * Tz:], seg_T=Tz, seg_bstride=m.Mall * Tz, mode=md)
+            else:
+                K.wgrad_gemm(p=ws['gated'][l], q0=dskip, q1=dnet, dw=G['out_w'][l], B=B, T_q=T, T_p=T,
+                             Cp=R, Q0=S, Q1=0 if top else R, lddw=S + R, taps=[0])
+                if not top:
+                    K.rowsum(dnet, total=G['out_b'][l][S:])
+                K.wgrad_gemm(p=ws['net'][l], q0=dpre, dw=G['gated_w'][l], B=B, T_q=T, T_p=T, Cp=R, Q0=2 * R, taps=taps)
+                K.rowsum(dpre, seg_out=self.seg, total=G['gated_b'][l], seg=ws['ratio'])
+                dce[:, l * 2 * R:(l + 1) * 2 * R].copy_(self.seg)
+            if self.side is not self.main:
+                self.done[l] = torch.cuda.Event()
+                self.done[l].record(self.side)
+
+    def finish(self):
+        pass
+
+
+class _BatchedWgrads(_WgradSchedule):
+    """The plane engine's default: dpre and dnet of EVERY layer are kept (4.9 GB at B = 8 instead of rings of 2 / 3 buffers) and
+    the weight gradients of several layers go out as ONE launch (vqw_f16x3_wgrad_batch):
+      * the skip halves of all layers' 1x1 kernels, dW_s[l] = gated[l] (x) dskip -- dskip is the same tensor for every
+        layer -- at once, before the first layer: 60 tiles x 4 K splits instead of 30 x (2 tiles x 80 splits);
+      * the gate kernels of up to 6 layers (VQW_WG_GATE_BATCH) (layers whose tap shifts are all multiples of 4 and the others --
+        dilations 1 and 2 -- in separate batches: the latter need the kernel's slower unaligned-window variant);
+      * the residual halves, dW_r[l] = gated[l] (x) dnet[l+1], of up to 29 layers (VQW_WG_RES_BATCH).
+    A launch writes tiles x splits <= CUs partial 256x256 tiles to the slab whatever its batch size: per layer the slab
+    traffic (2 x 61 MB per single launch, 7.3 GB per step) falls with the batch size, dskip is read once per XCD instead
+    of once per layer, and 68 reductions become ~10.
+    ... and (qp) dpre is kept as the operand PLANES gate backward writes for the input gradient anyway: the gate kernels' weight
+    gradient reads its q operand from them (transposed LDS reads, vqw_f16x3_wgrad q_planes) and gate backward no longer
+    writes fp32 dpre at all (109 of its 312 MB per layer); (pp) p = the layer's input planes and the gated planes likewise."""
+
+    def __init__(self, model, ws, dskip, main, side):
+        super().__init__(model, ws, dskip, main, side)
+        m, plan, sc = model, self.plan, self.sc
+        R, S, L, B, T = m.R, m.S, m.L, ws['B'], ws['T']
+        A.scratch(ws, 'dnet_all', lambda: [A.empty(B, R, T, device=m.dev) for _ in range(L)])       # dnet_all[l] = d loss / d net[l]
+        if plan.qp:
+            A.scratch(ws, 'dp_all', lambda: [A.empty(2 * B * 2 * R * T, dtype=torch.float16, device=m.dev) for _ in range(L)])
+        else:
+            A.scratch(ws, 'dpre_all', lambda: [A.empty(B, 2 * R, T, device=m.dev) for _ in range(L)])
+        self.pend_gate, self.pend_res = {False: [], True: []}, []      # layers waiting for a launch (gate: by tap alignment)
+        # the skip halves of all layers (dskip: the first S / 8 chunks of the gradient planes)
+        qsk = dict(q_planes=ws['gr'], q_planes_KC=(S + R) // 8, q_planes_scale=plan.GS) if (plan.qp and plan.gbwd_x3) else dict(q0=dskip)
+        for i0 in range(0, L, K.WGRAD_MAX_BATCH):
+            self._launch([dict(dw=m.G['out_w'][i].view(-1), **self._gated(i)) for i in range(i0, min(L, i0 + K.WGRAD_MAX_BATCH))],
+                         Q0=S, lddw=S + R, taps=[0], q0_scale=sc('G'), **qsk)
+
+    def _gated(self, i):         # layer i's gated output as the p operand
+        m, ws = self.m, self.ws
+        return dict(p_planes=ws['gp'], p_planes_kc0=i * (m.R // 8), p_planes_KC=m.L * (m.R // 8)) if self.plan.pp else dict(p=ws['gated'][i])
+
+    def _launch(self, probs, **common):
+        ws = self.ws
+        with side_after(self.side, side_mark(self.main, self.side)):
+            K.f16x3_wgrad_batch(probs, slab=ws['wslab'], B=ws['B'], T=ws['T'], Cp=self.m.R, mode=self.m.x3_mode_bwd, **common)
+
+    def buffers(self, l):
+        ws = self.ws
+        return (None, ws['dp_all'][l], ws['dnet_all'][l]) if self.plan.qp else (ws['dpre_all'][l], ws.get('dp'), ws['dnet_all'][l])
+
+    def layer(self, l, dnet, dpre, ready):
+        odd = any(shift % 4 for shift in mirrored_taps(self.m.ks, self.m.dil[l]))
+        self.pend_gate[odd].append(l)
+        if len(self.pend_gate[odd]) >= self.plan.gate_batch:      # 6: 36 tiles x 7 K splits = 252 blocks (tools/wg_batch_sweep.sh)
+            self._flush_gate(odd)
+        if dnet is not None:         # layer l + 1 wrote dnet[l + 1] before this one (the top layer has no dnet: its residual kernel gets no gradient)
+            self.pend_res.append(l)
+            if len(self.pend_res) >= self.plan.res_batch:
+                self._flush_res()
+
+    def _flush_gate(self, odd):
+        m, ws, plan, sc = self.m, self.ws, self.plan, self.sc
+        layers, self.pend_gate[odd] = self.pend_gate[odd], []
+        if layers:
+            R, Tz, dce = m.R, ws['Tz'], ws['dcondenc']
+            self._launch([dict(dw=m.G['gated_w'][i], taps=causal_taps(m.ks, m.dil[i]),
+                               p_scale=sc('X', i), q0_scale=sc('DP', i), q_seg=dce.view(-1)[i * 2 * R * Tz:],
+                               **(dict(p_planes=ws['xp_all'][i]) if plan.pp else dict(p=ws['net'][i])),
+                               **(dict(q_planes=ws['dp_all'][i], q_planes_scale=plan.GS) if plan.qp else dict(q0=ws['dpre_all'][i]))) for i in layers],
+                         Q0=2 * R, seg_T=Tz, seg_bstride=m.Mall * Tz)
+
+    def _flush_res(self):
+        m, ws, S = self.m, self.ws, self.m.S
+        layers, self.pend_res = self.pend_res, []
+        if layers:
+            self._launch([dict(q0=ws['dnet_all'][i + 1], dw=m.G['out_w'][i].view(-1)[S:], q_total=m.G['out_b'][i][S:], **self._gated(i))
+                          for i in layers], Q0=m.R, lddw=S + m.R, taps=[0], q0_scale=self.sc('G'), total_cols=(0, m.R))
+
+    def finish(self):
+        self._flush_gate(False)
+        self._flush_gate(True)
+        self._flush_res()
+
+
 class WaveNet:
     """Decoder/WaveNet/wavenet.py:24-172 with its training step: flat parameters, engine switches and range guards, workspaces,
     forward, backward, Adam + EMA, teacher-forced scoring.  What makes the condition (and, for the prior, the input stage) is the
@@ -216,6 +354,7 @@ class WaveNet:
         self.x3_amax = torch.zeros(self.SL['N'], dtype=torch.int32, device=self.dev)
         self.x3_flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self.x3_void = torch.zeros(1, dtype=torch.int32, device=self.dev)      # deferred mode: a flagged step is waiting to be repeated
+        self._guard_sets = {}                   # (sc, am, flag) per kind of pass (_guards)
         self.defer_guard = sw.defer_guard       # read the range flag one step late (train_step)
         self._pending, self._void_host, self._void_slot, self._in_step = [], None, 0, False
         # the condition projections (K = Cc ~ 80, rows of Tz ~ 104 frames) on their own fp32-MFMA kernels (csrc/cond_proj.hip)
@@ -491,11 +630,7 @@ class WaveNet:
     def _wslab(self, ws):
         """Slab of the engine's weight-gradient kernels: the partial 256x256 tiles of ONE launch.  The launcher cuts K so that
         tiles x K splits <= the device's CU count (vqw_device_cus), hence one 256x256 fp32 tile per CU."""
-        if 'wslab' not in ws:
-            cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
-            ws['wslab'] = A.empty(cus * 65536, device=self.dev)
-            ws['_poison'].append(ws['wslab'])
-        return ws['wslab']
+        return A.scratch(ws, 'wslab', lambda: A.empty(torch.cuda.get_device_properties(self.dev).multi_processor_count * 65536, device=self.dev))
 
     def _side_stream(self):
         if self._side is None:
@@ -573,6 +708,16 @@ class WaveNet:
         """The accessor of the guard slots of buf = x3_scale or x3_amax: sc('X', l), am('G') give the 1-element view of slot (name, i); None where the guards are off."""
         return (lambda name, i=0: buf[self.SL[name] + i:self.SL[name] + i + 1]) if on else (lambda name, i=0: None)
 
+    def _guards(self, plan):
+        """(sc, am, flag) of any stage of a pass, forward or backward: the accessors of the guard's scales and max-abs collectors
+        (_slots) and the range flag, each off (None) unless the plan runs the guarded engine.  calib: the fp32 repeat of a step
+        measures what the planes would have held, so its collectors are on (nothing of it runs on the plane engine).  Built once
+        per kind of pass: the buffers are the model's for its lifetime."""
+        key = (plan.gd, plan.gd or plan.calib)
+        if key not in self._guard_sets:
+            self._guard_sets[key] = (self._slots(self.x3_scale, key[0]), self._slots(self.x3_amax, key[1]), self.x3_flag if key[0] else None)
+        return self._guard_sets[key]
+
     def _decode_prologue(self, x, ws, save=True):
         """Everything of the decoder's forward pass that does not depend on the front: inputs / labels, the preprocess conv
         (wavenet.py:33-44), this step's guard scales and weight planes, the skip start (wavenet.py:53-54).  Leaves the plan of
@@ -586,7 +731,7 @@ class WaveNet:
         self._decode_input(x, ws)
         net, gd, WS, ngrp, md = ws['net'], plan.gd, plan.WS, plan.ngrp, self.x3_mode_fwd
         ws['skip_groups'], ws['x3_used'] = ngrp if plan.f16x3_skip else 0, plan.x3_used
-        sc, am, flag = self._slots(self.x3_scale, gd), self._slots(self.x3_amax, gd), self.x3_flag if gd else None
+        sc, am, flag = self._guards(plan)
         if gd:
             K.f16x3_amax(P['gated_w'], am('WG'), flag=flag)
             K.f16x3_amax(P['out_w'], am('WO'), flag=flag)
@@ -630,8 +775,8 @@ class WaveNet:
         P, R, S, Q, L, B, T, Tz = self.P, self.R, self.S, self.Q, self.L, ws['B'], ws['T'], ws['Tz']
         f16x3, f16x3_skip, f16x3_out, ngrp, WS, head_x3, drop_th, drop_g, save = (
             plan.f16x3, plan.f16x3_skip, plan.f16x3_out, plan.ngrp, plan.WS, plan.head_x3, plan.drop_th, plan.drop_g, plan.save)
-        Lg, md, flag = L // ngrp, self.x3_mode_fwd, self.x3_flag if plan.gd else None
-        sc, am = self._slots(self.x3_scale, plan.gd), self._slots(self.x3_amax, plan.gd)
+        Lg, md = L // ngrp, self.x3_mode_fwd
+        sc, am, flag = self._guards(plan)
         xpl = (lambda l: ws['xp_all'][l]) if plan.keep_xp else (lambda l: ws['xp'])    # noqa: E731
         net = ws['net']
         if self.cond_proj:                                                                # all add_condition 1x1s
@@ -653,25 +798,23 @@ class WaveNet:
                                   out_planes_kc0=l * (R // 8) if f16x3_skip else 0, out_planes_KC=L * (R // 8) if f16x3_skip else 0,
                                   x_scale=sc('X', l), w_scale=sc('WG'), mode=md)
                 if f16x3_skip:   # residual half now; the skip half of all layers after the loop
-                    if l == L - 1:
-                        continue     # the top layer's residual output feeds nothing (wavenet.py:58-78: TF prunes the op from the graph)
-                    K.f16x3_out_conv(xp=ws['gp'], xp_kc0=l * (R // 8), xp_KC=L * (R // 8), Cin=R, wp=ws['wres'][l],
-                                     bias=P['out_b'][l][S:], net_in=net[l], net_out=net[l + 1], net_out_planes=xpl(l + 1),
-                                     B=B, T=T, R=R, S=0, w_scale_inv=1.0 / WS, w_scale=sc('WO'), out_scale=sc('X', l + 1),
-                                     out_amax=am('X', l + 1), flag=flag, mode=md)
-                elif f16x3_out:
+                    if l < L - 1:    # the top layer's residual output feeds nothing (wavenet.py:58-78: TF prunes the op from the graph)
+                        K.f16x3_out_conv(xp=ws['gp'], xp_kc0=l * (R // 8), xp_KC=L * (R // 8), Cin=R, wp=ws['wres'][l],
+                                         bias=P['out_b'][l][S:], net_in=net[l], net_out=net[l + 1], net_out_planes=xpl(l + 1),
+                                         B=B, T=T, R=R, S=0, w_scale_inv=1.0 / WS, w_scale=sc('WO'), out_scale=sc('X', l + 1),
+                                         out_amax=am('X', l + 1), flag=flag, mode=md)
+                    continue
+                if f16x3_out:
                     K.f16x3_out_conv(xp=ws['gp'], wp=ws['wop'][l], bias=P['out_b'][l], skip=ws['skip'], net_in=net[l],
                                      net_out=net[l + 1], net_out_planes=xpl(l + 1), B=B, T=T, R=R, S=S, w_scale_inv=1.0 / 256.0, mode=md)
-                else:
-                    K.conv_gemm(x0=ws['gated'][l], w=P['out_w'][l], bias=P['out_b'][l], out0=ws['skip'], out1=net[l + 1],
-                                aux1=net[l], B=B, T_in=T, T_out=T, M=S + R, M0=S, C0=R, taps=[0],
-                                epilogue=K.EPI_ACCUM_SPLIT, tile=self.tiles['out'])
-                continue
-            K.conv_gemm(x0=net[l], w=P['gated_w'][l], bias=P['gated_b'][l], out0=ws['gated'][l],
-                        save0=ws['th'][l] if save else None, save1=ws['sg'][l] if save else None,
-                        cond=ce_flat[l * 2 * R * Tz:], cond_T=Tz, cond_bstride=cbs, B=B, T_in=T, T_out=T,
-                        M=2 * R, C0=R, taps=causal_taps(self.ks, d),
-                        epilogue=K.EPI_GATE)                                              # wavenet_ops.py:104-114
+                    continue
+            else:
+                K.conv_gemm(x0=net[l], w=P['gated_w'][l], bias=P['gated_b'][l], out0=ws['gated'][l],
+                            save0=ws['th'][l] if save else None, save1=ws['sg'][l] if save else None,
+                            cond=ce_flat[l * 2 * R * Tz:], cond_T=Tz, cond_bstride=cbs, B=B, T_in=T, T_out=T,
+                            M=2 * R, C0=R, taps=causal_taps(self.ks, d),
+                            epilogue=K.EPI_GATE)                                          # wavenet_ops.py:104-114
+            # the 1x1 skip + residual conv on the fp32 engine (also behind a plane gate conv: ladder step 1)
             K.conv_gemm(x0=ws['gated'][l], w=P['out_w'][l], bias=P['out_b'][l], out0=ws['skip'], out1=net[l + 1],
                         aux1=net[l], B=B, T_in=T, T_out=T, M=S + R, M0=S, C0=R, taps=[0],
                         epilogue=K.EPI_ACCUM_SPLIT, tile=self.tiles['out'])                                       # :132-136, wavenet.py:72-73
@@ -925,11 +1068,6 @@ class WaveNet:
         self._backward_tail(x, ws, dskip, dnet)
         self._backward_front(x, spk, ws)
 
-    def _backward_guards(self, plan):
-        """(sc, am, flag) of a backward stage: the accessors of the guard's scales and max-abs collectors (_slots) and the range flag."""
-        am = self._slots(self.x3_amax, plan.gd or plan.calib)      # (calib: the fp32 repeat of a step measures what the planes would have held)
-        return self._slots(self.x3_scale, plan.gd), am, self.x3_flag if plan.gd else None
-
     def _backward_head(self, ws):
         """postprocess2 / postprocess1 (wavenet.py:79-96) from d logits: their gradients, postprocess1's part of the condition
         gradient (ws['dcondenc']), and d skip, which it returns (in ws['skip'])."""
@@ -939,7 +1077,7 @@ class WaveNet:
         cbs, dce = self.Mall * Tz, ws['dcondenc']
         plan, md = ws['plan'], self.x3_mode_bwd
         calib, GSh = plan.calib, plan.GSh
-        sc, am, flag = self._backward_guards(plan)
+        sc, am, flag = self._guards(plan)
         if plan.head_x3:
             # the convs around the stack on the fp16x3 engine (forward: _decode_layers): d logits as planes with a fixed scale
             # (|d logits| <= 1 / (B T)), each input gradient hands the next one its planes, the weight gradients split their fp32
@@ -981,176 +1119,91 @@ class WaveNet:
         return skip
 
     def _backward_stack(self, ws, dskip):
-        """The residual stack, top layer first (wavenet.py:63-74): gate backward -> input gradient down the layers, the layers'
-        weight gradients, bias sums and their part of the condition gradient beside them.  Returns dnet = d loss / d net[0]
-        without the skip start's share."""
-        P, G, R, S, L, ks = self.P, self.G, self.R, self.S, self.L, self.ks
-        B, T, Tz, ratio = ws['B'], ws['T'], ws['Tz'], ws['ratio']
-        cbs, dce = self.Mall * Tz, ws['dcondenc']
-        plan, md = ws['plan'], self.x3_mode_bwd
-        head_x3, dgrad_x3, gbwd_x3, wg_x3, batched, qp, pp, calib, GS, WS, th_dropped, g_dropped = (
-            plan.head_x3, plan.dgrad_x3, plan.gbwd_x3, plan.wg_x3, plan.batched, plan.qp, plan.pp, plan.calib, plan.GS, plan.WS, plan.drop_th, plan.drop_g)
-        sc, am, flag = self._backward_guards(plan)
-        net = ws['net']
-        seg_l = A.empty(B, 2 * R, Tz, device=self.dev)
-        # Two streams: the chain gate-backward -> input gradient -> next layer stays on the current stream, the
-        # weight gradients and bias/condition sums of a layer (which nothing downstream waits for) run on a side
-        # stream, so one kernel's thin last round is filled by the other's blocks.  dnet / dpre are rings (3 / 2
-        # buffers): the chain may run two layers ahead of the side stream before it has to wait for it.
+        """The residual stack, top layer first (wavenet.py:63-74): the chain gate backward -> input gradient down the layers on
+        the current stream.  The layers' weight gradients, bias sums and their part of the condition gradient go out beside it
+        by a schedule (_BatchedWgrads / _PerLayerWgrads), which also says where each layer writes.  Returns dnet =
+        d loss / d net[0] without the skip start's share."""
+        P, G, R, S, L, ks, B, T = self.P, self.G, self.R, self.S, self.L, self.ks, ws['B'], ws['T']
+        plan, md, dce = ws['plan'], self.x3_mode_bwd, ws['dcondenc']
+        sc, am, flag = self._guards(plan)
         main = torch.cuda.current_stream()
         side = self._side_stream() if self.overlap_wgrad else main
-        dnet_ring, dpre_ring = ws['dnet_ring'], ws['dpre_ring']
-        if dgrad_x3:
-            K.f16x3_pack_weights_t(P['gated_w'], ws['wdg'], ks * 2 * R, R, 2 * R, 2 * R, R * 2 * R, WS, count=L, scale_dev=sc('WG'), mode=md)
-        if gbwd_x3:
-            K.f16x3_pack_weights_t(P['out_w'], ws['wgb'], S + R, R, S + R, S + R, R * (S + R), WS, count=L, scale_dev=sc('WO'), mode=md)
-            K.f16x3_pack_weights_t(P['out_w'][L - 1], ws['wgb_top'], S, R, S, S + R, 0, WS, scale_dev=sc('WO'), mode=md)       # the top layer has no dnet
-            if not head_x3:      # (the input gradient of postprocess1 wrote them otherwise)
-                K.f16x3_split_activations(dskip, ws['gr'], B, S, T, scale=GS, kc0=0, KC=(S + R) // 8, scale_dev=sc('G'),
+        if plan.dgrad_x3:
+            K.f16x3_pack_weights_t(P['gated_w'], ws['wdg'], ks * 2 * R, R, 2 * R, 2 * R, R * 2 * R, plan.WS, count=L, scale_dev=sc('WG'), mode=md)
+        if plan.gbwd_x3:
+            K.f16x3_pack_weights_t(P['out_w'], ws['wgb'], S + R, R, S + R, S + R, R * (S + R), plan.WS, count=L, scale_dev=sc('WO'), mode=md)
+            K.f16x3_pack_weights_t(P['out_w'][L - 1], ws['wgb_top'], S, R, S, S + R, 0, plan.WS, scale_dev=sc('WO'), mode=md)       # the top layer has no dnet
+            if not plan.head_x3:      # (the input gradient of postprocess1 wrote them otherwise)
+                K.f16x3_split_activations(dskip, ws['gr'], B, S, T, scale=plan.GS, kc0=0, KC=(S + R) // 8, scale_dev=sc('G'),
                                           amax=am('G'), flag=flag, mode=md)   # one tensor for all layers
-        if calib:
+        if plan.calib:
             K.f16x3_amax(dskip, am('G'))
-        if wg_x3 and not head_x3:      # the weight-gradient kernels add the per-frame sums of dpre into the condition gradient
+        if plan.wg_x3 and not plan.head_x3:      # the weight-gradient kernels add the per-frame sums of dpre into the condition gradient
             dce[:, :L * 2 * R].zero_()
-        # Batched weight gradients (the engine's default): dpre and dnet of EVERY layer are kept (4.9 GB at B = 8 instead of
-        # rings of 2 / 3 buffers) and the weight gradients of several layers go out as ONE launch (vqw_f16x3_wgrad_batch):
-        #   * the skip halves of all layers' 1x1 kernels, dW_s[l] = gated[l] (x) dskip -- dskip is the same tensor for every
-        #     layer -- at once, before the layer loop: 60 tiles x 4 K splits instead of 30 x (2 tiles x 80 splits);
-        #   * the gate kernels of up to 6 layers (VQW_WG_GATE_BATCH) (layers whose tap shifts are all multiples of 4 and the others --
-        #     dilations 1 and 2 -- in separate batches: the latter need the kernel's slower unaligned-window variant);
-        #   * the residual halves, dW_r[l] = gated[l] (x) dnet[l+1], of up to 29 layers (VQW_WG_RES_BATCH).
-        # A launch writes tiles x splits <= CUs partial 256x256 tiles to the slab whatever its batch size: per layer the slab
-        # traffic (2 x 61 MB per single launch, 7.3 GB per step) falls with the batch size, dskip is read once per XCD instead
-        # of once per layer, and 68 reductions become ~10.
-        # ... and (qp) dpre is kept as the operand PLANES gate backward writes for the input gradient anyway: the gate kernels' weight
-        # gradient reads its q operand from them (transposed LDS reads, vqw_f16x3_wgrad q_planes) and gate backward no longer
-        # writes fp32 dpre at all (109 of its 312 MB per layer); (pp) p = the layer's input planes and the gated planes likewise
-        gated_p = (lambda i: dict(p_planes=ws['gp'], p_planes_kc0=i * (R // 8), p_planes_KC=L * (R // 8))) if pp else \
-            (lambda i: dict(p=ws['gated'][i]))
-        if batched and 'dnet_all' not in ws:
-            ws['dnet_all'] = [A.empty(B, R, T, device=self.dev) for _ in range(L)]       # dnet_all[l] = d loss / d net[l]
-            ws['_poison'] += ws['dnet_all']
-        if batched and ('dp_all' if qp else 'dpre_all') not in ws:
-            if qp:
-                ws['dp_all'] = [A.empty(2 * B * 2 * R * T, dtype=torch.float16, device=self.dev) for _ in range(L)]
-            else:
-                ws['dpre_all'] = [A.empty(B, 2 * R, T, device=self.dev) for _ in range(L)]
-            ws['_poison'] += ws['dp_all' if qp else 'dpre_all']
-        pend_gate, pend_res = {False: [], True: []}, []
-
-        def on_side(launch):           # weight gradients: nothing downstream waits for them
-            with side_after(side, side_mark(main, side)):
-                launch()
-
-        def flush_gate(odd):
-            layers, pend_gate[odd] = pend_gate[odd], []
-            if layers:
-                probs = [dict(dw=G['gated_w'][i], taps=causal_taps(ks, self.dil[i]),
-                              p_scale=sc('X', i), q0_scale=sc('DP', i), q_seg=dce.view(-1)[i * 2 * R * Tz:],
-                              **(dict(p_planes=ws['xp_all'][i]) if pp else dict(p=net[i])),
-                              **(dict(q_planes=ws['dp_all'][i], q_planes_scale=GS) if qp else dict(q0=ws['dpre_all'][i]))) for i in layers]
-                on_side(lambda: K.f16x3_wgrad_batch(probs, slab=ws['wslab'], B=B, T=T, Cp=R, Q0=2 * R, seg_T=Tz, seg_bstride=cbs, mode=md))
-
-        def flush_res():
-            nonlocal pend_res
-            layers, pend_res = pend_res, []
-            if layers:         # (the top layer has no dnet: its residual kernel gets no gradient)
-                probs = [dict(q0=ws['dnet_all'][i + 1], dw=G['out_w'][i].view(-1)[S:], q_total=G['out_b'][i][S:], **gated_p(i))
-                         for i in layers]
-                on_side(lambda: K.f16x3_wgrad_batch(probs, slab=ws['wslab'], B=B, T=T, Cp=R, Q0=R, lddw=S + R, taps=[0],
-                                                    q0_scale=sc('G'), total_cols=(0, R), mode=md))
-
-        if batched:      # the skip halves of all layers (dskip: the first S / 8 chunks of the gradient planes)
-            qsk = dict(q_planes=ws['gr'], q_planes_KC=(S + R) // 8, q_planes_scale=GS) if (qp and gbwd_x3) else dict(q0=dskip)
-            for i0 in range(0, L, K.WGRAD_MAX_BATCH):
-                probs = [dict(dw=G['out_w'][i].view(-1), **gated_p(i)) for i in range(i0, min(L, i0 + K.WGRAD_MAX_BATCH))]
-                on_side(lambda: K.f16x3_wgrad_batch(probs, slab=ws['wslab'], B=B, T=T, Cp=R, Q0=S, lddw=S + R, taps=[0],
-                                                    q0_scale=sc('G'), mode=md, **qsk))
-        side_done = {}
-        dnet = dnet_ring[(L - 1) % 3]
+        wgrads = (_BatchedWgrads if plan.batched else _PerLayerWgrads)(self, ws, dskip, main, side)
+        dnet = None                  # the top layer has none: net[L] is unused by the graph, its gradient is zero
         for l in range(L - 1, -1, -1):
-            d = self.dil[l]
-            top = (l == L - 1)       # net[L] is unused by the graph: its gradient is zero
-            dpre = (None if qp else ws['dpre_all'][l]) if batched else dpre_ring[l % 2]
-            dplanes = ws['dp_all'][l] if qp else ws.get('dp')
-            dnet_next = ws['dnet_all'][l] if batched else dnet_ring[(l - 1) % 3]
-            if not batched and side is not main and (l + 2) in side_done:
-                main.wait_event(side_done[l + 2])            # dpre[l % 2] and dnet[(l - 1) % 3] are free again
-            if gbwd_x3:
-                K.f16x3_out_conv(epi=1, xp=ws['gr'], Cin=S if top else S + R, xp_KC=(S + R) // 8,
-                                 wp=ws['wgb_top'] if top else ws['wgb'][l], aux0=None if g_dropped else (ws['gated'][l] if th_dropped else ws['th'][l]),
-                                 aux0_planes=ws['gp'] if g_dropped else None, aux0_KC=L * (R // 8), aux0_kc0=l * (R // 8),
-                                 aux0_is_gated=th_dropped, aux1=ws['sg'][l], net_out=dpre,
-                                 net_out_planes=dplanes, plane_scale=GS, B=B, T=T, R=R, S=0, w_scale_inv=1.0 / (WS * GS),
-                                 x_scale=sc('G'), w_scale=sc('WO'), out_scale=sc('DP', l), out_amax=am('DP', l), flag=flag, mode=md)
-            else:
-                K.conv_gemm(x0=dskip, x1=None if top else dnet, w=self._tt('out_w')[l], out0=dpre, aux0=ws['th'][l],
-                            aux1=ws['sg'][l], B=B, T_in=T, T_out=T, M=R, C0=S, C1=0 if top else R, taps=[0],
-                            epilogue=K.EPI_GATE_BWD, tile=self.tiles['gate_bwd'])
-            if calib:
-                K.f16x3_amax(dpre, am('DP', l))
-            ready = side_mark(main, side)
-            taps_b = mirrored_taps(ks, d)
-            if dgrad_x3:
-                if not gbwd_x3:      # (gate backward hands dpre over as planes)
-                    K.f16x3_split_activations(dpre, ws['dp'], B, 2 * R, T, scale=GS, mode=md)
-                K.f16x3_out_conv(xp=dplanes, Cin=2 * R, ks=ks, dilation=d, direction=-1, wp=ws['wdg'][l],
-                                 net_in=None if top else dnet, net_out=dnet_next, B=B, T=T, R=R, S=0,
-                                 w_scale_inv=1.0 / (WS * GS),
-                                 net_out_planes=ws['gr'] if gbwd_x3 else None, planes_kc0=S // 8 if gbwd_x3 else 0,
-                                 planes_KC=(S + R) // 8 if gbwd_x3 else 0, plane_scale=GS if gbwd_x3 else 0.0,
-                                 x_scale=sc('DP', l), w_scale=sc('WG'), out_scale=sc('G'), out_amax=am('G'), flag=flag, mode=self.x3_mode_dgrad)
-            elif top:
-                K.conv_gemm(x0=dpre, w=self._tt('gated_w')[l], out0=dnet_next, B=B, T_in=T, T_out=T, M=R, C0=2 * R, taps=taps_b,
-                            tile=self.tiles['dgrad'])
-            else:
-                K.conv_gemm(x0=dpre, w=self._tt('gated_w')[l], out1=dnet_next, aux1=dnet, out0=dnet_next, B=B, T_in=T, T_out=T,
-                            M=R, M0=0, C0=2 * R, taps=taps_b, epilogue=K.EPI_ACCUM_SPLIT, tile=self.tiles['dgrad'])
-            if calib:
-                K.f16x3_amax(dnet_next, am('G'))
-            if batched:
-                odd = any(shift % 4 for shift in taps_b)
-                pend_gate[odd].append(l)
-                if len(pend_gate[odd]) >= plan.gate_batch:      # 6: 36 tiles x 7 K splits = 252 blocks (tools/wg_batch_sweep.sh)
-                    flush_gate(odd)
-                if not top:                  # layer l + 1 wrote dnet[l + 1] in the iteration before this one
-                    pend_res.append(l)
-                    if len(pend_res) >= plan.res_batch:
-                        flush_res()
-                dnet = dnet_next
-                continue
-            with side_after(side, ready):
-                if wg_x3:    # weight gradients on the fp16 pipe too: operands split in registers with the planes' guard scales;
-                    # the bias sums and the condition gradient (sums of dpre per condition frame) come out of the same kernels
-                    K.f16x3_wgrad(p=ws['gated'][l], q0=dskip, q1=None if top else dnet, dw=G['out_w'][l], slab=ws['wslab'], B=B,
-                                  T=T, Cp=R, Q0=S, Q1=0 if top else R, lddw=S + R, taps=[0], q0_scale=sc('G'), q1_scale=sc('G'),
-                                  q_total=None if top else G['out_b'][l], total_cols=(S, S + R), mode=md)
-                    K.f16x3_wgrad(p=net[l], q0=dpre, dw=G['gated_w'][l], slab=ws['wslab'], B=B, T=T, Cp=R, Q0=2 * R,
-                                  taps=causal_taps(ks, d), p_scale=sc('X', l), q0_scale=sc('DP', l),
-                                  q_seg=dce.view(-1)[l * 2 * R * Tz:], seg_T=Tz, seg_bstride=cbs, mode=md)
-                else:
-                    K.wgrad_gemm(p=ws['gated'][l], q0=dskip, q1=None if top else dnet, dw=G['out_w'][l], B=B, T_q=T, T_p=T,
-                                 Cp=R, Q0=S, Q1=0 if top else R, lddw=S + R, taps=[0])
-                    if not top:
-                        K.rowsum(dnet, total=G['out_b'][l][S:])
-                    K.wgrad_gemm(p=net[l], q0=dpre, dw=G['gated_w'][l], B=B, T_q=T, T_p=T, Cp=R, Q0=2 * R, taps=causal_taps(ks, d))
-                    K.rowsum(dpre, seg_out=seg_l, total=G['gated_b'][l], seg=ratio)
-                    dce[:, l * 2 * R:(l + 1) * 2 * R].copy_(seg_l)
-                if side is not main:
-                    side_done[l] = torch.cuda.Event()
-                    side_done[l].record(side)
+            dpre, dplanes, dnet_next = wgrads.buffers(l)
+            self._gate_backward(ws, l, dskip, dnet, dpre, dplanes)
+            ready = side_mark(main, side)            # dpre of layer l is complete
+            self._gate_dgrad(ws, l, dpre, dplanes, dnet, dnet_next)
+            wgrads.layer(l, dnet, dpre, ready)
             dnet = dnet_next
-        if batched:
-            flush_gate(False)
-            flush_gate(True)
-            flush_res()
+        wgrads.finish()
         if side is not main:
             main.wait_stream(side)
-        if wg_x3:      # gated biases: the condition gradient summed over batch and frames, all layers in one launch
+        if plan.wg_x3:      # gated biases: the condition gradient summed over batch and frames, all layers in one launch
             tot = torch.zeros(self.Mall, device=self.dev)
             K.rowsum(dce, total=tot)
             G['gated_b'].view(-1).add_(tot[:L * 2 * R])
         return dnet
+
+    def _gate_backward(self, ws, l, dskip, dnet, dpre, dplanes):
+        """Layer l's link of the chain, first half: dpre = d loss / d (gate pre-activation) from dskip and dnet = d loss / d net[l + 1]
+        (None: the top layer), as fp32 (dpre) and / or operand planes (dplanes) -- on the plane engine or the fp32 engine."""
+        R, S, L, B, T = self.R, self.S, self.L, ws['B'], ws['T']
+        plan, md, top = ws['plan'], self.x3_mode_bwd, dnet is None
+        sc, am, flag = self._guards(plan)
+        if plan.gbwd_x3:
+            GS, WS, th_dropped, g_dropped = plan.GS, plan.WS, plan.drop_th, plan.drop_g
+            K.f16x3_out_conv(epi=1, xp=ws['gr'], Cin=S if top else S + R, xp_KC=(S + R) // 8,
+                             wp=ws['wgb_top'] if top else ws['wgb'][l], aux0=None if g_dropped else (ws['gated'][l] if th_dropped else ws['th'][l]),
+                             aux0_planes=ws['gp'] if g_dropped else None, aux0_KC=L * (R // 8), aux0_kc0=l * (R // 8),
+                             aux0_is_gated=th_dropped, aux1=ws['sg'][l], net_out=dpre,
+                             net_out_planes=dplanes, plane_scale=GS, B=B, T=T, R=R, S=0, w_scale_inv=1.0 / (WS * GS),
+                             x_scale=sc('G'), w_scale=sc('WO'), out_scale=sc('DP', l), out_amax=am('DP', l), flag=flag, mode=md)
+        else:
+            K.conv_gemm(x0=dskip, x1=dnet, w=self._tt('out_w')[l], out0=dpre, aux0=ws['th'][l],
+                        aux1=ws['sg'][l], B=B, T_in=T, T_out=T, M=R, C0=S, C1=0 if top else R, taps=[0],
+                        epilogue=K.EPI_GATE_BWD, tile=self.tiles['gate_bwd'])
+        if plan.calib:
+            K.f16x3_amax(dpre, am('DP', l))
+
+    def _gate_dgrad(self, ws, l, dpre, dplanes, dnet, dnet_next):
+        """... second half: dnet_next = d loss / d net[l] = the gate conv's input gradient of dpre, plus dnet (the residual
+        connection; None: the top layer) -- on the plane engine (guarded, or the ladder's fixed lift behind either gate backward)
+        or the fp32 engine."""
+        R, S, ks, d, B, T = self.R, self.S, self.ks, self.dil[l], ws['B'], ws['T']
+        plan, md = ws['plan'], self.x3_mode_bwd
+        sc, am, flag = self._guards(plan)
+        if plan.dgrad_x3:
+            gbwd_x3, GS = plan.gbwd_x3, plan.GS
+            if not gbwd_x3:      # (gate backward hands dpre over as planes)
+                K.f16x3_split_activations(dpre, ws['dp'], B, 2 * R, T, scale=GS, mode=md)
+            K.f16x3_out_conv(xp=dplanes, Cin=2 * R, ks=ks, dilation=d, direction=-1, wp=ws['wdg'][l],
+                             net_in=dnet, net_out=dnet_next, B=B, T=T, R=R, S=0,
+                             w_scale_inv=1.0 / (plan.WS * GS),
+                             net_out_planes=ws['gr'] if gbwd_x3 else None, planes_kc0=S // 8 if gbwd_x3 else 0,
+                             planes_KC=(S + R) // 8 if gbwd_x3 else 0, plane_scale=GS if gbwd_x3 else 0.0,
+                             x_scale=sc('DP', l), w_scale=sc('WG'), out_scale=sc('G'), out_amax=am('G'), flag=flag, mode=self.x3_mode_dgrad)
+        elif dnet is None:
+            K.conv_gemm(x0=dpre, w=self._tt('gated_w')[l], out0=dnet_next, B=B, T_in=T, T_out=T, M=R, C0=2 * R, taps=mirrored_taps(ks, d),
+                        tile=self.tiles['dgrad'])
+        else:
+            K.conv_gemm(x0=dpre, w=self._tt('gated_w')[l], out1=dnet_next, aux1=dnet, out0=dnet_next, B=B, T_in=T, T_out=T,
+                        M=R, M0=0, C0=2 * R, taps=mirrored_taps(ks, d), epilogue=K.EPI_ACCUM_SPLIT, tile=self.tiles['dgrad'])
+        if plan.calib:
+            K.f16x3_amax(dnet_next, am('G'))
 
     def _backward_tail(self, x, ws, dskip, dnet):
         """Skip start + preprocess (wavenet.py:42-55): dnet += W_skip0^T dskip, the skip start's gradients and the skip bias sums,
@@ -1159,7 +1212,7 @@ class WaveNet:
         dce, net = ws['dcondenc'], ws['net']
         plan, md = ws['plan'], self.x3_mode_bwd
         wg_x3, GS = plan.wg_x3, plan.GS
-        sc = self._slots(self.x3_scale, plan.gd)
+        sc = self._guards(plan)[0]
         if plan.head_x3 and plan.gbwd_x3:      # dnet += W_skip0^T dskip over dskip's planes (chunks 0..S/8 of the gradient planes)
             K.f16x3_out_conv(xp=ws['gr'], xp_KC=(S + R) // 8, Cin=S, wp=ws['wskip0t'], net_in=dnet, net_out=dnet, B=B, T=T, R=R, S=0,
                              w_scale_inv=1.0 / GS, x_scale=sc('G'), w_scale=sc('WH'), mode=md)
@@ -1178,11 +1231,9 @@ class WaveNet:
         self._backward_input(x, ws, dnet)
         # ---- local condition (wavenet_ops.py:93-101) -> d cond
         if self.cond_proj and Tz % 4 == 0 and P['cond_w'].data_ptr() % 16 == 0:
-            if 'cp_scratch' not in ws:
-                ws['cp_scratch'] = A.empty(K.cond_proj_dgrad_scratch(B, self.Cc, self.Mall, Tz), device=self.dev)
-                ws['_poison'].append(ws['cp_scratch'])
+            scratch = A.scratch(ws, 'cp_scratch', lambda: A.empty(K.cond_proj_dgrad_scratch(B, self.Cc, self.Mall, Tz), device=self.dev))
             K.cond_proj_wgrad(ws['cond'], dce, G['cond_w'], B=B, Cc=self.Cc, Mall=self.Mall, Tz=Tz)
-            K.cond_proj_dgrad(P['cond_w'], dce, ws['dcond'], ws['cp_scratch'], B=B, Cc=self.Cc, Mall=self.Mall, Tz=Tz)
+            K.cond_proj_dgrad(P['cond_w'], dce, ws['dcond'], scratch, B=B, Cc=self.Cc, Mall=self.Mall, Tz=Tz)
         else:
             K.wgrad_gemm(p=ws['cond'], q0=dce, dw=G['cond_w'], B=B, T_q=Tz, T_p=Tz, Cp=self.Cc, Q0=self.Mall, taps=[0])
             K.conv_gemm(x0=dce, w=self._tt('cond_w'), out0=ws['dcond'], B=B, T_in=Tz, T_out=Tz, M=self.Cc, C0=self.Mall, taps=[0])
@@ -1413,7 +1464,7 @@ class WaveNet:
             self.x3_fallbacks += 1
 
             def measure(ws):                     # what the layer-input planes would have held (net[L] feeds nothing)
-                am = self._slots(self.x3_amax, True)
+                am = self._guards(ws['plan'])[1]
                 for l in range(1, self.L):
                     K.f16x3_amax(ws['net'][l], am('X', l))
                 K.f16x3_amax(ws['skip'], am('SK'))
