@@ -843,10 +843,24 @@ int vqw_f16x3_strided_conv(const vqw_f16x3_sconv_desc* d, vqw_stream_t s);
  *   dw[j][c][o] += sum_{b,t} p[b][c][t + tap_shift[j]] * q[b][o][t],   q = [q0 (Q0 rows); q1 (Q1 rows)] along o,
  * p [B][Cp][T], q0 [B][Q0][T], q1 [B][Q1][T] fp32 (time contiguous = the contraction index: the operands are split into
  * fp16 planes inside the kernel, with the power-of-two guard scales *_scale (device scalars or NULL) of the same tensors'
- * planes, whose producers range-check them).  T % 32 == 0; Cp, Q0, Q1 multiples of 256; tap_shift <= 0 (reads outside
- * [0, T) are zero).  `slab` is scratch: tiles * nsplit * 65536 floats (tiles = ntaps * Cp/256 * (Q0+Q1)/256; nsplit 0 =
- * CUs / tiles): partial tiles are summed in a fixed order by a second launch -- dw is bitwise reproducible (q_total /
- * q_seg are met by fp32 atomics).                                                                                  */
+ * planes, whose producers range-check them).  Cp, Q0, Q1 multiples of 256, 1 .. VQW_MAX_TAPS taps; reads outside [0, T) of
+ * the batch row are zero.  Either operand may come as planes instead (q_planes, p_planes below).
+ *   T:      a multiple of 32 with an fp32 operand, and with q_seg in every form; any T > 0 with both operands as planes and no
+ *           q_seg (the steps behind the row's end add zeros); a multiple of 4 with p_stride 2.
+ *   shifts: tap_shift <= 0 with fp32 p at p_stride 1; either sign with p_planes or p_stride 2 (|shift| < 2^24).  A tap that lies
+ *           in the padding throughout adds exact zeros.
+ *   K split: the B * ceil(T / 32) pairs of 16-step stages are cut into nsplit contiguous, even ranges per tile; nsplit 0 = CUs /
+ *           tiles (one round of blocks), and either value is clamped to [1, B * ceil(T / 32)]; tiles = n * ntaps * Cp/256 *
+ *           (Q0+Q1)/256 over the n problems of a launch.
+ *   slab:   scratch of at least tiles * nsplit * 65536 floats (the clamped nsplit), else the launch is refused; exactly that many
+ *           floats are written, every one of them, and nothing behind them.  The partial tiles are summed in a fixed order by a
+ *           second launch and added onto dw -- dw is bitwise reproducible.
+ *   sums:   q_total and q_seg are formed only by the blocks of tap 0 and the first row tile (each sum arrives once, whatever
+ *           ntaps and Cp), from the q those blocks hold anyway, and met by fp32 atomics: exact sums are exact, others
+ *           depend on the order of arrival.
+ * A descriptor that breaks a rule (these, lddw % 4 == 0 and >= Q0 + Q1, dw 16-byte aligned, mode within its two bits, the chunk
+ * ranges of the planes, (T / seg_T) % 32 == 0 and seg_bstride >= (Q0 + Q1) * seg_T) is refused before anything is launched: the
+ * call returns non-zero, vqw_last_error names the rule, and no output is touched.                                          */
 typedef struct vqw_f16x3_wgrad_desc {
     const float* p;
     const float* q0;

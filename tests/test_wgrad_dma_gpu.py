@@ -6,6 +6,7 @@ the plane entries reach LDS.  Every dW of tests/wgrad_dma_cases.py is therefore
   * inside 2e-6 max |dW| of the float64 sum over the plane values (tests/x3_ref.py) where it is not (T = 40, 72) and for the
     bf16 plane (rounded operands),
   * the same from one run to the next.
+On top of that every unstrided dW, and the sums, are held elementwise to the plane-exact reference and bars of tests/x3_wgrad_ref.py.
 A differing digest means a stage reached the MFMAs with other bytes: a step behind the row's end or before the batch row that
 did not read zero, a stage read before it had landed, a ring slot refilled too early, a request past the block's K range that
 was read after all.  q_total / q_seg are sums by atomics: held at the bounds of test_wgrad_f16x3_matches_fp64."""
@@ -20,6 +21,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import wgrad_dma_cases as W  # noqa: E402
 import x3_ref as X  # noqa: E402
+import x3_wgrad_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'wgrad_dma_digests.json')
@@ -91,6 +93,21 @@ def test_planes_both_matches_the_parent_and_the_register_path(K, want, name, kw)
             err, top = float((got[k].double() - w64).abs().max()), float(w64.abs().max())
             print('%s %s: max err %.3e, bar %.3e' % (name, k, err, 2e-6 * top))
             assert err <= 2e-6 * top, '%s: %s is %.3e from float64 of the plane values (bar %.3e)' % (name, k, err, 2e-6 * top)
+    if not kw.get('strided', False):
+        block = kw.get('dw_form') == 'block'
+        for i, k in enumerate(dws):
+            p, q = W.operands(kw['B'], kw['T'], kw['Q0'], kw.get('seed', 0) + i)
+            _, _, sp, sq = W.problem_scales(i)
+            ns = min(kw['nsplit'], R.pairs(kw['B'], kw['T'])[1])
+            w64, t64, _, bar, bar_t, _, _ = R.wgrad(p, q, None, kw['taps'][i], sp, sq, mode=kw.get('mode', 0), p_planes=True, q_planes=True, nsplit=ns,
+                                                    total=block, total_cols=(64, kw['Q0'] - 32) if block else None, full=True)
+            dev = got[k].cpu().numpy().astype(np.float64)
+            dev = dev[None, :, 512:] if block else dev
+            over = np.abs(dev - w64) > bar
+            assert not over.any(), '%s: %d elements of %s outside the elementwise bars of x3_wgrad_ref (worst %.3f of its bar)' % (
+                name, int(over.sum()), k, float((np.abs(dev - w64) / bar).max()))
+            if block:
+                assert not (np.abs(got['tot%d' % i].cpu().numpy().astype(np.float64) - t64) > bar_t).any(), '%s: bias sums outside the bars of x3_wgrad_ref' % name
     if kw.get('dw_form') == 'block':
         lo, hi = 64, kw['Q0'] - 32
         for i, k in enumerate(dws):
@@ -127,3 +144,10 @@ def test_q_sums_from_the_fragments(K, mode):
         err = float((segs[i][:, :Q0].double() - q.reshape(B, Q0, Tz, T // Tz).sum(-1)).abs().max())
         assert err <= 1e-5 * float(q.abs().max()) * 32 * (T // Tz // 32), 'problem %d: segment sums off by %.3e' % (i, err)
         assert float(segs[i][:, Q0:].abs().max()) == 0.0, 'the slack between the batch rows was written'
+        # and elementwise against the reference: (terms + 3) u sum |q| per sum, of what the planes hold
+        p, q32 = W.operands(B, T, Q0, 50 + i)
+        _, _, sp, sq = W.problem_scales(i)
+        _, t64, s64, _, bar_t, bar_s, _ = R.wgrad(p, q32, None, probs[i]['taps'], sp, sq, mode=mode, p_planes=True, q_planes=True, nsplit=5, total=True, seg_T=Tz,
+                                                  csel=np.arange(8), full=True)
+        assert not (np.abs(tots[i].cpu().numpy().astype(np.float64) - t64) > bar_t).any(), 'problem %d: column totals outside the bars of x3_wgrad_ref' % i
+        assert not (np.abs(segs[i][:, :Q0].cpu().numpy().astype(np.float64) - s64) > bar_s).any(), 'problem %d: segment sums outside the bars of x3_wgrad_ref' % i
