@@ -18,7 +18,7 @@ generator, and written as `<dir>/<step>_<speaker>_prior.wav` (N x 64 samples) pl
 generators (generator.WidePriorGenerator for the codes, generator.WideGenerator for the audio), `-rows` (1..1024, default 256)
 rows per batch; writes `<dir>/<step>_<speaker>_prior_<m>.wav` and `prior_codes_<step>_<speaker>_<m>.npy`.  With `-seed` row i
 draws its code uniforms from child 0 of the seed sequence (seed, i) and its audio uniforms from child 1, so a row's codes and
-audio do not depend on `-rows`.  Not with `-prompt_frames` (the wide generators have no prefill).
+audio do not depend on `-rows`.  Not with `-prompt_frames` (many continuations of one prompt: `-takes`).
 
 `-temperature / -top_k / -top_p` temper and truncate the audio sampling, `-prior_temperature / -prior_top_k / -prior_top_p`
 the code sampling of `-prior` (mode sample only; the same values for every speaker; the defaults are plain sampling).
@@ -29,6 +29,14 @@ speaker; the wav holds them verbatim, then `length - N` generated samples.  `-pr
 prefills the prior with the utterance's first N codes (encode_codes), samples `-frames` more, and decodes all N + frames codes
 with the audio generator prefilled with the utterance's first N x 64 samples (which the wav holds verbatim); the codes file
 holds all N + frames codes.  With `-seed`, uniforms are drawn for the generated samples / codes only.
+
+`-takes M` (M > 1) with a prompt: M sampled continuations of the one prompt per speaker, on the wide generators prefilled from
+the prompt (WideGenerator.prefill_prompt / WidePriorGenerator.prefill_codes); every (speaker k, take m) pair is one row i = k M + m, `-rows`
+(1..1024, default 256) rows per batch.  With `-audio A -prompt_samples N` it writes `<dir>/<step>_<speaker>_take_<m>.wav` (the
+prompt verbatim, then `length - N` generated samples); with `-prior P -audio A -prompt_frames N`,
+`<dir>/<step>_<speaker>_prior_take_<m>.wav` and `prior_codes_<step>_<speaker>_take_<m>.npy` (`-frames` more codes per row).  With
+`-seed` row i draws its code uniforms from row_uniforms' stage 0 and its audio uniforms from stage 1, so a take does not depend on
+`-rows`.  Mode sample only (greedy takes would all be equal); not with `-audio_list`, `-count` above 1 or `-teacher_forced`.
 
 `-audio_list FILE` (one wav path per line; `-data_root` for relative paths) converts every utterance of the list to every
 speaker with the wide generator (generator.WideGenerator): every (utterance, speaker) pair is one row, `-rows` (1..1024, default
@@ -86,9 +94,25 @@ def main():
                         'with -prior -count M: (speaker, take) rows per batch')
     parser.add_argument('-count', default=1, type=int, help='with -prior: takes per speaker; above 1 both stages run on the wide '
                         'generators (<step>_<speaker>_prior_<m>.wav, prior_codes_<step>_<speaker>_<m>.npy)')
+    parser.add_argument('-takes', default=1, type=int, help='with a prompt (-prompt_samples / -prompt_frames): sampled continuations '
+                        'per speaker; above 1 they run on the wide generators (<step>_<speaker>_take_<m>.wav)')
     parser.add_argument('-data_root', default='', help='with -audio_list: directory the list\'s relative paths start from')
     parser.add_argument('-out_dir', default=None, help='with -audio_list: where the wavs go (default: beside the weights)')
     args = parser.parse_args()
+    if args.takes < 1:
+        parser.error('-takes %d must be >= 1' % args.takes)
+    if args.takes > 1:
+        for flag, on in (('-audio_list', args.audio_list is not None), ('-count above 1', args.count > 1),
+                         ('-teacher_forced', args.teacher_forced)):
+            if on:
+                parser.error('-takes %d continues one prompt several times: not with %s' % (args.takes, flag))
+        if not args.prompt_samples and not args.prompt_frames:
+            parser.error('-takes %d needs a prompt (-prompt_samples, or -prompt_frames with -prior); without one, -audio_list '
+                         'converts many utterances and -prior -count samples many takes' % args.takes)
+        if args.mode == 'greedy':
+            parser.error('-takes %d with -mode greedy: all takes of a prompt would be equal' % args.takes)
+        if not 1 <= args.rows <= 1024:
+            parser.error('-rows %d must be in 1..1024' % args.rows)
     if args.audio_list is not None:
         return convert_list(args, parser)
     if args.count < 1:
@@ -134,6 +158,8 @@ def main():
         return generate_from_prior(args, pkg, gs, rank, world, dev, parser)
     if args.teacher_forced:
         return teacher_forced(args, pkg, gs, rank, world, dev, parser)
+    if args.takes > 1:
+        return prompted_takes(args, pkg, gs, rank, world, dev, parser)
     wav = read_wav(args.audio_path)
     length = len(wav)
     n_prompt = args.prompt_samples
@@ -179,6 +205,51 @@ def main():
             s = 'no_speaker' if args.speakers[i] == 'None' else args.speakers[i]
             wavfile.write(save_path + '/%d_%s.wav' % (gs, s), 16000, out[j])
             print('wrote', save_path + '/%d_%s.wav' % (gs, s))
+
+
+def prompted_takes(args, pkg, gs, rank, world, dev, parser):
+    """-audio -prompt_samples N -takes M: every (speaker k, take m) pair is row i = k M + m of the wide generator, cut into
+    consecutive batches of at most -rows.  Each batch is prefilled from the utterance's first N samples (WideGenerator.prefill_prompt)
+    and generates length - N more; with -seed row i draws from row_uniforms' stage 1 (the audio stage), so with the
+    generator's batch independence a take depends neither on -rows nor on the sharding."""
+    from scipy.io import wavfile
+    wav = read_wav(args.audio_path)
+    length, n_prompt, M = len(wav), args.prompt_samples, args.takes
+    if n_prompt >= length:
+        parser.error('-prompt_samples %d is not shorter than the trimmed utterance (%d samples): nothing to generate'
+                     % (n_prompt, length))
+    num_speakers, ids = speaker_ids(args, pkg)
+    parameters, wavenet_parameters = pkg.model.load_configs(args.parameter_path)
+    model = load_vqvae(args, pkg, parameters, wavenet_parameters, num_speakers, dev)
+    save_path = args.restore_path.split('/weights')[0]
+    all_rows = [(k, m) for k in range(len(ids)) for m in range(M)]            # speaker order, then take
+    mine = list(range(rank, len(all_rows), world))                            # rows sharded over ranks: no collective
+    if not mine:
+        return
+    x = torch.from_numpy(wav).to(dev).unsqueeze(0).contiguous()
+    enc_all = model.encode(x, torch.tensor(ids, dtype=torch.int64, device=dev))      # one row per speaker
+    ratio = length // enc_all.shape[2]
+    n = length - n_prompt
+    gens = {}
+    for b0 in range(0, len(mine), args.rows):
+        batch = mine[b0:b0 + args.rows]
+        nb = len(batch)
+        enc = enc_all[[all_rows[i][0] for i in batch]].contiguous()
+        uniforms = torch.stack([row_uniforms(args.seed, i, n, stage=1) for i in batch]).to(dev)
+        if nb not in gens:
+            gens[nb] = pkg.generator.WideGenerator(model, batch=nb)
+        gens[nb].prefill_prompt(x[:, :n_prompt].expand(nb, n_prompt).contiguous(), enc, ratio=ratio)
+        audio, _ = gens[nb].generate(enc, n, mode=args.mode, ratio=ratio, uniforms=uniforms, temperature=args.temperature,
+                                     top_k=args.top_k, top_p=args.top_p)
+        audio = audio.cpu().numpy()
+        for j, i in enumerate(batch):
+            k, m = all_rows[i]
+            s = 'no_speaker' if args.speakers[k] == 'None' else args.speakers[k]
+            name = save_path + '/%d_%s_take_%d.wav' % (gs, s, m)
+            wavfile.write(name, 16000, np.concatenate([wav[:n_prompt], audio[j]]))
+            print('wrote', name)
+    for gen in gens.values():
+        gen.close()
 
 
 def read_list(path, data_root):
@@ -410,6 +481,8 @@ def generate_from_prior(args, pkg, gs, rank, world, dev, parser):
     save_path = args.restore_path.split('/weights')[0]
     if args.count > 1:
         return prior_corpus(args, pkg, gs, rank, world, dev, ids, model, prior, save_path)
+    if args.takes > 1:
+        return prior_takes(args, pkg, gs, rank, world, dev, ids, model, prior, save_path, wav)
     mine = list(range(rank, len(ids), world))
     n, length = args.frames, args.frames * 64
     g = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
@@ -486,6 +559,50 @@ def prior_corpus(args, pkg, gs, rank, world, dev, ids, model, prior, save_path):
             wavfile.write(save_path + '/%d_%s_prior_%d.wav' % (gs, s, m), 16000, audio[j])
             np.save(save_path + '/prior_codes_%d_%s_%d.npy' % (gs, s, m), codes[j])
             print('wrote', save_path + '/%d_%s_prior_%d.wav' % (gs, s, m))
+    for gen in list(pgens.values()) + list(gens.values()):
+        gen.close()
+
+
+def prior_takes(args, pkg, gs, rank, world, dev, ids, model, prior, save_path, wav):
+    """-prior -audio -prompt_frames N -takes M: every (speaker k, take m) pair is row i = k M + m of both wide generators, in
+    batches of at most -rows.  WidePriorGenerator is prefilled with the utterance's first N codes and draws -frames more
+    (row_uniforms' stage 0); WideGenerator is prefilled with the first N x 64 samples and decodes the new codes (stage 1)."""
+    from scipy.io import wavfile
+    M, n_prompt = args.takes, args.prompt_frames
+    n, length = args.frames, args.frames * 64
+    all_rows = [(k, m) for k in range(len(ids)) for m in range(M)]            # speaker order, then take
+    mine = list(range(rank, len(all_rows), world))                            # rows sharded over ranks: no collective
+    if not mine:
+        return
+    x = torch.from_numpy(wav).to(dev).unsqueeze(0).contiguous()
+    prompt_codes = model.encode_codes(x, torch.tensor([ids[0]], dtype=torch.int64, device=dev))[:, :n_prompt]
+    prompt_audio = x[:, :n_prompt * 64]
+    pgens, gens = {}, {}
+    for b0 in range(0, len(mine), args.rows):
+        batch = mine[b0:b0 + args.rows]
+        nb = len(batch)
+        spk = torch.tensor([ids[all_rows[i][0]] for i in batch], dtype=torch.int64, device=dev)
+        u_codes = torch.stack([row_uniforms(args.seed, i, n, stage=0) for i in batch]).to(dev)
+        u_audio = torch.stack([row_uniforms(args.seed, i, length, stage=1) for i in batch]).to(dev)
+        if nb not in gens:
+            pgens[nb] = pkg.generator.WidePriorGenerator(prior, batch=nb)
+            gens[nb] = pkg.generator.WideGenerator(model, batch=nb)
+        pgens[nb].prefill_codes(prompt_codes.expand(nb, n_prompt).contiguous(), spk)
+        codes = pgens[nb].sample(n, spk, mode=args.mode, uniforms=u_codes, temperature=args.prior_temperature,
+                                 top_k=args.prior_top_k, top_p=args.prior_top_p)
+        codes = torch.cat([prompt_codes.expand(nb, n_prompt), codes], dim=1).contiguous()
+        cond = model.condition_from_codes(codes, spk)
+        gens[nb].prefill_prompt(prompt_audio.expand(nb, n_prompt * 64).contiguous(), cond, ratio=64)
+        audio, _ = gens[nb].generate(cond, length, mode=args.mode, ratio=64, uniforms=u_audio, temperature=args.temperature,
+                                     top_k=args.top_k, top_p=args.top_p)
+        audio = torch.cat([prompt_audio.expand(nb, n_prompt * 64), audio], dim=1).cpu().numpy()
+        codes = codes.cpu().numpy()
+        for j, i in enumerate(batch):
+            k, m = all_rows[i]
+            s = 'no_speaker' if args.speakers[k] == 'None' else args.speakers[k]
+            wavfile.write(save_path + '/%d_%s_prior_take_%d.wav' % (gs, s, m), 16000, audio[j])
+            np.save(save_path + '/prior_codes_%d_%s_take_%d.npy' % (gs, s, m), codes[j])
+            print('wrote', save_path + '/%d_%s_prior_take_%d.wav' % (gs, s, m))
     for gen in list(pgens.values()) + list(gens.values()):
         gen.close()
 

@@ -598,7 +598,7 @@ int vqw_ar_prior_create(vqw_ar_decoder** out, const vqw_ar_weights* w, int batch
  * behind the work already in `s`, _wait blocks the host until the run is done.  A row's indices, audio and probs_last do
  * not depend on the batch: not on `batch`, not on the row's position, not on the other rows' inputs or settings; a run cut
  * into several equals the single run bit for bit.  The condition is projected for a window of 4 frames at a time
- * (4 * (2 R n_layers + S) * batch floats), refreshed in stream order.  There is no prefill.
+ * (4 * (2 R n_layers + S) * batch floats), refreshed in stream order.
  * Shapes: R, S, Q multiples of 32, Q <= 1024; Cc a multiple of 16; 1 <= pre_k <= 64; 2 <= kernel_size <= VQW_MAX_TAPS;
  * 1 <= batch <= 1024; anything else is an error that names the value. */
 typedef struct vqw_ar_wide vqw_ar_wide;
@@ -611,6 +611,28 @@ int vqw_ar_wide_wait(vqw_ar_wide* h);
 int vqw_ar_wide_destroy(vqw_ar_wide* h);
 /* The mu-law level of an audio wide handle (256 after vqw_ar_wide_create): the rules of vqw_ar_decode_set_levels. */
 int vqw_ar_wide_set_levels(vqw_ar_wide* h, int levels);
+/* Prefill of a wide handle, with the contract of vqw_ar_decode_prefill_*: afterwards the handle is in the state of
+ * vqw_ar_wide_reset plus t_end steps teacher-forced on a prompt; the next vqw_ar_wide_run_async continues at step t_end
+ * (sample i of it uses frame (t_end + i) / ratio, and the run projects its own first condition window from that frame, as
+ * every run does).  Sequence: vqw_ar_wide_reset, then _layer for every layer and every chunk of rows, in any order, then
+ * _finish once, all on one stream, ordered as reset orders its work.  Each call first waits for a pending run, as reset does.
+ * _layer: x [nrows][R][ld] (device) holds layer l's input (the residual stream entering layer l) for rows row0 .. row0+nrows-1
+ *   of the handle at steps t_first .. t_first + ld - 1; the columns must cover [max(0, t_end - (kernel_size-1) d_l), t_end).
+ *   Step tau goes to ring slot tau % ((kernel_size-1) d_l) at [slot][r][row0 + i], where the layer's output kernel would have
+ *   pushed it, bit for bit; slots of steps before 0 stay as reset left them.  The rows of a batch may come in chunks (a
+ *   teacher-forced pass over hundreds of rows at once would need gigabytes): a row's state does not depend on the chunking.
+ * _finish: the input history, the last value, the device step counter and its host mirror, as the stepping kernels leave
+ *   them after step t_end - 1 (the input that step 0 stores included; the history slot of step t_end - pre_k, which step t_end
+ *   overwrites before any tap reads it, keeps reset's zero).  Tails [batch][pre_k] for ALL rows with the meaning of
+ *   vqw_ar_decode_prefill_finish: audio_tail = a[t_end-pre_k .. t_end) on an audio handle (encoded at the handle's mu-law
+ *   level, vqw_ar_wide_set_levels), code_tail = c[t_end-pre_k .. t_end) in [0, n_codes) on a code handle (stored as code + 1,
+ *   0 = none); entries before step 0 are ignored; exactly one is non-NULL and it must match the handle's mode.  t_end = 0
+ *   leaves the handle as reset left it.
+ * Refused before any device call, naming the value: a bad l, t_end < 0, t_first < 0, a window that does not cover the steps,
+ * nrows < 1 or rows outside the handle, the wrong tail, both tails or none. */
+int vqw_ar_wide_prefill_layer(vqw_ar_wide* h, int l, const float* x, int ld, int t_first, int t_end, int row0, int nrows,
+                              vqw_stream_t s);
+int vqw_ar_wide_prefill_finish(vqw_ar_wide* h, int t_end, const float* audio_tail, const int32_t* code_tail, vqw_stream_t s);
 /* Code-input mode of the wide generator (the latent prior over VQ codes, prior.py): the same step with a discrete input, for
  * sampling many code rows at once.  w->Q is the number of codes n_codes (a multiple of 32 in 32..1024, equal to `n_codes`) and
  * w->pre_w is read as [pre_k][n_codes][R] (prior/preprocess/kernel).  The handle reads the caller's weights IN PLACE, W_pre

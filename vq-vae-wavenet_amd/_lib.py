@@ -188,6 +188,8 @@ SIGNATURES = {
     'vqw_ar_wide_reset': (_i, [_fp, _fp]),
     'vqw_ar_wide_set_levels': (_i, [_fp, _i]),
     'vqw_ar_wide_run_async': (_i, [_fp, _fp, _i, _i, _i, _i, _fp, C.POINTER(ArSampling), _fp, _fp, _fp, _fp]),
+    'vqw_ar_wide_prefill_layer': (_i, [_fp, _i, _fp, _i, _i, _i, _i, _i, _fp]),
+    'vqw_ar_wide_prefill_finish': (_i, [_fp, _i, _fp, _fp, _fp]),
     'vqw_ar_wide_wait': (_i, [_fp]),
     'vqw_ar_wide_destroy': (_i, [_fp]),
     'vqw_prior_input_fwd': (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp]),

@@ -344,6 +344,57 @@ __global__ __launch_bounds__(256) void arw_sample_kernel(WideState* st, const fl
     }
 }
 
+// Prefill (vqw_ar_wide_prefill_layer): layer inputs of a prompt into the layer's ring.  The source x [nrows][R][ld] is
+// contiguous along time, the ring [depth][R][B] along the batch row, with R between them in both: a tile of 32 rows x 32 steps
+// of ONE channel is transposed through LDS.  grid (step tiles, row tiles, R).  Loads run with the lanes along time (a half
+// wave reads 128 contiguous bytes of one row), stores with the lanes along the batch row (a half wave writes 128 contiguous
+// bytes of one slot once the chunk has 32 rows).  Rows of 33 floats, as in arw_pre_code_kernel: a half of the load phase
+// writes one LDS row (32 consecutive banks), a half of the store phase reads one column (bank (row + step) mod 32, every bank
+// once).  A partial tile neither loads nor stores past its rows or steps (arw_tile_extent).  A copy: no arithmetic touches
+// a value.  Step t_lo + s goes to slot arw_ring_slot: where MODE_OUT pushes the layer's input of that step.
+__global__ __launch_bounds__(256) void arw_prefill_scatter_kernel(float* ring, int depth, int R, int B, const float* __restrict__ x,
+                                                                  int ld, int t_first, int t_lo, int nt, int row0, int nrows) {
+    constexpr int PT = AR_WIDE_PREFILL_TILE;
+    __shared__ float tile[PT][PT + 1];      // [row][step]
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int r = blockIdx.z;
+    const int s0 = blockIdx.x * PT, i0 = blockIdx.y * PT;
+    const int ns = arw_tile_extent(nt, blockIdx.x), ni = arw_tile_extent(nrows, blockIdx.y);
+    if (tx < ns) {
+        const float* src = x + ((size_t)i0 * R + r) * ld + (t_lo - t_first) + s0 + tx;
+        for (int i = ty; i < ni; i += 8) tile[i][tx] = src[(size_t)i * R * ld];
+    }
+    __syncthreads();
+    if (tx < ni) {
+        for (int s = ty; s < ns; s += 8) {
+            const int slot = arw_ring_slot(t_lo + s0 + s, depth);
+            ring[((size_t)slot * R + r) * B + row0 + i0 + tx] = tile[tx][s];
+        }
+    }
+}
+
+// Prefill (vqw_ar_wide_prefill_finish): what the input kernels and the sampling kernel leave after step t_end - 1.  xhist slot
+// tau % pre_k holds the input of step tau for tau in (t_end - pre_k, t_end), tau >= 0: for tau >= 1 the value of the prompt at
+// tau - 1 = tail[b][tau - 1 - (t_end - pre_k)] (mu-law encoded at the handle's level, or code + 1), for tau = 0 what step 0
+// stores from the reset's prev = 0 (mu_law_encode(0), or 0 = no code).  The slot of step t_end - pre_k (whose value, for
+// t_end > pre_k, lies before the tail) is the one step t_end overwrites before any tap reads it: it keeps the reset's zero.
+// prev is the prompt's last value, step the counter.  One thread per (slot, row), the row innermost.
+__global__ __launch_bounds__(256) void arw_prefill_finish_kernel(WideState* st, float* prev, float* xhist, int B, int pre_k, int t_end,
+                                                                 const float* audio_tail, const int* code_tail, const VqwMu mu) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) st->step = t_end;
+    if (i >= B * pre_k) return;
+    const int j = i / B, b = i - j * B;                  // tail column j is the prompt's value at t_end - pre_k + j
+    const size_t at = (size_t)b * pre_k + j;
+    const int tau = t_end - pre_k + j + 1;               // the step whose input that value is
+    if (tau >= 1 && tau < t_end)
+        xhist[(size_t)(tau % pre_k) * B + b] = audio_tail ? vqw_mu_encode_m(audio_tail[at], mu) : (float)(code_tail[at] + 1);
+    if (j == pre_k - 1) {
+        prev[b] = audio_tail ? audio_tail[at] : (float)(code_tail[at] + 1);
+        if (t_end <= pre_k) xhist[b] = audio_tail ? vqw_mu_encode_m(0.0f, mu) : 0.0f;   // the input of step 0, slot 0
+    }
+}
+
 }  // namespace
 
 struct vqw_ar_wide : ArTables {
@@ -557,6 +608,57 @@ extern "C" int vqw_ar_wide_reset(vqw_ar_wide* h, vqw_stream_t s) {
     for (int l = 0; l < h->w.n_layers; ++l)
         HIPC(hipMemsetAsync(h->rings[l], 0, h->ring_floats(l, h->B) * sizeof(float), st));
     h->steps = 0;
+    return 0;
+}
+
+// Prefill: see include/vqwave.h.  Every check comes before any device call and names the value.
+extern "C" int vqw_ar_wide_prefill_layer(vqw_ar_wide* h, int l, const float* x, int ld, int t_first, int t_end, int row0, int nrows,
+                                         vqw_stream_t s) {
+    VQW_CHECK(h, "vqw_ar_wide_prefill_layer: null handle");
+    VQW_CHECK(l >= 0 && l < h->w.n_layers, "vqw_ar_wide_prefill_layer: layer %d outside 0..%d", l, h->w.n_layers - 1);
+    VQW_CHECK(t_end >= 0, "vqw_ar_wide_prefill_layer: t_end=%d < 0", t_end);
+    VQW_CHECK(t_first >= 0, "vqw_ar_wide_prefill_layer: t_first=%d < 0", t_first);
+    VQW_CHECK(nrows >= 1, "vqw_ar_wide_prefill_layer: nrows=%d < 1", nrows);
+    VQW_CHECK(arw_rows_inside(row0, nrows, h->B), "vqw_ar_wide_prefill_layer: rows [%d, %lld) outside the handle's 0..%d", row0,
+              (long long)row0 + nrows, h->B - 1);
+    const int depth = (h->w.kernel_size - 1) * h->dil[l];
+    const int t_lo = arw_prefill_first(t_end, depth), nt = arw_prefill_count(t_end, depth);
+    VQW_CHECK(arw_prefill_covers(t_first, ld, t_end, depth),
+              "vqw_ar_wide_prefill_layer: columns [%d, %lld) do not cover layer %d's steps [%d, %d)", t_first, (long long)t_first + ld, l,
+              t_lo, t_end);
+    if (nt == 0) return 0;
+    VQW_CHECK(x, "vqw_ar_wide_prefill_layer: null x");
+    if (h->pending) {
+        const int rcw = vqw_ar_wide_wait(h);
+        if (rcw) return rcw;
+    }
+    hipStream_t st = (hipStream_t)s;
+    hipLaunchKernelGGL(arw_prefill_scatter_kernel, dim3(arw_tiles(nt), arw_tiles(nrows), h->w.R), dim3(256), 0, st, h->rings[l], depth,
+                       h->w.R, h->B, x, ld, t_first, t_lo, nt, row0, nrows);
+    VQW_LAUNCH_CHECK("vqw_ar_wide_prefill_layer");
+    return 0;
+}
+
+extern "C" int vqw_ar_wide_prefill_finish(vqw_ar_wide* h, int t_end, const float* audio_tail, const int32_t* code_tail,
+                                          vqw_stream_t s) {
+    VQW_CHECK(h, "vqw_ar_wide_prefill_finish: null handle");
+    VQW_CHECK(t_end >= 0, "vqw_ar_wide_prefill_finish: t_end=%d < 0", t_end);
+    VQW_CHECK((audio_tail == nullptr) != (code_tail == nullptr),
+              "vqw_ar_wide_prefill_finish: exactly one of audio_tail / code_tail must be given (%s)",
+              audio_tail ? "both are" : "neither is");
+    VQW_CHECK(h->n_codes > 0 ? code_tail != nullptr : audio_tail != nullptr,
+              "vqw_ar_wide_prefill_finish: %s handle takes %s", h->n_codes > 0 ? "a code-input" : "an audio",
+              h->n_codes > 0 ? "code_tail" : "audio_tail");
+    if (h->pending) {
+        const int rcw = vqw_ar_wide_wait(h);
+        if (rcw) return rcw;
+    }
+    if (t_end == 0) return 0;
+    hipStream_t st = (hipStream_t)s;
+    hipLaunchKernelGGL(arw_prefill_finish_kernel, dim3(vqw_cdiv(h->B * h->w.pre_k, 256)), dim3(256), 0, st, h->st, h->prev, h->xhist,
+                       h->B, h->w.pre_k, t_end, audio_tail, code_tail, h->mu);
+    VQW_LAUNCH_CHECK("vqw_ar_wide_prefill_finish");
+    h->steps = t_end;
     return 0;
 }
 

@@ -4,9 +4,9 @@ through vqw_ar_decode_* / vqw_ar_wide_* (ring buffers instead of FIFO queues, on
 
 FastGenerator (audio) and PriorGenerator (VQ codes) cut 1..8 rows into handles of the persistent kernel (or of the
 launch-per-phase path) and share FastGenerator._run; WideGenerator and WidePriorGenerator run up to 1024 rows on one
-vqw_ar_wide handle and share _WideBase._run.  What all four do alike (weight table, argument checks, uniforms, per-row sampling
-settings) is in the helpers in front of the classes.  Every public method refuses in the order mode, sampling settings,
-tensor arguments, before anything touches the model or the device."""
+vqw_ar_wide handle and share _WideBase._run and _WideBase._prefill.  What all four do alike (weight table, argument checks,
+uniforms, per-row sampling settings, a prompt's checks and tail) is in the helpers in front of the classes.  Every public
+method refuses in the order mode, sampling settings, tensor arguments, before anything touches the model or the device."""
 import ctypes as C
 import functools
 
@@ -175,6 +175,65 @@ def _row_slices(parts):
 
 
 PRIOR_RATIO = 64    # code steps per condition frame (prior.CODES_PER_FRAME)
+PREFILL_BUDGET = 2 << 30    # bytes of workspace one teacher-forced pass of a wide prefill may take (prefill_chunk)
+
+
+def prefill_chunk(batch, R, Mall, Tw, Tzw, budget=PREFILL_BUDGET):
+    """Rows per teacher-forced pass of a wide prefill (WideGenerator.prefill_prompt, chunk_rows=None): the largest chunk whose
+    pass workspace stays within `budget` bytes, at least 1, at most `batch`.  A pass over a window of Tw steps and Tzw condition
+    frames (wavenet.prefill_window) holds per row two layer inputs and the gated tensor, [R][Tw] each, and the projected
+    condition [Mall][Tzw]: 4 * (3 R Tw + Mall Tzw) bytes (25 MB at the reference widths with a saturated window, 19 MB of
+    it the three [R][Tw] tensors, where 1024 rows at once would be 26 GB).  Pure: no GPU, no model."""
+    for name, v in (('batch', batch), ('R', R), ('Mall', Mall)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError('prefill_chunk: %s must be an integer >= 1 (got %r)' % (name, v))
+    if Tw < 0 or Tzw < 0 or budget < 0:
+        raise ValueError('prefill_chunk: Tw, Tzw and budget must be >= 0 (got %r, %r, %r)' % (Tw, Tzw, budget))
+    per_row = 4 * (3 * R * Tw + Mall * Tzw)
+    return batch if per_row == 0 else max(1, min(batch, int(budget) // per_row))
+
+
+def even_chunk(batch, max_rows):
+    """The chunk that cuts `batch` rows into the fewest passes of at most max_rows rows, as evenly as they go:
+    ceil(batch / ceil(batch / max_rows)).  256 rows at 85 per pass are 4 x 64, not 85 + 85 + 85 + 1: the same number of
+    passes, none of one row.  Pure."""
+    for name, v in (('batch', batch), ('max_rows', max_rows)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError('even_chunk: %s must be an integer >= 1 (got %r)' % (name, v))
+    passes = -(-batch // max_rows)
+    return -(-batch // passes)
+
+
+def _check_prompt(prompt, encoding, B, Cc, ratio):
+    """The argument checks of FastGenerator.prefill / WideGenerator.prefill_prompt; returns T, the prompt's length."""
+    if not isinstance(prompt, torch.Tensor) or prompt.dtype != torch.float32 or prompt.dim() != 2 or prompt.shape[0] != B:
+        raise ValueError('prompt must be a float32 [%d][T] tensor' % B)
+    _check_encoding(encoding, B, Cc)
+    T = prompt.shape[1]
+    if T > encoding.shape[2] * ratio:
+        raise ValueError('a prompt of %d samples is longer than the encoding (%d frames x %d)' % (T, encoding.shape[2], ratio))
+    return T
+
+
+def _check_codes(codes, spk, B, Q):
+    """The argument checks of PriorGenerator.prefill / WidePriorGenerator.prefill_codes; returns T, the number of prompt codes."""
+    if (not isinstance(codes, torch.Tensor) or codes.dtype != torch.int32 or codes.dim() != 2 or codes.shape[0] != B
+            or not codes.is_cuda):
+        raise ValueError('codes must be an int32 [%d][T] tensor on the GPU' % B)
+    _check_speakers(spk, B)
+    T = codes.shape[1]
+    if T and (int(codes.min()) < 0 or int(codes.max()) >= Q):
+        raise ValueError('codes must lie in [0, %d)' % Q)
+    return T
+
+
+def _prefill_tail(x, T, pre_k):
+    """[B][pre_k]: the prompt's last pre_k values x[:, T - pre_k : T], zeros where that reaches before step 0 (ignored by the
+    library): the tail of vqw_ar_decode_prefill_finish / vqw_ar_wide_prefill_finish."""
+    n = min(T, pre_k)
+    tail = torch.zeros(x.shape[0], pre_k, dtype=x.dtype, device=x.device)
+    tail[:, pre_k - n:] = x[:, T - n:T]
+    return tail
 
 
 class _Closes:
@@ -203,6 +262,30 @@ class _WideBase(_Closes):
         """sess.run(wavenet.init_ops) (generate.py:105): empty queues, the next sample is step 0."""
         L.check(L.lib().vqw_ar_wide_reset(self._h, L.stream()))
 
+    def _prefill(self, x, cond, T, ratio, audio, chunk_rows):
+        """reset, then the prompt's layer inputs into the rings, chunk_rows rows per teacher-forced pass (each pass's
+        net[l] scattered by vqw_ar_wide_prefill_layer as soon as it is made), then the input history, the last value and the
+        step counter (vqw_ar_wide_prefill_finish).  A row's pass does not see the other rows, so its state does not depend
+        on the chunking.  chunk_rows None: prefill_chunk's choice for the prompt's window, cut evenly (even_chunk)."""
+        from .wavenet import prefill_window
+        if chunk_rows is not None and (isinstance(chunk_rows, bool) or not isinstance(chunk_rows, int) or chunk_rows < 1):
+            raise ValueError('chunk_rows must be an integer >= 1 or None (got %r)' % (chunk_rows,))
+        lib, st, m = L.lib(), L.stream(), self.model
+        L.check(lib.vqw_ar_wide_reset(self._h, st))
+        if T == 0:
+            return
+        _, s0, end = prefill_window(T, m.ks, m.dil, m.pre_k, ratio)
+        if chunk_rows is None:
+            chunk_rows = even_chunk(self.B, prefill_chunk(self.B, m.R, m.Mall, end - s0, (end - s0) // ratio))
+        for r0 in range(0, self.B, chunk_rows):
+            n = min(chunk_rows, self.B - r0)
+
+            def sink(l, net, t0):
+                L.check(lib.vqw_ar_wide_prefill_layer(self._h, l, L.ptr(net), net.shape[2], t0, T, r0, n, st))
+            m.decoder_states(x[r0:r0 + n], cond[r0:r0 + n], T, sink, ratio)
+        tail = _prefill_tail(x, T, m.pre_k)
+        L.check(lib.vqw_ar_wide_prefill_finish(self._h, T, L.ptr(tail) if audio else None, None if audio else L.ptr(tail), st))
+
     def _run(self, cond, Tz, ratio, n, mode, uniforms, settings, audio, return_probs):
         """n steps of every row on condition cond [B][Cc][Tz]; audio [B][n] or None (code mode).  Returns (indices, probs of
         the last step or None)."""
@@ -229,12 +312,25 @@ class WideGenerator(_WideBase):
     FastGenerator.  A row's indices, audio and probabilities do not depend on the batch it ran in (its size, the row's
     position, the other rows), and a run cut into several generate() calls equals the single run bit for bit.
 
-    There is no prefill: to continue a prompt, use FastGenerator.prefill + generate."""
+    The class has no prefill attribute, and that name stays FastGenerator's: a wide handle is prefilled in chunks of rows, by
+    prefill_prompt(), which takes FastGenerator.prefill's arguments and meaning plus chunk_rows."""
 
     def _create(self, h, w):
         L.check(L.lib().vqw_ar_wide_create(C.byref(h), C.byref(w), self.B))
         if self.model.levels != 256:     # the model's mu-law level (a created handle compands at 256)
             L.check(L.lib().vqw_ar_wide_set_levels(h, self.model.levels))
+
+    def prefill_prompt(self, prompt, encoding, ratio=None, chunk_rows=None):
+        """FastGenerator.prefill for a wide handle: every row in the state of reset() and T = prompt.shape[1] steps
+        teacher-forced on its prompt; the next generate() continues at step T.  prompt float32 [B][T] in [-1, 1] on the GPU;
+        encoding [B][Cc][Tz], the one the later generate calls use, with Tz * ratio >= T.  T = 0 is reset().  The
+        teacher-forced pass (VQVAE.decoder_states) runs over chunk_rows rows at a time (None: prefill_chunk's choice, which
+        bounds the pass's workspace, cut evenly).  A row's state, and so its continuation, does not depend on chunk_rows,
+        on the batch size, on the row's position or on the other rows, bit for bit."""
+        ratio = ratio or 64
+        T = _check_prompt(prompt, encoding, self.B, self.model.Cc, ratio)
+        L.require_cuda(prompt.contiguous(), encoding.contiguous())
+        self._prefill(prompt.contiguous(), encoding.contiguous(), T, ratio, True, chunk_rows)
 
     def generate(self, encoding, n_steps, mode='greedy', uniforms=None, ratio=None, return_probs=False,
                  temperature=1.0, top_k=0, top_p=1.0):
@@ -259,7 +355,8 @@ class WidePriorGenerator(_WideBase):
     variables, read in place (prior.use_ema_weights() first for the EMA shadows).  A row's codes and probabilities do not
     depend on the batch it ran in, and a run cut into several sample() calls equals the single run bit for bit.
 
-    There is no prefill: to continue a prompt of codes, use PriorGenerator.prefill + sample."""
+    The class has no prefill attribute, and that name stays PriorGenerator's: a wide handle is prefilled in chunks of rows, by
+    prefill_codes(), which takes PriorGenerator.prefill's arguments and meaning plus chunk_rows."""
     _n_name = 'n_frames'
 
     def __init__(self, prior, batch):
@@ -273,6 +370,15 @@ class WidePriorGenerator(_WideBase):
         """Empty history ("no code yet": a zero one-hot, not code 0); the next sample is step 0."""
         super().reset()
         self._t = 0
+
+    def prefill_codes(self, codes, spk, chunk_rows=None):
+        """PriorGenerator.prefill for a wide handle: every row in the state of reset() and T = codes.shape[1] steps
+        teacher-forced on its codes; the next sample() continues at step T.  codes int32 [B][T] in [0, k) on the GPU, spk
+        int64 [B] (the speakers the later sample calls use).  T = 0 is reset().  chunk_rows: as in WideGenerator.prefill_prompt."""
+        T = _check_codes(codes, spk, self.B, self.model.Q)
+        cond = self.model.speaker_condition(spk.contiguous(), max(1, -(-T // PRIOR_RATIO)))
+        self._prefill(codes.contiguous(), cond, T, PRIOR_RATIO, False, chunk_rows)
+        self._t = T
 
     def sample(self, n_frames, spk, mode='greedy', uniforms=None, return_probs=False, temperature=1.0, top_k=0, top_p=1.0):
         """n_frames codes per row, continuing from the current state.  spk int64 [B] on the GPU.  mode 'greedy' (argmax) or
@@ -339,12 +445,7 @@ class FastGenerator(_Closes):
         encoding [B][Cc][Tz] (model.encode), the one the later generate calls use, with Tz * ratio >= T.  T = 0 is reset().
         One teacher-forced pass over at most model.prefill_window's window (VQVAE.decoder_states), scattered into the rings."""
         ratio = ratio or 64
-        if not isinstance(prompt, torch.Tensor) or prompt.dtype != torch.float32 or prompt.dim() != 2 or prompt.shape[0] != self.B:
-            raise ValueError('prompt must be a float32 [%d][T] tensor' % self.B)
-        _check_encoding(encoding, self.B, self.model.Cc)
-        T = prompt.shape[1]
-        if T > encoding.shape[2] * ratio:
-            raise ValueError('a prompt of %d samples is longer than the encoding (%d frames x %d)' % (T, encoding.shape[2], ratio))
+        T = _check_prompt(prompt, encoding, self.B, self.model.Cc, ratio)
         L.require_cuda(prompt.contiguous(), encoding.contiguous())
         self._prefill(prompt.contiguous(), encoding.contiguous(), T, ratio, audio=True)
 
@@ -363,10 +464,7 @@ class FastGenerator(_Closes):
             for h, r in zip(self._hs, rows):
                 L.check(lib.vqw_ar_decode_prefill_layer(h, l, L.ptr(net[r]), net.shape[2], s0, T, st))
         self.model.decoder_states(x, cond, T, sink, ratio)
-        pk = self.model.pre_k
-        n = min(T, pk)
-        tail = torch.zeros(self.B, pk, dtype=x.dtype, device=x.device)
-        tail[:, pk - n:] = x[:, T - n:T]
+        tail = _prefill_tail(x, T, self.model.pre_k)
         for h, r in zip(self._hs, rows):
             L.check(lib.vqw_ar_decode_prefill_finish(h, T, L.ptr(tail[r]) if audio else None, None if audio else L.ptr(tail[r]), st))
 
@@ -450,13 +548,7 @@ class PriorGenerator(FastGenerator):
         """Leave every row in the state it would have after reset() and T = codes.shape[1] steps teacher-forced on its codes
         (the input of step t is c[t-1], no code at t = 0): the next sample() continues at step T.  codes int32 [B][T] in [0, k)
         on the GPU, spk int64 [B] (the speakers the later sample calls use).  T = 0 is reset()."""
-        if (not isinstance(codes, torch.Tensor) or codes.dtype != torch.int32 or codes.dim() != 2 or codes.shape[0] != self.B
-                or not codes.is_cuda):
-            raise ValueError('codes must be an int32 [%d][T] tensor on the GPU' % self.B)
-        _check_speakers(spk, self.B)
-        T = codes.shape[1]
-        if T and (int(codes.min()) < 0 or int(codes.max()) >= self.model.Q):
-            raise ValueError('codes must lie in [0, %d)' % self.model.Q)
+        T = _check_codes(codes, spk, self.B, self.model.Q)
         cond = self.model.speaker_condition(spk.contiguous(), max(1, -(-T // PRIOR_RATIO)))
         self._prefill(codes.contiguous(), cond, T, PRIOR_RATIO, audio=False)
         self._t = T
