@@ -384,6 +384,36 @@ int vqw_cond_proj_dgrad(const float* w, const float* dce, float* dcond, float* s
 int vqw_cond_proj_dgrad_scratch_floats(int B, int Cc, int Mall, int Tz, int64_t* out);
 
 /* ------------------------------------------------------------------------------------
+ * The 2019 decoder's conditioning conv over the latents (arXiv 1901.08810; Decoder/decoder.py:22-28 names it,
+ * Decoder/decoder_ops.py:31-32 builds it: Conv1D(filters=C, kernel_size=k, padding='same') between the VQ and the speaker
+ * concat).  z / dz [B][D][Tz], out / dout [B][C][Tz], each at a batch stride of its own (>= its row size: out and dout are
+ * the first C rows of [B][Cc][Tz] buffers); w / dw [k][D][C] (the Keras layout), bias / db [C].  pl = (k - 1) / 2, zero
+ * padding per utterance, rows independent:
+ *   fwd:    out[b][o][t] = bias[o] + sum_{j<k} sum_{d<D} w[j][d][o] z[b][d][t + j - pl]
+ *           one fmaf chain from bias[o], j ascending, inside it d ascending; a tap whose frame lies outside [0, Tz) is left out
+ *   dgrad:  dz[b][d][s]  = sum_{j<k} sum_{o<C} w[j][d][o] dout[b][o][s - j + pl]
+ *           one fmaf chain from +0.0f, j ascending, inside it o ascending; taps outside [0, Tz) left out; every element written
+ *   wgrad:  dw[j][d][o] += sum_{b,t} z[b][d][t + j - pl] dout[b][o][t];   db[o] += sum_{b,t} dout[b][o][t]
+ *           the (b, 64-frame chunk) pairs, n = B * ceil(Tz / 64) of them in ascending (b, t), are cut into ns = min(n, 16)
+ *           ranges [s n / ns, (s + 1) n / ns); a range's partial sum is one chain from +0.0f over its frames in ascending
+ *           (b, t) (fmaf for dw, a plain add for db; a frame outside [0, Tz) enters as a zero), written to
+ *           scratch[s][k D C + C]; then total = (..(p_0 + p_1) + ..) + p_{ns-1} and dw / db += total: ONE add per element.
+ *           scratch: vqw_cond_conv_wgrad_scratch_floats() floats, every one of them written.
+ * Every sum runs in that one order: an element of out / dz depends on its own batch row only (row b computed alone has the
+ * same bits as inside a batch), the order of a dw / db sum depends on (B, Tz) only, nothing is atomic, two launches on the
+ * same operands give the same bits.  fp32 in every engine mode.
+ * Any B, D, Tz >= 1 (Tz <= 2^24, D <= 2^16); C a multiple of 16 (<= 2^16); k odd, 1 <= k <= 7.  Refused before any launch:
+ * null pointers, those sizes, a batch stride below the row size, too little scratch, and an output (out; dz; dw, db, scratch)
+ * whose range -- (B - 1) * stride + rows * Tz floats -- overlaps another operand's.                                        */
+int vqw_cond_conv_fwd(const float* z, int64_t z_bstride, const float* w, const float* bias, float* out, int64_t out_bstride,
+                      int B, int D, int C, int Tz, int k, vqw_stream_t s);
+int vqw_cond_conv_dgrad(const float* w, const float* dout, int64_t dout_bstride, float* dz, int64_t dz_bstride, int B, int D,
+                        int C, int Tz, int k, vqw_stream_t s);
+int vqw_cond_conv_wgrad(const float* z, int64_t z_bstride, const float* dout, int64_t dout_bstride, float* dw, float* db,
+                        float* scratch, int64_t scratch_floats, int B, int D, int C, int Tz, int k, vqw_stream_t s);
+int vqw_cond_conv_wgrad_scratch_floats(int B, int D, int C, int Tz, int k, int64_t* out);
+
+/* ------------------------------------------------------------------------------------
  * Fused TF-1.x Adam + ExponentialMovingAverage step over a flat buffer --
  * model.py:116-128:
  *   g = grad*grad_scale; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;

@@ -160,6 +160,10 @@ SIGNATURES = {
     'vqw_cond_proj_wgrad': (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _fp]),
     'vqw_cond_proj_dgrad': (_i, [_fp, _fp, _fp, _fp, C.c_int64, _i, _i, _i, _i, _fp]),
     'vqw_cond_proj_dgrad_scratch_floats': (_i, [_i, _i, _i, _i, C.POINTER(C.c_int64)]),
+    'vqw_cond_conv_fwd': (_i, [_fp, _i64, _fp, _fp, _fp, _i64, _i, _i, _i, _i, _i, _fp]),
+    'vqw_cond_conv_dgrad': (_i, [_fp, _fp, _i64, _fp, _i64, _i, _i, _i, _i, _i, _fp]),
+    'vqw_cond_conv_wgrad': (_i, [_fp, _i64, _fp, _i64, _fp, _fp, _fp, _i64, _i, _i, _i, _i, _i, _fp]),
+    'vqw_cond_conv_wgrad_scratch_floats': (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int64)]),
     'vqw_adam_ema_step': (_i, [_fp, _fp, _fp, _fp, _fp, _sz, _f, _f, _f, _f, _f, _f, _fp]),
     'vqw_adam_ema_step_guarded': (_i, [_fp, _fp, _fp, _fp, _fp, _sz, _f, _f, _f, _f, _f, _f, _fp, _fp]),
     'vqw_adam_ema_step_scaled': (_i, [_fp, _fp, _fp, _fp, _fp, _sz, _f, _f, _f, _f, _f, _f, _fp, _fp, _fp]),

@@ -17,7 +17,7 @@ LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, os.environ.get('VQW_LIB_NAME', 'libvqwave.so'))
 # the longest compiles first (the pool takes sources in list order): ar_persist, then the fp16x3 engine's gate backward and convs
 SOURCES = ['ar_persist', 'f16x3_gate_bwd', 'f16x3_conv', 'f16x3_wgrad', 'f16x3_sconv', 'common', 'conv_gemm', 'wgrad_gemm', 'pointwise', 'cond_proj',
-           'vq', 'wrappers', 'ar_decode', 'ar_wide', 'f16x3_planes', 'prior', 'score', 'gradnorm', 'jitter', 'sample', 'dtw']
+           'vq', 'wrappers', 'ar_decode', 'ar_wide', 'f16x3_planes', 'prior', 'score', 'gradnorm', 'jitter', 'sample', 'dtw', 'cond_conv']
 # -pragma-unroll-threshold: the fully unrolled epilogues over 256 accumulator registers are longer than LLVM's default bound for
 # `#pragma unroll` (16 k instructions); a loop it leaves rolled indexes the accumulators dynamically, i.e. puts them in scratch
 FLAGS = ['-O3', '--offload-arch=gfx950', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function', '-mllvm', '-pragma-unroll-threshold=65536'] + \

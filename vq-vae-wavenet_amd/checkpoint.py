@@ -68,6 +68,10 @@ def load(model, path, ema_to_live=False, strict=True):
         hits = [k for k in state if k.endswith('/' + name)]        # tolerate slot-scope prefixes of a real TF checkpoint
         return hits[0] if len(hits) == 1 else None
     live, ema, m, v = _views(model)
+    conv = 'decoder/condition_conv/kernel'      # (say which key differs, not which local_condition kernel's shape does)
+    if (find(conv) is not None) != (conv in live):
+        raise ValueError("checkpoint %s was written %s 'condition_conv' and the model is built %s it: the shapes of the decoder's "
+                         "local_condition kernels differ" % ((path,) + (('with', 'without') if conv not in live else ('without', 'with'))))
     used = []
     for sfx, group, required in (('', live, True), (EMA, ema, strict), (M1, m, False), (M2, v, False)):
         for name, view in group.items():

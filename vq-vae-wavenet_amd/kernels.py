@@ -911,6 +911,50 @@ def cond_proj_dgrad(w, dce, dcond, scratch, *, B, Cc, Mall, Tz):
     L.check(L.lib().vqw_cond_proj_dgrad(L.ptr(w), L.ptr(dce), L.ptr(dcond), L.ptr(scratch), scratch.numel(), B, Cc, Mall, Tz, L.stream()))
 
 
+def _cond_conv_shapes(z, out, w, z_bstride, out_bstride):
+    """(B, D, C, Tz, k, z_bstride, out_bstride) of z [B][>= D][Tz], out [B][>= C][Tz] and w [k][D][C]."""
+    k, D, C_ = w.shape
+    B, Tz = z.shape[0], z.shape[-1]
+    z_bstride, out_bstride = z_bstride or D * Tz, out_bstride or C_ * Tz
+    _need(z, (B - 1) * z_bstride + D * Tz, 'z / dz')
+    _need(out, (B - 1) * out_bstride + C_ * Tz, 'out / dout')
+    _need(w, k * D * C_, 'w')
+    return B, D, C_, Tz, k, z_bstride, out_bstride
+
+
+def cond_conv_fwd(z, w, bias, out, *, z_bstride=0, out_bstride=0):
+    """vqw_cond_conv_fwd: out[b][o][t] = bias[o] + sum_{j,d} w[j][d][o] z[b][d][t + j - (k-1)/2], zero padding per row.  w
+    [k][D][C]; z / out are [B][>= D][Tz] / [B][>= C][Tz] buffers whose first rows are used (batch strides default to the rows)."""
+    L.require_cuda(z, w, bias, out)
+    B, D, C_, Tz, k, zb, ob = _cond_conv_shapes(z, out, w, z_bstride, out_bstride)
+    _need(bias, C_, 'bias')
+    L.check(L.lib().vqw_cond_conv_fwd(L.ptr(z), zb, L.ptr(w), L.ptr(bias), L.ptr(out), ob, B, D, C_, Tz, k, L.stream()))
+
+
+def cond_conv_dgrad(w, dout, dz, *, dout_bstride=0, dz_bstride=0):
+    """vqw_cond_conv_dgrad: dz[b][d][s] = sum_{j,o} w[j][d][o] dout[b][o][s - j + (k-1)/2]; every element of dz is written."""
+    L.require_cuda(w, dout, dz)
+    B, D, C_, Tz, k, zb, ob = _cond_conv_shapes(dz, dout, w, dz_bstride, dout_bstride)
+    L.check(L.lib().vqw_cond_conv_dgrad(L.ptr(w), L.ptr(dout), ob, L.ptr(dz), zb, B, D, C_, Tz, k, L.stream()))
+
+
+def cond_conv_wgrad_scratch(B, D, C_, Tz, k):
+    n = C.c_int64(0)
+    L.check(L.lib().vqw_cond_conv_wgrad_scratch_floats(B, D, C_, Tz, k, C.byref(n)))
+    return int(n.value)
+
+
+def cond_conv_wgrad(z, dout, dw, db, scratch, *, z_bstride=0, dout_bstride=0):
+    """vqw_cond_conv_wgrad: dw[j][d][o] += sum_{b,t} z[b][d][t + j - (k-1)/2] dout[b][o][t], db[o] += sum_{b,t} dout[b][o][t]
+    (one add per element, no atomics); scratch: cond_conv_wgrad_scratch(...) floats."""
+    L.require_cuda(z, dout, dw, db, scratch)
+    B, D, C_, Tz, k, zb, ob = _cond_conv_shapes(z, dout, dw, z_bstride, dout_bstride)
+    _need(db, C_, 'db')
+    _need(scratch, cond_conv_wgrad_scratch(B, D, C_, Tz, k), 'scratch')
+    L.check(L.lib().vqw_cond_conv_wgrad(L.ptr(z), zb, L.ptr(dout), ob, L.ptr(dw), L.ptr(db), L.ptr(scratch), scratch.numel(),
+                                        B, D, C_, Tz, k, L.stream()))
+
+
 def adam_ema_step(param, grad, m, v, ema, *, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, decay=0.999,
                   grad_scale=1.0, skip=None, scale=None):
     """skip: device int32 read when the kernel runs; non-zero = the step changes nothing (vqw_adam_ema_step_guarded).

@@ -14,6 +14,17 @@ from .encoders import Encoder64, Encoder2019, EncoderMagenta
 from .wavenet import DEFAULT_ENGINE, WaveNet, load_configs, mix_seed, prefill_window  # noqa: F401  (load_configs, prefill_window, DEFAULT_ENGINE: callers' names)
 
 
+def cond_conv_config(cfg):
+    """(C, k) of the decoder's conditioning conv from a model configuration: 'condition_conv' output channels (absent or 0:
+    off, C = 0) and 'condition_conv_kernel' taps (default 3).  Refuses by key what the kernels do not take."""
+    C, k = cfg.get('condition_conv', 0), cfg.get('condition_conv_kernel', 3)
+    if isinstance(C, bool) or not isinstance(C, int) or C < 0 or C % 16 != 0:
+        raise ValueError("'condition_conv' must be a positive multiple of 16 channels, or 0 / absent for none (got %r)" % (C,))
+    if isinstance(k, bool) or not isinstance(k, int) or k % 2 != 1 or not 1 <= k <= 7:
+        raise ValueError("'condition_conv_kernel' must be odd and in 1..7 (got %r)" % (k,))
+    return C, k
+
+
 class VQVAE(WaveNet):
     """model.py:7-159.  encoder '64' + VQ + speaker embedding + WaveNet decoder."""
 
@@ -49,8 +60,12 @@ class VQVAE(WaveNet):
         # condition rows are always zero, their kernel rows never receive a gradient)
         self.spk_table = self.Cs > 0
         self.Cs_eff = self.Cs if self.spk_table else (num_speakers + 15) // 16 * 16
-        self.Cc_ref = self.D + (self.Cs if self.spk_table else num_speakers)      # the reference's condition width
-        self.Cc = self.D + self.Cs_eff
+        # the 2019 decoder's conditioning conv over the latents (condition_conv channels, condition_conv_kernel taps):
+        # between the VQ and the speaker concat.  Dc: the latent rows of the condition
+        self.cconv, self.cconv_k = cond_conv_config(model_cfg)
+        self.Dc = self.cconv or self.D
+        self.Cc_ref = self.Dc + (self.Cs if self.spk_table else num_speakers)      # the reference's condition width
+        self.Cc = self.Dc + self.Cs_eff
         self.encoder = encoders[self.enc](self.D, self.F)     # (constants only: every call hands it the model, encoders.py)
 
     def _front_segments(self, seg):
@@ -59,6 +74,9 @@ class VQVAE(WaveNet):
             seg['speaker_embedding'] = (self.S_spk, self.Cs)
         seg.update(self.encoder.segments())
         seg['embedding'] = (self.Kc, self.D)
+        if self.cconv:
+            seg['condition_conv_w'] = (self.cconv_k, self.D, self.cconv)      # [k][D][C]: the Keras layout
+            seg['condition_conv_b'] = (self.cconv,)
 
     def _init_front(self, P, uus, glorot):
         """Initial values of the _front_segments (hook)."""
@@ -70,6 +88,8 @@ class VQVAE(WaveNet):
         self.bn_mean = torch.zeros(6 * self.F + self.D, device=self.dev)   # moving stats (never updated:
         self.bn_var = torch.ones(6 * self.F + self.D, device=self.dev)     #  SURVEY.md Appendix A-3)
         P['embedding'].copy_(uus((self.Kc, self.D), self.Kc, 1.7))                  # model.py:47-49
+        if self.cconv:          # Keras's defaults: glorot-uniform kernel, zero bias (the flat buffer starts as zeros)
+            P['condition_conv_w'].copy_(glorot((self.cconv_k, self.D, self.cconv), self.cconv_k, self.D, self.cconv))
 
     def _front_scratch(self):
         """Transposed-kernel scratch of the encoder's input-gradient GEMMs (hook)."""
@@ -82,6 +102,9 @@ class VQVAE(WaveNet):
         self.encoder.named(self, V, out, bn_stats)
         if self.use_vq:          # (the reference only creates the codebook under use_vq, model.py:137-138)
             out['embedding/embedding'] = V['embedding']
+        if self.cconv:
+            out['decoder/condition_conv/kernel'] = V['condition_conv_w']
+            out['decoder/condition_conv/bias'] = V['condition_conv_b']
 
     def _front_workspace(self, B, T, train):
         """The (B, T) workspace up to the condition: inputs / labels, encoder + VQ buffers, ws['cond'] (hook)."""
@@ -97,11 +120,18 @@ class VQVAE(WaveNet):
         ws['e_k'] = e(B, D, Tz)
         ws['mind'] = e(B, Tz)
         ws['cond'] = e(B, self.Cc, Tz)
+        if self.cconv:          # z_q, what the conditioning conv reads (the jitter puts a second such buffer between them)
+            ws['zq'] = e(B, D, Tz)
         return ws
 
     def _front_workspace_train(self, ws):
         """Backward buffers of the VQ (hook; the encoder's are made with its forward buffers)."""
-        ws['dz'] = A.empty(ws['B'], self.D, ws['Tz'], device=self.dev)
+        B, D, Tz = ws['B'], self.D, ws['Tz']
+        ws['dz'] = A.empty(B, D, Tz, device=self.dev)
+        if self.cconv:          # d z_q (straight into dz where nothing is quantised) and the partial sums of the conv's weight gradients
+            if self.use_vq:
+                ws['dzq'] = A.empty(B, D, Tz, device=self.dev)
+            ws['cconv_scratch'] = A.empty(K.cond_conv_wgrad_scratch(B, D, self.cconv, Tz, self.cconv_k), device=self.dev)
 
     # ------------------------------------------------------------------ forward pieces
     def _encode(self, x, spk, ws, save=True):
@@ -111,6 +141,8 @@ class VQVAE(WaveNet):
 
     def _quantise(self, spk, ws):
         """model.py:57-74 (VQ) + model.py:22-27 / decoder_ops.py:39-43 (speaker embedding tiled over time)."""
+        if self.cconv:
+            return self._quantise_conv(spk, ws)
         P, D, Tz = self.P, self.D, ws['Tz']
         # time jitter (a train_step's passes only): z_q goes to a buffer of its own and the jitter kernel fills the
         # condition's first D rows from it; idx, e_k, mind (the VQ / commitment losses) are those of the un-jittered latents
@@ -133,6 +165,31 @@ class VQVAE(WaveNet):
         K.speaker_tile_fwd(P['speaker_embedding'] if self.spk_table else self.onehot, spk, ws['cond'],
                            cond_bstride=self.Cc * Tz, row0=D, Cs=self.Cs_eff, Tz=Tz)
 
+    def _quantise_conv(self, spk, ws):
+        """_quantise with the conditioning conv: VQ -> ws['zq'], jitter (a train_step's passes only) -> ws['zj'],
+        conv of whichever is last -> the condition's first Dc rows, speaker rows behind them.  idx, e_k, mind, the losses and
+        the codebook statistics are those of the un-jittered, un-convolved latents."""
+        P, D, Tz, zq = self.P, self.D, ws['Tz'], ws['zq']
+        jit = ws['jittered'] = self._jitter_step is not None and self._time_jitter > 0.0
+        if self.use_vq:
+            K.vq_nearest_fwd(ws['z_e'], P['embedding'], idx=ws['idx'], e_k=ws['e_k'], zq=zq, zq_bstride=D * Tz, mind=ws['mind'])
+            if self._codebook_ema > 0.0:
+                ws['cb_stats'] = self._jitter_step is not None
+                if ws['cb_stats']:
+                    self._cluster_stats(ws, self._jitter_step)
+        else:
+            zq.copy_(ws['z_e'])
+            ws['idx'].zero_()
+            ws['mind'].zero_()
+        if jit:
+            self._jitter_buffers(ws)
+            ws['jitter_u'].copy_(self.jitter_uniforms(ws['B'], Tz, self._jitter_step))
+            K.time_jitter_fwd(zq, ws['jitter_u'], ws['zj'], ws['jitter_src'], p=self._time_jitter, D=D)
+        ws['cconv_in'] = ws['zj'] if jit else zq
+        K.cond_conv_fwd(ws['cconv_in'], P['condition_conv_w'], P['condition_conv_b'], ws['cond'], out_bstride=self.Cc * Tz)
+        K.speaker_tile_fwd(P['speaker_embedding'] if self.spk_table else self.onehot, spk, ws['cond'],
+                           cond_bstride=self.Cc * Tz, row0=self.Dc, Cs=self.Cs_eff, Tz=Tz)
+
     # ------------------------------------------------------------------ time jitter (DESIGN 3.10)
     @property
     def time_jitter(self):
@@ -147,11 +204,13 @@ class VQVAE(WaveNet):
         self._time_jitter = float(value)
 
     def _jitter_buffers(self, ws):
-        """z_q before the jitter, its gradient, the step's uniforms and source frames: made at the first jittered step."""
-        if 'zq' not in ws:
+        """z_q before the jitter, its gradient, the step's uniforms and source frames: made at the first jittered step.  (With
+        the conditioning conv z_q has its buffer already, and the jitter's own output and its gradient are made here: zj, dzj.)"""
+        if 'jitter_src' not in ws:
             B, D, Tz = ws['B'], self.D, ws['Tz']
+            a, b = ('zj', 'dzj') if self.cconv else ('zq', 'dzq')
             with A.record(ws['_poison']):
-                ws['zq'], ws['dzq'] = A.empty(B, D, Tz, device=self.dev), A.empty(B, D, Tz, device=self.dev)
+                ws[a], ws[b] = A.empty(B, D, Tz, device=self.dev), A.empty(B, D, Tz, device=self.dev)
                 ws['jitter_u'] = A.empty(B, Tz, device=self.dev)
             ws['jitter_src'] = torch.zeros(B, Tz, dtype=torch.int32, device=self.dev)
         return ws
@@ -416,17 +475,27 @@ class VQVAE(WaveNet):
             self.grad_sync.bucket_ready(self.seg_off['pre_w'][0], self.n_flat)
         # ---- speaker embedding + VQ (model.py:22-27, 57-74, 99-106)
         if self.spk_table:
-            K.speaker_tile_bwd(ws['dcond'], spk, G['speaker_embedding'], dcond_bstride=self.Cc * Tz, row0=D, Cs=self.Cs, Tz=Tz)
+            K.speaker_tile_bwd(ws['dcond'], spk, G['speaker_embedding'], dcond_bstride=self.Cc * Tz, row0=self.Dc, Cs=self.Cs, Tz=Tz)
         nd = float(B * Tz * D)
         dzq, dzq_bs = ws['dcond'], self.Cc * Tz
-        if ws.get('jittered'):      # d z_q from d cond through the transposed gather (straight into dz where nothing is quantised)
+        if self.cconv:
+            # the conditioning conv: weight and bias gradients, then d z_q from d cond's first Dc rows -- through the jitter's
+            # transposed gather where the pass jittered (straight into dz where nothing is quantised)
+            K.cond_conv_wgrad(ws['cconv_in'], ws['dcond'], G['condition_conv_w'], G['condition_conv_b'], ws['cconv_scratch'],
+                              dout_bstride=self.Cc * Tz)
+            dzq, dzq_bs = ws['dzq'] if self.use_vq else ws['dz'], D * Tz
+            dzc = ws['dzj'] if ws.get('jittered') else dzq
+            K.cond_conv_dgrad(self.P['condition_conv_w'], ws['dcond'], dzc, dout_bstride=self.Cc * Tz)
+            if ws.get('jittered'):
+                K.time_jitter_bwd(dzc, ws['jitter_src'], dzq, D=D)
+        elif ws.get('jittered'):      # d z_q from d cond through the transposed gather (straight into dz where nothing is quantised)
             dzq, dzq_bs = ws['dzq'] if self.use_vq else ws['dz'], D * Tz
             K.time_jitter_bwd(ws['dcond'], ws['jitter_src'], dzq, D=D, dout_bstride=self.Cc * Tz)
         if self.use_vq:
             K.vq_nearest_bwd(ws['z_e'], ws['e_k'], ws['idx'], dzq=dzq, dzq_bstride=dzq_bs, dz_e=ws['dz'],
                              demb=None if self._codebook_ema > 0.0 else G['embedding'],      # (moving averages: no codebook-loss gradient)
                              cscale=2.0 * self.beta / nd, escale=2.0 / nd, K=self.Kc)
-        elif not ws.get('jittered'):
+        elif not ws.get('jittered') and not self.cconv:
             ws['dz'].copy_(ws['dcond'][:, :D])
         self.encoder.backward(self, x, ws)
 
@@ -446,7 +515,7 @@ class VQVAE(WaveNet):
             return ws['cond'].clone()
         cond = ws['cond'].repeat(B, 1, 1)
         K.speaker_tile_fwd(self.P['speaker_embedding'] if self.spk_table else self.onehot, spk, cond,
-                           cond_bstride=self.Cc * ws['Tz'], row0=self.D, Cs=self.Cs_eff, Tz=ws['Tz'])
+                           cond_bstride=self.Cc * ws['Tz'], row0=self.Dc, Cs=self.Cs_eff, Tz=ws['Tz'])
         return cond
 
     def encode_codes(self, x, spk):
@@ -470,9 +539,13 @@ class VQVAE(WaveNet):
         if spk.numel() != B:
             raise ValueError('condition_from_codes: %d code rows for %d speaker ids' % (B, spk.numel()))
         cond = torch.empty(B, self.Cc, Tz, device=self.dev)
-        cond[:, :self.D] = self.P['embedding'][codes.long()].permute(0, 2, 1)      # e_k = the chosen rows, exactly
+        z_q = self.P['embedding'][codes.long()].permute(0, 2, 1)                   # e_k = the chosen rows, exactly
+        if self.cconv:          # the conv encode() runs on them
+            K.cond_conv_fwd(z_q.contiguous(), self.P['condition_conv_w'], self.P['condition_conv_b'], cond, out_bstride=self.Cc * Tz)
+        else:
+            cond[:, :self.D] = z_q
         K.speaker_tile_fwd(self.P['speaker_embedding'] if self.spk_table else self.onehot, spk, cond,
-                           cond_bstride=self.Cc * Tz, row0=self.D, Cs=self.Cs_eff, Tz=Tz)
+                           cond_bstride=self.Cc * Tz, row0=self.Dc, Cs=self.Cs_eff, Tz=Tz)
         return cond
 
     def state_dict(self):
@@ -484,9 +557,16 @@ class VQVAE(WaveNet):
         if self._codebook_ema > 0.0:
             self._codebook_state()
             sd.update(vq_ema_n=self.vq_ema_n, vq_ema_m=self.vq_ema_m)
+        if self.cconv:          # (channels, taps): a model of another setting refuses the state by this key
+            sd['condition_conv'] = torch.tensor([self.cconv, self.cconv_k], dtype=torch.int64)
         return sd
 
     def load_state_dict(self, sd):
+        theirs = tuple(int(v) for v in sd['condition_conv']) if 'condition_conv' in sd else (0, self.cconv_k)
+        if theirs[0] != self.cconv or (self.cconv and theirs[1] != self.cconv_k):
+            raise ValueError("load_state_dict: 'condition_conv' is %d (kernel %d) in the state and %d (kernel %d) in the model: the "
+                             "decoder's local_condition kernels have %d rows there and %d here"
+                             % (theirs + (self.cconv, self.cconv_k, (theirs[0] or self.D) + self.Cs_eff, self.Cc)))
         super().load_state_dict(sd)
         for k in ('bn_mean', 'bn_var'):
             getattr(self, k).copy_(sd[k].to(self.dev))
